@@ -3,12 +3,18 @@
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--reps R] [--log2n 20]
                     [--workload prove|prove_from_r1cs|prove_sharded|prove_pinocchio|msm_g1|msm_sharded] [--logical-shards S]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps once and prints the line: every check and every figure that needs runs of
+its own (proof checks, the extras below, CPU baselines, the strong-scaling section, repetitions) is taken with --full only.
+--dump-outputs DIR writes the last timed step's result (the proof's points, or the MSM's point) as DIR/<name>.npy; the inputs
+are seeded, so two builds given the same arguments can be compared array by array.
 
 A "step" is one full groth16.GenerateProofs (groth16/groth16.go:225-278: H(x) = P(x)/Z(x), the
 five MSMs, the O(1) tail) over a synthetic instance with n = 2^log2n constraints, m = n + 1
 variables, NPublic = 1 (BASELINE.json configs[2]); the proving key, w and px are resident in HBM
 before the timed region.  The timed region (K steps between barrier + synchronize) is repeated R
-times; `ms_per_step` / `value` are the MEDIAN repetition, every repetition is listed.
+times (R = 1, or 5 with --full); `ms_per_step` / `value` are the MEDIAN repetition, every repetition is listed.
 
 N > 1 starts however it is invoked:
   * under torch.distributed.run (WORLD_SIZE = N in the environment): one rank per GPU; the control plane (barriers, the max over
@@ -22,7 +28,7 @@ N > 1 starts however it is invoked:
     the same command line under torch.distributed.run instead.
 Either way `value` is the WEAK-scaling figure: every GPU proves independent instances of the same circuit with its own
 witness (the batch-of-proofs partition of BASELINE.json configs[4]; no data-path collective), N * n * K / (max time);
-and the SAME line carries the STRONG-scaling figures under `strong` -- ONE 2^log2n proof whose MSM term ranges are split
+and with --full the SAME line carries the STRONG-scaling figures under `strong` -- ONE 2^log2n proof whose MSM term ranges are split
 over the N GPUs (both routes: replicated H(x) / owner's values scattered) and ONE 2^22-term G1 MSM split the same way
 (BASELINE configs[3]), each checked against the single-device result / the naive-loop golden -- plus `rccl` (ranks the
 communicator saw, mode, collectives executed) and `devices` (ordinals, hipDeviceCanAccessPeer matrix).
@@ -32,11 +38,11 @@ SURVEY 8e).  With `--logical-shards S` on ONE GPU the S shards run as S logical 
 (gs_groth16_prove_multi / gs_msm_g1_multi): per-shard times are measured and an S-GPU figure is MODELLED
 from them (labelled as such) -- there is no multi-GPU hardware behind a gpurun call.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), including
+Prints ONE JSON line on rank 0, including
   roofline:     the dominant kernel (G1 bucket accumulation) against the HBM roofline,
   cpu_baseline: the reference algorithm (oracle/gs_oracle.c: naive MulScalar/Add loops + schoolbook
-                Div) timed on ONE host core on a bounded sample (rank 0, N = 1 only),
-and, on the default single-GPU run, the second half of BASELINE's metric (G1-MSM terms/s at 2^20 and
+                Div) timed on ONE host core on a bounded sample (rank 0, N = 1, --full only),
+and, on the single-GPU run with --full, the second half of BASELINE's metric (G1-MSM terms/s at 2^20 and
 2^16), the blocking-call latency, witness -> proof from the resident sparse R1CS, the host-buffer
 entry point, and the reference's own compiled prover (wasm under node) on a small instance.
 """
@@ -441,17 +447,47 @@ def cold_path(inst, pk, n, r_, s_, ref_proof):
 
 
 def pipelined(begin, end, count, depth, on_done=None):
-    tickets = []
+    """`count` operations, `depth` in flight; returns what the last end() returned."""
+    tickets, last = [], None
     for _ in range(count):
         tickets.append(begin())
         if len(tickets) == depth:
-            end(tickets.pop(0))
+            last = end(tickets.pop(0))
             if on_done:
                 on_done()
     while tickets:
-        end(tickets.pop(0))
+        last = end(tickets.pop(0))
         if on_done:
             on_done()
+    return last
+
+
+def _limbs(x):
+    """A field element (int < 2^256) -> eight 32-bit limbs, least significant first (float64 holds each exactly); nested tuples of
+    them (the coordinates of a point) -> nested lists."""
+    if isinstance(x, int):
+        return [float((x >> (32 * i)) & 0xFFFFFFFF) for i in range(8)]
+    return [_limbs(y) for y in x]
+
+
+def _point_array(p):
+    """A point as the library returns it (None = an MSM at infinity, written as (0, 0)) -> float64 limbs."""
+    return np.array(_limbs((0, 0) if p is None else p), dtype=np.float64)
+
+
+def dump_outputs(out_dir, result):
+    """--dump-outputs: what the timed path returned in its last step, one DIR/<name>.npy per array (float64 limbs, see _limbs).
+    result: a groth16 / snark Proof, an MSM point, or a list of proofs (one per device; stacked along a leading axis)."""
+    os.makedirs(out_dir, exist_ok=True)
+    proofs = result if isinstance(result, list) else [result]
+    fields = getattr(proofs[0], "FIELDS", ("PiA", "PiB", "PiC")) if hasattr(proofs[0], "PiA") else None
+    arrays = ({k: np.stack([_point_array(getattr(p, k)) for p in proofs]) for k in fields} if fields else
+              {"msm_g1": np.stack([_point_array(p) for p in proofs])})
+    if not isinstance(result, list):
+        arrays = {k: v[0] for k, v in arrays.items()}
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+    return sorted(arrays)
 
 
 def live_pmc_traffic(args):
@@ -1059,10 +1095,13 @@ def main_one_process(args):
         sync_all()
         rep_elapsed.append(time.perf_counter() - t0)
     elapsed = statistics.median(rep_elapsed)
-    good = all(groth16.VerifyProof(inst.vk, last[-N + d], [xs[d]]) and not groth16.VerifyProof(inst.vk, last[-N + d], [xs[(d + 1) % N] if N > 1 else (xs[d] + 1) % R])
-               for d in range(N))
-    if not good:
-        raise SystemExit("bench.py: groth16.VerifyProof rejected a device's proof (or accepted it for another device's public input)")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last[-N:])             # the last step: one proof per device
+    if args.full:
+        good = all(groth16.VerifyProof(inst.vk, last[-N + d], [xs[d]]) and not groth16.VerifyProof(inst.vk, last[-N + d], [xs[(d + 1) % N] if N > 1 else (xs[d] + 1) % R])
+                   for d in range(N))
+        if not good:
+            raise SystemExit("bench.py: groth16.VerifyProof rejected a device's proof (or accepted it for another device's public input)")
     spread = ("%d GPUs" % N) if visible >= N else ("%d LOGICAL devices on %d visible GPU(s): NOT a multi-GPU measurement" % (N, visible))
     out = base_line(args, n, N, n * N * args.steps / elapsed, elapsed, rep_elapsed,
                     "groth16_prove_2^%d_constraints_per_gpu" % args.log2n,
@@ -1071,7 +1110,8 @@ def main_one_process(args):
     tm = capi.device_timing(0)
     out["config"]["window_bits"] = tm["window_bits"]
     out["roofline"], out["roofline_valu"] = accumulate_roofline(tm)
-    out["proof_verified"] = "groth16.VerifyProof accepted each device's last proof for its own public input and rejected it for another's (%d/%d devices)" % (N, N)
+    if args.full:
+        out["proof_verified"] = "groth16.VerifyProof accepted each device's last proof for its own public input and rejected it for another's (%d/%d devices)" % (N, N)
     out["launch"] = "one process, no launcher (WORLD_SIZE unset)"
     out["config"]["key_replicas"] = replica_note
     out["devices"] = device_report(devs)
@@ -1080,19 +1120,20 @@ def main_one_process(args):
     for d in range(1, N):
         for h in (ws[d], pxs[d], pks[d].handle):
             h.free()
-    # The communicator is created only now: the weak-scaling workload above needs none (independent proofs, no collective), and with the
-    # line already parked in the guard a first ncclCommInitAll that never returns costs the strong section, not the measurement.
-    comm_err = None
-    guard.arm(args.strong_budget_s, "gs_comm_init_local (ncclCommInitAll)")
-    try:
-        capi.comm_init_local()           # one RCCL rank per distinct physical device; the records of the sharded workloads travel through it
-    except Exception as e:              # noqa: BLE001 -- the sharded workloads fall back to host memory
-        comm_err = str(e)[:300]
-    guard.disarm()
-    if not args.no_strong:
-        out["strong"] = strong_one_process(args, N, inst, r_, s_, guard)
-    out["rccl"] = rccl_report("local: ncclCommInitAll over the distinct physical devices of this process (gs_comm_init_local)", comm_err)
-    guard.disarm()
+    if args.full:
+        # The communicator is created only now: the weak-scaling workload above needs none (independent proofs, no collective), and with the
+        # line already parked in the guard a first ncclCommInitAll that never returns costs the strong section, not the measurement.
+        comm_err = None
+        guard.arm(args.strong_budget_s, "gs_comm_init_local (ncclCommInitAll)")
+        try:
+            capi.comm_init_local()           # one RCCL rank per distinct physical device; the records of the sharded workloads travel through it
+        except Exception as e:              # noqa: BLE001 -- the sharded workloads fall back to host memory
+            comm_err = str(e)[:300]
+        guard.disarm()
+        if not args.no_strong:
+            out["strong"] = strong_one_process(args, N, inst, r_, s_, guard)
+        out["rccl"] = rccl_report("local: ncclCommInitAll over the distinct physical devices of this process (gs_comm_init_local)", comm_err)
+        guard.disarm()
     import ctypes
     ctypes.CDLL(None).fflush(None)
     print(json.dumps(out), flush=True)
@@ -1103,7 +1144,8 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--settle-ms", type=float, default=400.0, help="untimed steps before the W warm-up steps until this many ms have passed (0 = none)")
-    ap.add_argument("--reps", type=int, default=5, help="repetitions of the timed K steps; the median repetition is reported")
+    ap.add_argument("--reps", type=int, default=None, help="repetitions of the timed K steps; the median repetition is reported "
+                                                            "(default: 1, or 5 with --full)")
     ap.add_argument("--log2n", type=int, default=20)
     ap.add_argument("--workload", default="prove", choices=["prove", "prove_from_r1cs", "prove_witness", "prove_sharded", "prove_pinocchio", "msm_g1", "msm_sharded"],
                     help="prove: one independent proof per GPU (weak scaling, the default the driver runs); prove_sharded: ONE proof "
@@ -1140,13 +1182,21 @@ def main():
     ap.add_argument("--no-strong", action="store_true", help="N > 1: skip the strong-scaling figures (`strong`) of the line")
     ap.add_argument("--strong-budget-s", type=int, default=240, help="N > 1: a strong-scaling section that runs longer than this is abandoned "
                                                                       "and the line is printed without it")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: proof checks, the extra single-GPU measurements (other routes, the cold path, "
+                         "MSM figures, live PMC traffic), CPU baselines, the reference's wasm prover, strong scaling for N > 1, 5 repetitions")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (field elements as eight "
+                         "32-bit limbs in float64, least significant first)")
     args = ap.parse_args()
+    if args.reps is None:
+        args.reps = 5 if args.full else 1
 
     if args.gpus > 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1:
         if args.multi == "ranks":
             cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus), "--master-addr", "127.0.0.1",
                    "--master-port", str(29500 + os.getpid() % 400), os.path.abspath(__file__)] + sys.argv[1:]
-            os.execv(sys.executable, cmd)
+            raise SystemExit(subprocess.call(cmd))       # the same command line under the launcher, in a child process
         if args.workload == "prove" and not args.logical_shards:
             return main_one_process(args)
         raise SystemExit("bench.py --gpus %d --workload %s needs a launcher (python -m torch.distributed.run --nproc-per-node %d bench.py ...) or --multi ranks; "
@@ -1321,10 +1371,12 @@ def main():
             return pipelined(lambda: groth16.prove_begin(pk, w_dev, px_dev, r_, s_), groth16.prove_end, count, args.pipeline, on_done)
         if witness_pipe:
             return pipelined(lambda: groth16.prove_witness_begin(pk, dev_r1cs, w_dev, r_, s_), groth16.prove_end, count, args.pipeline, on_done)
+        last = None
         for _ in range(count):
-            step()
+            last = step()
             if on_done:
                 on_done()
+        return last
 
     # Untimed settling before the W warm-up steps: the first few hundred milliseconds after the (host-side) instance generation run
     # 5-15 % slow (clocks ramp from idle, first-touch of the workspaces); the timed region below is still exactly K steps.
@@ -1345,11 +1397,11 @@ def main():
         for k in tm_keys:
             tm_acc[k] += tm[k]
         window_bits[0] = tm["window_bits"]
-    rep_elapsed = []
+    rep_elapsed, last = [], None
     for _ in range(max(1, args.reps)):
         barrier()
         t0 = time.perf_counter()
-        run_steps(args.steps, None if logical else book)
+        last = run_steps(args.steps, None if logical else book)
         barrier()
         elapsed = time.perf_counter() - t0
         if world > 1:
@@ -1359,6 +1411,8 @@ def main():
         rep_elapsed.append(elapsed)
     elapsed = statistics.median(rep_elapsed)
     total_steps = args.steps * len(rep_elapsed)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
     # what the library holds in the state the timed steps ran in (VERDICT r5 weak #8a: round 5 took this snapshot at the very end, after the
     # cold-path extras had dropped the window tables, so the line said table_bytes 0 under policy `always`)
     memory_timed = None
@@ -1371,7 +1425,7 @@ def main():
         pass
 
     proof_verified = None
-    if args.workload == "prove" and not logical and args.instance in ("setup", "realistic", "gates") and not args.no_check:
+    if args.full and args.workload == "prove" and not logical and args.instance in ("setup", "realistic", "gates") and not args.no_check:
         # Product verifier (groth16.VerifyProof -> gs_groth16_verify, host side), outside the timed region, on EVERY rank:
         # the proof of this rank's instance against the vk its device setup produced, for the right public input and a wrong one.
         p_last = step()
@@ -1383,7 +1437,7 @@ def main():
         if not good:
             raise SystemExit("bench.py: groth16.VerifyProof rejected the proof of the benchmarked instance (or accepted a wrong public input)")
         proof_verified = "groth16.VerifyProof accepted each rank's proof against its device-built vk and rejected a wrong public input (%d/%d ranks)" % (world, world)
-    if args.workload == "prove_pinocchio" and not args.no_check:
+    if args.full and args.workload == "prove_pinocchio" and not args.no_check:
         from gosnark_amd import snark as _snark
         p_last = step()
         good = _snark.VerifyProof(inst.vk, p_last, inst.public) and not _snark.VerifyProof(inst.vk, p_last, [(inst.public[0] + 1) % R])
@@ -1395,13 +1449,13 @@ def main():
             raise SystemExit("bench.py: snark.VerifyProof rejected the proof of the benchmarked instance (or accepted a wrong public input)")
         proof_verified = "snark.VerifyProof (five pairing equations) accepted each rank's proof against its device-built vk and rejected a wrong public input (%d/%d ranks)" % (world, world)
     proof_check = None
-    if rank == 0 and world == 1 and args.cpu_log2n > 0 and plain_prove and args.instance in ("setup", "realistic", "gates") and not args.no_check:
+    if args.full and rank == 0 and world == 1 and args.cpu_log2n > 0 and plain_prove and args.instance in ("setup", "realistic", "gates") and not args.no_check:
         # Outside the timed region, part of the checker/baseline leg (the only place bench.py touches oracle/): the toxic
         # values of the synthetic setup are known, so the proof the benchmarked instance must produce is known in closed form.
         proof_check = checker_leg_proof(step(), inst, r_, s_)
 
     extras = {}
-    if rank == 0 and world == 1 and plain_prove and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and plain_prove and not args.no_extras:
         # --- every figure below is measured OUTSIDE the timed region and reported beside `value`, never as `value` -----------
         # one blocking call per proof (gs_groth16_prove_resident): the latency of a lone proof
         extras["blocking_ms_per_proof"], extras["blocking_ms_reps"] = time_calls_median(step, 6)
@@ -1538,7 +1592,8 @@ def main():
             if tm_acc["plan_digits"]:
                 out["plan_per_step"] = {"digits": tm_acc["plan_digits"] / total_steps, "bucket_additions": tm_acc["plan_entries"] / total_steps,
                                         "zero_digit_share": 1.0 - tm_acc["plan_entries"] / tm_acc["plan_digits"], "heavy_buckets": tm_acc["heavy_buckets"] / total_steps}
-            live, why = (live_pmc_traffic(args) if (world == 1 and plain_prove and not args.no_extras) else (None, "only the default single-GPU run measures it"))
+            live, why = (live_pmc_traffic(args) if (args.full and world == 1 and plain_prove and not args.no_extras) else
+                         (None, "only the single-GPU run with --full measures it"))
             if live:
                 # raw counters: the guide's x2 correction of FETCH_SIZE is calibrated for wide coalesced streams; this kernel's reads are 64-byte
                 # gathers, so the raw sum is `traffic` and the x2-corrected read side is given as the upper bound
@@ -1597,7 +1652,7 @@ def main():
             out["proof_verified"] = proof_verified
         if proof_check:
             out["proof_check"] = proof_check
-        if world == 1 and args.cpu_log2n > 0 and not logical:
+        if args.full and world == 1 and args.cpu_log2n > 0 and not logical:
             out["cpu_baseline"] = cpu_baseline(args.cpu_log2n, seed + 1000)
             out["cpu_baseline_all_cores"] = cpu_baseline_all_cores(args.cpu_log2n + 3, seed + 2000)
             # the container may grant fewer CPUs than os.cpu_count() reports: state what the threads actually bought
@@ -1607,7 +1662,7 @@ def main():
                 out["cpu_baseline"]["note"] = "baseline is the Groth16 prove sample; 1 constraint ~ 4 G1 + 1 G2 terms"
             if plain_prove and not args.no_extras:
                 out["cpu_baseline_reference_wasm"] = cpu_baseline_reference_wasm()
-    if world > 1 and plain_prove and args.instance == "setup" and not args.no_strong:
+    if args.full and world > 1 and plain_prove and args.instance == "setup" and not args.no_strong:
         guard.line = out if rank == 0 else None
         torch_rccl = None
         if not share:       # torch's own RCCL group, exercised once: a sum of ones over the ranks (after the line is parked: a hang costs this probe only)

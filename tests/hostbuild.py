@@ -14,7 +14,7 @@ def build(name, opt="-O2"):
     if os.environ.get("GS_HOST_SANITIZE"):      # dev switch: the same drivers under UBSan + ASan (host code only), built aside
         exe += "_san"
         if not os.path.exists(exe) or os.path.getmtime(exe) < os.path.getmtime(src):
-            subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-Wno-option-ignored", "-fsanitize=undefined,address",
+            subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-Wno-option-ignored", "-fsanitize=undefined,address", "-fno-gpu-sanitize",
                                    "-fno-sanitize-recover=undefined", src, "-o", exe])
         return exe
     deps = [src] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]

@@ -46,7 +46,7 @@ print('   n_gpus', d['n_gpus'], '| weak %.4g %s' % (d['value'], d['unit']), '| s
 assert d['n_gpus']==$N and all(need) and 'devices' in d and 'rccl' in d
 " || { echo "   FAILED (line incomplete):"; echo "$out" | tail -5; fail=1; }
 }
-plain "plain form, one process over $N devices: weak + strong + rccl in ONE line" --steps 3 --warmup 1 --reps 1 --log2n 16
+plain "plain form, one process over $N devices: weak + strong + rccl in ONE line" --full --steps 3 --warmup 1 --reps 1 --log2n 16
 step "driver command line, $N ranks sharing GPU 0 (gloo): weak scaling, independent proofs" 1 --steps 3 --warmup 1 --reps 1 --log2n 16 --cpu-log2n 0 --no-extras
 step "same, ONE proof sharded over the $N ranks (host gather): strong scaling" 1 --workload prove_sharded --steps 3 --warmup 1 --reps 1 --log2n 16 --cpu-log2n 0
 echo "== rank-mode entry points at world size 1 (RCCL communicator, gather, scatter)"
