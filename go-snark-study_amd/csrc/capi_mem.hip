@@ -22,38 +22,28 @@ void for_each_table(Object* o, F f) {
       if (b->table) f(*static_cast<BaseTable*>(b->table.get()));
       break;
     }
-    case Kind::GrothPk: {
-      auto* k = static_cast<GrothPkObj*>(o);
-      for (BaseTable* t : {&k->t_at, &k->t_bacgamma1, &k->t_bacdelta, &k->t_ptd, &k->t_bacgamma2, &k->t_ptd_eval}) f(*t);
+    default:
+      if (ProverKey* k = as_prover_key(o)) k->for_each_array([&](KeyArray& a, size_t, bool) { f(a.table); });
       break;
-    }
-    case Kind::PinocchioPk: {
-      auto* k = static_cast<PinocchioPkObj*>(o);
-      for (BaseTable* t : {&k->t_a, &k->t_ap, &k->t_bp, &k->t_c, &k->t_cp, &k->t_kp, &k->t_g1t, &k->t_b2, &k->t_g1t_eval}) f(*t);
-      break;
-    }
-    default: break;
   }
 }
 
 uint64_t object_bytes(Object* o) {
+  if (ProverKey* k = as_prover_key(o)) {
+    uint64_t t = divisor_bytes(k->z);
+    k->for_each_array([&](KeyArray& a, size_t, bool) { t += a.pts.bytes; });
+    return t;
+  }
   switch (o->kind) {
     case Kind::G1Bases: case Kind::G2Bases: return static_cast<Bases*>(o)->buf.bytes;
     case Kind::Scalars: return static_cast<Scalars*>(o)->buf.bytes;
-    case Kind::GrothPk: {
-      auto* k = static_cast<GrothPkObj*>(o);
-      return k->at.bytes + k->bacgamma1.bytes + k->bacdelta.bytes + k->ptd.bytes + k->bacgamma2.bytes + k->ptd_eval.bytes + divisor_bytes(k->z);
-    }
-    case Kind::PinocchioPk: {
-      auto* k = static_cast<PinocchioPkObj*>(o);
-      return k->a.bytes + k->ap.bytes + k->bp.bytes + k->c.bytes + k->cp.bytes + k->kp.bytes + k->g1t.bytes + k->b2.bytes + k->g1t_eval.bytes + divisor_bytes(k->z);
-    }
     case Kind::R1cs: {
       auto* r = static_cast<R1csObj*>(o);
       uint64_t t = r->w_mont.bytes + r->vals.bytes + r->coef.bytes + r->prod.bytes;
       for (int i = 0; i < 3; ++i) t += r->rowptr[i].bytes + r->col[i].bytes + r->val[i].bytes;
       return t;
     }
+    default: break;
   }
   return 0;
 }
@@ -182,25 +172,16 @@ int gs_build_tables(gs_handle h, int route) {
         build(*static_cast<BaseTable*>(b->table.get()), b->buf, b->n, o->kind == Kind::G2Bases);
         return GS_OK;
       }
-      case Kind::GrothPk: {
-        auto* k = static_cast<GrothPkObj*>(o);
+      default: {
+        ProverKey* k = as_prover_key(o);
+        if (!k) return fail(GS_ERR_ARG, "gs_build_tables: the handle has no base arrays");
         for_each_table(o, [&](BaseTable& t) { t.last_use = c.call_clock; });      // none of them is this call's eviction victim
-        build(k->t_at, k->at, k->n_w, false); build(k->t_bacgamma1, k->bacgamma1, k->n_w, false); build(k->t_bacdelta, k->bacdelta, k->n_w, false);
-        build(k->t_bacgamma2, k->bacgamma2, k->n_w, true);
-        if (route != 2) build(k->t_ptd, k->ptd, k->n_h, false);
-        if (route != 1 && k->n_e) build(k->t_ptd_eval, k->ptd_eval, k->n_e, false);
+        for (int i = 0; i < k->n_g1w; ++i) build(k->g1w[i].table, k->g1w[i].pts, k->n_w, false);
+        build(k->g2w.table, k->g2w.pts, k->n_w, true);
+        if (route != 2) build(k->h.table, k->h.pts, k->n_h, false);
+        if (route != 1 && k->n_e) build(k->h_eval.table, k->h_eval.pts, k->n_e, false);
         return GS_OK;
       }
-      case Kind::PinocchioPk: {
-        auto* k = static_cast<PinocchioPkObj*>(o);
-        for_each_table(o, [&](BaseTable& t) { t.last_use = c.call_clock; });
-        build(k->t_a, k->a, k->n_w, false); build(k->t_ap, k->ap, k->n_w, false); build(k->t_bp, k->bp, k->n_w, false); build(k->t_c, k->c, k->n_w, false);
-        build(k->t_cp, k->cp, k->n_w, false); build(k->t_kp, k->kp, k->n_w, false); build(k->t_b2, k->b2, k->n_w, true);
-        if (route != 2) build(k->t_g1t, k->g1t, k->n_h, false);
-        if (route != 1 && k->n_e) build(k->t_g1t_eval, k->g1t_eval, k->n_e, false);
-        return GS_OK;
-      }
-      default: return fail(GS_ERR_ARG, "gs_build_tables: the handle has no base arrays");
     }
   }, true, false, h);
 }

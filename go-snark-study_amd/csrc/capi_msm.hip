@@ -177,9 +177,8 @@ int msm_begin(Ctx& c, Kind kind, gs_handle hb, size_t off, gs_handle hs, size_t 
 
 int msm_end(Ctx& c, uint64_t ticket, uint64_t* out_affine, int* is_inf) {
   if (!out_affine || !is_inf) return fail(GS_ERR_ARG, "null output");
-  int parity = -1;
-  for (int p = 0; p < Ctx::kMaxInFlight; ++p) if (c.inflight[p] && c.inflight[p]->ticket == ticket) parity = p;
-  if (parity < 0) return fail(GS_ERR_ARG, "gs_msm_end: unknown ticket %llu", (unsigned long long)ticket);
+  const int parity = find_ticket(c, "gs_msm_end", ticket);
+  if (parity < 0) return GS_ERR_ARG;
   MsmInFlight* st = dynamic_cast<MsmInFlight*>(c.inflight[parity].get());
   if (!st) return fail(GS_ERR_ARG, "gs_msm_end: ticket %llu belongs to a proof (use gs_groth16_prove_end)", (unsigned long long)ticket);
   std::shared_ptr<InFlightBase> base = std::move(c.inflight[parity]);
@@ -403,7 +402,7 @@ int gs_len(gs_handle h, size_t* out) {
     switch (it->second->kind) {
       case Kind::G1Bases: case Kind::G2Bases: *out = static_cast<Bases*>(it->second.get())->n; return GS_OK;
       case Kind::Scalars: *out = static_cast<Scalars*>(it->second.get())->n; return GS_OK;
-      case Kind::GrothPk: *out = static_cast<GrothPkObj*>(it->second.get())->n_w; return GS_OK;       // entries of At held (a slice holds fewer than NVars)
+      case Kind::GrothPk: *out = static_cast<ProverKey*>(it->second.get())->n_w; return GS_OK;       // entries of At held (a slice holds fewer than NVars)
       default: return fail(GS_ERR_ARG, "gs_len: handle has no length");
     }
   }, true, true, h);

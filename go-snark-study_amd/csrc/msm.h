@@ -88,7 +88,7 @@ inline double build_credit(double units, size_t n) { return std::max(kBuildCredi
 bool prepare_tables(Ctx& c, const std::vector<TableRef>& group, uint32_t nterms, int* cbits, double* credit = nullptr);
 // the tables one call will use, stamped for the LRU BEFORE any of them is built: an allocation made while the first group's tables are
 // built must not evict the second group's (prepare_tables only stamped the group it was called for)
-void stamp_tables(Ctx& c, std::initializer_list<BaseTable*> tables);
+void stamp_tables(Ctx& c, const std::vector<BaseTable*>& tables);
 // wait for a pending build and install it (finishing it first if instalments are missing) or drop it (gs_release_tables, gs_build_tables)
 void table_settle(Ctx& c, BaseTable& t, bool install);
 
@@ -109,7 +109,7 @@ struct LaunchShape { int njobs; bool g2; };
 void build_plan(Ctx& c, int slot, const uint32_t* scalars_dev, uint32_t n, MsmPlan& plan, const std::vector<LaunchShape>& users, int cbits = 0,
                 bool table_free = false, const uint32_t* term_index = nullptr, uint32_t index_bias = 0);
 // true when build_plan sorts a plan of this width partition-first (>= GS_PART_MIN_R bucket ranges of 2^15, i.e. c >= 18 as shipped):
-// that sort takes no term list, so callers that would hand build_plan one (the sparse-B plans of prove.hip) must ask first
+// that sort takes no term list, so callers that would hand build_plan one (the sparse-B plan of prove.hip's proof_enqueue) must ask first
 bool plan_partitions_first(int cbits);
 // which points of one or two packed-affine arrays are finite: mask (ceil(n / 32) words, written) and their number (synchronises the stream)
 uint32_t finite_mask_dev(Ctx& c, const uint32_t* g1_pts, const uint32_t* g2_pts, uint32_t n, uint32_t* mask_dev);

@@ -374,7 +374,7 @@ static bool advance_pending(Ctx& c, BaseTable& t, double& credit) {
   return true;
 }
 
-void stamp_tables(Ctx& c, std::initializer_list<BaseTable*> tables) {
+void stamp_tables(Ctx& c, const std::vector<BaseTable*>& tables) {
   for (BaseTable* t : tables) if (t) t->last_use = c.call_clock;
 }
 

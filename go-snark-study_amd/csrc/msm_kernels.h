@@ -61,7 +61,7 @@ GS_HD int32_t next_digit(const uint32_t (&k)[8], const PlanParams& pp, int w, ui
 using digit_t = uint32_t;
 // term_index (optional): the plan covers only the listed terms -- compact term i of the plan is term term_index[i] - index_bias of the
 // scalar vector (and of the base arrays: k_scatter writes that id into the entries).  For keys with sparse B arrays (prove.h,
-// GrothPkObj::b_index): the terms whose base points are the point at infinity never enter the digit matrix.
+// ProverKey::b_index): the terms whose base points are the point at infinity never enter the digit matrix.
 __global__ void __launch_bounds__(256) k_digits(const uint32_t* __restrict__ scalars, PlanParams pp, digit_t* __restrict__ digits,
                                                  const uint32_t* __restrict__ term_index, uint32_t index_bias) {
   wave_priority<GS_PRIO_PLAN>();

@@ -51,7 +51,7 @@ void interpolate_dev(Ctx& c, const uint32_t* values_std, size_t n, size_t nvec, 
 // witness satisfies the constraints at the dz = deg Z roots of Z: node extension by one batched convolution, ONE tree
 // interpolation, one Taylor shift.  false (nothing written) when a constraint is violated -- take the px route then.
 bool hx_direct_dev(Ctx& c, const uint32_t* vals_std, size_t n, size_t dz, uint32_t* hx_out_std);
-// The two halves of the above, for keys that carry an evaluation-basis copy of PowersTauDelta / G1T (prove.h): the prover then
+// The two halves of the above, for keys that carry an evaluation-basis copy of PowersTauDelta / G1T (prove.h, ProverKey::h_eval): the prover then
 // needs only H's VALUES at the nodes n+1..2n.  hx_values_dev: hv[k-1] = H(n+k), k = 1..n, canonical standard form (false: shape
 // not served); r1cs_check_dev: *bad_dev = number of roots of Z at which a b != c (enqueue only -- the caller reads the word when
 // it collects the proof, and takes the exact route if it is not zero); hx_from_values_dev: values -> coefficients.

@@ -1,5 +1,7 @@
-// Internal: device-resident proving keys and the prover drivers (implemented in prove.hip).
+// Internal: device-resident proving keys (described as data the prover engine in prove.hip reads) and what the other
+// translation units need of the prover's staging and of the R1CS routines (capi_poly.hip, capi_r1cs.hip).
 #pragma once
+#include <functional>
 #include <vector>
 #include <mutex>
 #include "msm.h"
@@ -8,62 +10,114 @@
 
 namespace gs {
 
-struct GrothPkObj : Object {      // groth16.Pk (groth16/groth16.go:15-32), resident
-  size_t nvars = 0, npublic = 0, nz = 0, nptd = 0;   // global counts (nptd = len(PowersTauDelta))
+struct KeyArray {                 // one base array of a key: packed affine points (an owned copy) and their window table (built on the
+  DevBuf pts;                     // first proofs, msm.h)
+  BaseTable table;
+};
+
+// What a Groth16 and a Pinocchio proving key have in common -- which is everything the prover engine needs: a proof of either
+// scheme is some G1 sums and one G2 sum over w sharing a plan, H(x) = px / Z, and one G1 sum over h.  The engine (prove.hip),
+// the memory accounting (capi_mem.hip) and the evaluation-basis entry points (setup.hip) walk this description; none of them asks
+// which scheme a key belongs to.
+struct ProverKey : Object {
+  const char* const scheme;       // "groth16" / "pinocchio": names the entry points in error messages (gs_<scheme>_prove_partials ...)
+  const char* const hx_too_long;  // wording of "len(hx) exceeds the h array" (two %zu: len(hx), len_h)
+  size_t nvars = 0, npublic = 0, nz = 0, len_h = 0;   // global counts (len_h = len(PowersTauDelta) / len(G1T))
   // Key slices (multi-GPU, SURVEY 8e "each GPU holds 1/8 of every pk array"): a key created by gs_groth16_pk_create_shard /
-  // gs_groth16_pk_shard holds only the term ranges of shard `shard_index` of `shard_count`: At / BACGamma / BACDelta entries
-  // [w_lo, w_lo + n_w) and PowersTauDelta entries [h_lo, h_lo + n_h).  A full key has shard_count = 1, n_w = nvars, n_h = nptd.
+  // gs_*_pk_shard holds only the term ranges of shard `shard_index` of `shard_count`: entries [w_lo, w_lo + n_w) of the arrays over w
+  // and entries [h_lo, h_lo + n_h) of the h array.  A full key has shard_count = 1, n_w = nvars, n_h = len_h.
   size_t shard_index = 0, shard_count = 1, w_lo = 0, n_w = 0, h_lo = 0, n_h = 0;
-  DevBuf at, bacgamma1, bacdelta, ptd;     // packed affine G1 (owned copies)
-  DevBuf bacgamma2;                        // packed affine G2
-  BaseTable t_at, t_bacgamma1, t_bacdelta, t_ptd, t_bacgamma2;   // their window tables (built on the first prove)
+  // The arrays.  g1w[0 .. n_g1w): the G1 arrays summed over w, in the order of the sums (one launch over one plan of w); g1w[b_g1]
+  // is the one that shares B's sparsity with the G2 array g2w; h is summed over hx = px / Z.
+  static constexpr int kMaxG1w = 6;
+  const int n_g1w, b_g1;
+  KeyArray g1w[kMaxG1w], g2w, h;
+  // Evaluation-basis twin of h (optional; the setups build it, gs_*_pk_set_eval attaches one): h_eval[j-1] = l_j(tau) * (what h[i]
+  // multiplies tau^i with) * G,  l_j = Lagrange basis over the nodes n+1 .. 2n  (j = 1..n_eval = #constraints), so that
+  //   sum_j H(n+j) h_eval[j-1] = sum_i h_i h[i]      (groth16.go:139-149, 269-271; snark.go:239-247, 284-286):
+  // the witness route runs the h-MSM over H's VALUES and never interpolates H.  A slice holds entries [e_lo, e_lo + n_e).
+  size_t n_eval = 0, e_lo = 0, n_e = 0;
+  KeyArray h_eval;
+  // The workspace sets (of the eight a ticket slot owns; the G1 group over w takes set 0) of the G2 group, of the B' group of a
+  // proof with split B, and of the h group.  They decide which grow-only buffers a proof touches, hence gs_memory.
+  const int ws_g2, ws_b, ws_h;
+  Divisor z;                      // pk.Z with cached 1/rev(Z) series + spectrum
+  // Which of the held variables appear in B at all (round 5).  The reference's circuit compiler puts a variable into B only as the
+  // second operand of a multiplication or a divisor (circuitcompiler/circuit.go:110-128: `+` / `-` / `in` rows have B = [one]), so for
+  // its circuits most points of g1w[b_g1] / g2w are the point at infinity.  b_index lists the held variables of which either
+  // point is finite (ascending, relative to the first held variable; on the device and on the host, where a call cuts its term range out
+  // of it), b_finite is their number: when enough are missing the prover sums the two B arrays -- 3.8 of a Groth16 proof's 6.8
+  // job-units -- over a SECOND plan of w that holds the listed terms only (prove.hip, proof_enqueue).  Scanned once, when the key is
+  // created; keys without a missing point keep no list.
+  DevBuf b_index;
+  std::vector<uint32_t> b_index_host;
+  size_t b_finite = 0;
+
+  // every array with its held length, in the fixed order  g1w .. | h | g2w | h_eval  (f(KeyArray&, size_t n, bool g2))
+  template <class F> void for_each_array(F f) {
+    for (int i = 0; i < n_g1w; ++i) f(g1w[i], n_w, false);
+    f(h, n_h, false); f(g2w, n_w, true); f(h_eval, n_e, false);
+  }
+ protected:
+  ProverKey(Kind k, const char* scheme_, const char* hx_too_long_, int n_g1w_, int b_g1_, int ws_g2_, int ws_b_, int ws_h_)
+      : Object(k), scheme(scheme_), hx_too_long(hx_too_long_), n_g1w(n_g1w_), b_g1(b_g1_), ws_g2(ws_g2_), ws_b(ws_b_), ws_h(ws_h_) {}
+};
+inline ProverKey* as_prover_key(Object* o) {
+  return o && (o->kind == Kind::GrothPk || o->kind == Kind::PinocchioPk) ? static_cast<ProverKey*>(o) : nullptr;
+}
+void pk_scan_sparsity(Ctx& c, ProverKey& pk);      // fills b_index / b_finite (synchronises the stream)
+
+struct GrothPkObj : ProverKey {   // groth16.Pk (groth16/groth16.go:15-32), resident
+  static constexpr Kind kKind = Kind::GrothPk;
+  enum { kAt = 0, kBacGamma1 = 1, kBacDelta = 2 };      // g1w: the sums over w in the order of gs_groth16_prove_partials
+  DevBuf& at() { return g1w[kAt].pts; }
+  DevBuf& bacgamma1() { return g1w[kBacGamma1].pts; }
+  DevBuf& bacdelta() { return g1w[kBacDelta].pts; }
+  DevBuf& bacgamma2() { return g2w.pts; }
+  DevBuf& ptd() { return h.pts; }                       // PowersTauDelta
+  DevBuf& ptd_eval() { return h_eval.pts; }             // l_j(tau) * Z(tau) / delta * G
   G1Affine alpha, beta, delta;             // host, Montgomery
   G2Affine beta2, delta2;
   // host-side window tables of delta / delta2 for the tail's result-independent products (built on the first proof of the key)
   std::once_flag fixed_once;
   HostFixedBase<FqTag> delta_fixed;
   HostFixedBase<Fq2Tag> delta2_fixed;
-  Divisor z;                               // pk.Z with cached 1/rev(Z) series + spectrum
-  // Evaluation-basis copy of PowersTauDelta (optional; gs_groth16_setup builds it, gs_groth16_pk_set_eval attaches one):
-  //   ptd_eval[j-1] = l_j(tau) * Z(tau) / delta * G,  l_j = Lagrange basis over the nodes n+1 .. 2n  (j = 1..n_eval = #constraints)
-  // so that  sum_j H(n+j) ptd_eval[j-1] = H(tau) Z(tau) / delta * G = sum_i h_i PowersTauDelta[i]  (groth16.go:139-149, 269-271):
-  // the witness route runs the h-MSM over H's VALUES and never interpolates H.  A slice holds entries [e_lo, e_lo + n_e).
-  size_t n_eval = 0, e_lo = 0, n_e = 0;
-  DevBuf ptd_eval;
-  BaseTable t_ptd_eval;
-  // Which of the held variables appear in B at all (round 5).  The reference's circuit compiler puts a variable into B only as the
-  // second operand of a multiplication or a divisor (circuitcompiler/circuit.go:110-128: `+` / `-` / `in` rows have B = [one]), so for
-  // its circuits most G1.BACGamma / G2.BACGamma points are the point at infinity.  b_index lists the held variables of which either
-  // point is finite (ascending, relative to the first held variable; on the device and on the host, where a call cuts its term range out
-  // of it), b_finite is their number: when enough are missing the prover sums B1 and B2 -- 3.8 of a proof's 6.8 job-units -- over a
-  // SECOND plan of w that holds the listed terms only (prove.hip, groth16_enqueue).  Scanned once, when the key is created; keys
-  // without a missing point keep no list.
-  DevBuf b_index;
-  std::vector<uint32_t> b_index_host;
-  size_t b_finite = 0;
-  GrothPkObj() : Object(Kind::GrothPk) {}
+  GrothPkObj()
+      : ProverKey(kKind, "groth16", "len(hx) = len(px) - len(Z) + 1 = %zu exceeds len(PowersTauDelta) = %zu (groth16.go:269-271)", 3, kBacGamma1,
+                  4, 2, 3) {}
 };
-void groth_pk_scan_sparsity(Ctx& c, GrothPkObj& pk);      // fills b_index / b_finite (synchronises the stream)
 
-struct PinocchioPkObj : Object {  // snark.Pk (snark.go:16-26), resident
-  size_t nvars = 0, npublic = 0, nz = 0, ng1t = 0;      // global counts (ng1t = len(G1T))
-  // key slices as GrothPkObj's: the seven per-variable arrays hold entries [w_lo, w_lo + n_w), G1T entries [h_lo, h_lo + n_h)
-  size_t shard_index = 0, shard_count = 1, w_lo = 0, n_w = 0, h_lo = 0, n_h = 0;
-  DevBuf a, ap, bp, c, cp, kp, g1t;        // packed affine G1
-  DevBuf b2;                               // packed affine G2
-  BaseTable t_a, t_ap, t_bp, t_c, t_cp, t_kp, t_g1t, t_b2;
-  Divisor z;
-  // evaluation-basis copy of G1T (optional, as GrothPkObj::ptd_eval): g1t_eval[j-1] = l_j(tau) * G over the nodes n+1 .. 2n, so that
-  // sum_j H(n+j) g1t_eval[j-1] = H(tau) G = sum_i h_i G1T[i]  (snark.go:239-247, 284-286)
-  size_t n_eval = 0, e_lo = 0, n_e = 0;     // a slice holds entries [e_lo, e_lo + n_e)
-  DevBuf g1t_eval;
-  BaseTable t_g1t_eval;
-  // which held variables appear in B (as GrothPkObj::b_index): B (G2) and B' (G1) of a reference-style circuit are mostly infinity
-  DevBuf b_index;
-  std::vector<uint32_t> b_index_host;
-  size_t b_finite = 0;
-  PinocchioPkObj() : Object(Kind::PinocchioPk) {}
+struct PinocchioPkObj : ProverKey {  // snark.Pk (snark.go:16-26), resident
+  static constexpr Kind kKind = Kind::PinocchioPk;
+  enum { kA = 0, kAp, kBp, kC, kCp, kKp };              // g1w: A, A', B', C, C', K' (snark.go:265-278)
+  DevBuf& a() { return g1w[kA].pts; }
+  DevBuf& ap() { return g1w[kAp].pts; }
+  DevBuf& bp() { return g1w[kBp].pts; }
+  DevBuf& c() { return g1w[kC].pts; }
+  DevBuf& cp() { return g1w[kCp].pts; }
+  DevBuf& kp() { return g1w[kKp].pts; }
+  DevBuf& b2() { return g2w.pts; }
+  DevBuf& g1t() { return h.pts; }
+  DevBuf& g1t_eval() { return h_eval.pts; }             // l_j(tau) * G
+  PinocchioPkObj() : ProverKey(kKind, "pinocchio", "len(hx) = %zu exceeds len(G1T) = %zu (snark.go:284-286)", 6, kBp, 6, 5, 7) {}
 };
-void pinocchio_pk_scan_sparsity(Ctx& c, PinocchioPkObj& pk);
+
+// ---- shared with capi_poly.hip / capi_r1cs.hip ----------------------------------------------------------------------------------
+// Per-context staging of the prover and polynomial entry points (device memory belongs to one device).
+struct ProveState {
+  DevBuf hx[Ctx::kSlots];                       // hx = floor(px / Z) -- or H's values on the evaluation-basis route --, one per slot (standard form)
+  DevBuf up_w, up_px, up_a, up_b, up_o;         // uploads of host operands / results (blocking entry points only)
+  DevBuf exact_px[Ctx::kSlots];                 // px of the exact witness route, one per slot (allocated only if that route is ever taken)
+  // Host-buffer tickets (gs_*_host_begin): every in-flight slot owns the device copies of ITS w / px.  Grow-only, so a stream of
+  // proofs from host memory allocates nothing after its first lap over the slots (gs_alloc_counters); a slot is re-used only after
+  // its ticket was collected, i.e. after every device read of these buffers.
+  DevBuf slot_w[Ctx::kSlots], slot_px[Ctx::kSlots];
+};
+inline ProveState& prove_state(Ctx& c) { return c.state<ProveState>(c.prove_state); }
+const uint32_t* upload_tmp(Ctx& c, DevBuf& buf, const uint64_t* host, size_t n);   // host scalars -> a scratch buffer (books h2d_ms)
+void download(Ctx& c, uint64_t* host, const void* dev, size_t n);                  // n scalars to the host; synchronises c.stream
+// capi_r1cs.hip: w (standard form, m elements, device) -> o.vals = [A w | B w | C w], and -> o.coef = [ax | bx | cx] and px_out
+void r1cs_values_dev(Ctx& c, R1csObj& o, const uint32_t* w_dev);
+void r1cs_px_dev(Ctx& c, R1csObj& o, const uint32_t* w_dev, uint32_t* px_out);
 
 }  // namespace gs

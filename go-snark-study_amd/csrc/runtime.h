@@ -161,7 +161,7 @@ struct Scalars : Object {        // n x 8 u32 words, standard form, resident
   ~Scalars() override { if (!process_exiting()) for (auto& r : reads) (void)hipEventDestroy(r.ev); }
 };
 
-// a proof whose device work has been enqueued but not collected yet (prove.hip)
+// a proof whose device work has been enqueued but not collected yet (prove.hip: ProofInFlight; capi_msm.hip: MsmInFlight)
 struct InFlightBase {
   uint64_t ticket = 0;
   std::vector<std::shared_ptr<Object>> keep;   // the key and scalar vectors this operation reads: gs_free on them is deferred
@@ -397,6 +397,13 @@ int guarded(F&& f, bool need_init = true, bool allow_inflight = false, gs_handle
   }
 }
 inline void reset_timing(Ctx& c) { c.timing = gs_timing{}; }
+
+// the slot that holds an outstanding ticket; -1 with the error set ("<fn>: unknown ticket") when there is none
+inline int find_ticket(Ctx& c, const char* fn, uint64_t ticket) {
+  for (int p = 0; p < Ctx::kMaxInFlight; ++p) if (c.inflight[p] && c.inflight[p]->ticket == ticket) return p;
+  fail(GS_ERR_ARG, "%s: unknown ticket %llu", fn, (unsigned long long)ticket);
+  return -1;
+}
 
 // First phase of every gs_*_end: wait for the ticket's device work WITHOUT holding the context's lock (the second phase, under the
 // lock as before, then finds every event complete and only folds the downloaded partial sums).  Round 5's _end waited for the device

@@ -146,20 +146,20 @@ int gs_groth16_setup(size_t n, size_t m, size_t npublic,
     scaled_powers_dev(c, T, zt_inv_delta, m - 1, pw.as<uint32_t>());            // tau^i Z(tau) / delta    :139-149
     // --- encryption: k * G batches --------------------------------------------------------------------------
     auto pk = std::make_unique<GrothPkObj>();
-    pk->nvars = m; pk->npublic = npublic; pk->nz = m - 1; pk->nptd = m - 1; pk->n_w = m; pk->n_h = m - 1;
-    pk->at.alloc(m * 64); pk->bacgamma1.alloc(m * 64); pk->bacdelta.alloc(m * 64); pk->ptd.alloc(std::max<size_t>(m - 1, 1) * 64);
-    pk->bacgamma2.alloc(m * 128);
-    fixed_base_g1(c, at.as<uint32_t>(), (uint32_t)m, pk->at.as<uint32_t>());                    // Pk.G1.At        :164-165
-    fixed_base_g1(c, bt.as<uint32_t>(), (uint32_t)m, pk->bacgamma1.as<uint32_t>());             // Pk.G1.BACGamma  :168,171
-    fixed_base_g2(c, bt.as<uint32_t>(), (uint32_t)m, pk->bacgamma2.as<uint32_t>());             // Pk.G2.BACGamma  :169,173
-    fixed_base_g1(c, cd.as<uint32_t>(), (uint32_t)m, pk->bacdelta.as<uint32_t>());              // Pk.BACDelta     :177-200 (i <= NPublic: infinity)
-    fixed_base_g1(c, pw.as<uint32_t>(), (uint32_t)(m - 1), pk->ptd.as<uint32_t>());             // PowersTauDelta  :139-149
+    pk->nvars = m; pk->npublic = npublic; pk->nz = m - 1; pk->len_h = m - 1; pk->n_w = m; pk->n_h = m - 1;
+    pk->at().alloc(m * 64); pk->bacgamma1().alloc(m * 64); pk->bacdelta().alloc(m * 64); pk->ptd().alloc(std::max<size_t>(m - 1, 1) * 64);
+    pk->bacgamma2().alloc(m * 128);
+    fixed_base_g1(c, at.as<uint32_t>(), (uint32_t)m, pk->at().as<uint32_t>());                    // Pk.G1.At        :164-165
+    fixed_base_g1(c, bt.as<uint32_t>(), (uint32_t)m, pk->bacgamma1().as<uint32_t>());             // Pk.G1.BACGamma  :168,171
+    fixed_base_g2(c, bt.as<uint32_t>(), (uint32_t)m, pk->bacgamma2().as<uint32_t>());             // Pk.G2.BACGamma  :169,173
+    fixed_base_g1(c, cd.as<uint32_t>(), (uint32_t)m, pk->bacdelta().as<uint32_t>());              // Pk.BACDelta     :177-200 (i <= NPublic: infinity)
+    fixed_base_g1(c, pw.as<uint32_t>(), (uint32_t)(m - 1), pk->ptd().as<uint32_t>());             // PowersTauDelta  :139-149
     // The same group element through H's VALUES (prove.h): ptd_eval[j-1] = l_j(tau) Z(tau) / delta * G with l_j the Lagrange basis
     // over the nodes n+1 .. 2n, i.e. L_j(tau - n) over 1 .. n -- one more fixed-base batch while tau is still known.
     DevBuf lag2(n * 32), qe(n * 32);
     if (eval_basis_scalars(c, n, T, zt_inv_delta, lag2, qe)) {
-      pk->ptd_eval.alloc(n * 64);
-      fixed_base_g1(c, qe.as<uint32_t>(), (uint32_t)n, pk->ptd_eval.as<uint32_t>());
+      pk->ptd_eval().alloc(n * 64);
+      fixed_base_g1(c, qe.as<uint32_t>(), (uint32_t)n, pk->ptd_eval().as<uint32_t>());
       pk->n_eval = n; pk->e_lo = 0; pk->n_e = n;
     }
     // single points: alpha, beta, delta in G1; beta, gamma, delta in G2                          :151-160
@@ -193,7 +193,7 @@ int gs_groth16_setup(size_t n, size_t m, size_t npublic,
       GS_HIP(hipMemcpyAsync(vk_out + 12 + 72, j1.as<uint32_t>() + 24, nic * 96, hipMemcpyDeviceToHost, c.stream));
     }
     GS_HIP(hipStreamSynchronize(c.stream));
-    groth_pk_scan_sparsity(c, *pk);
+    pk_scan_sparsity(c, *pk);
     *pk_out = c.put(std::move(pk));
     return GS_OK;
   });
@@ -235,23 +235,23 @@ int gs_pinocchio_setup(size_t n, size_t m, size_t npublic,
     const uint64_t one[4] = {1, 0, 0, 0};
     scaled_powers_dev(c, T, one, m - 1, pw.as<uint32_t>());                          // G1T_i = tau^i G1      :239-247
     auto pk = std::make_unique<PinocchioPkObj>();
-    pk->nvars = m; pk->npublic = npublic; pk->nz = m - 1; pk->ng1t = m - 1;
+    pk->nvars = m; pk->npublic = npublic; pk->nz = m - 1; pk->len_h = m - 1;
     pk->n_w = m; pk->n_h = m - 1;                                                    // a full key
-    DevBuf* g1dst[7] = {&pk->a, nullptr, &pk->c, &pk->ap, &pk->bp, &pk->cp, &pk->kp};   // sb -> B lives in G2
+    DevBuf* g1dst[7] = {&pk->a(), nullptr, &pk->c(), &pk->ap(), &pk->bp(), &pk->cp(), &pk->kp()};   // sb -> B lives in G2
     for (int i = 0; i < 7; ++i) {
       if (!g1dst[i]) continue;
       g1dst[i]->alloc(m * 64);
       fixed_base_g1(c, outs[i], (uint32_t)m, g1dst[i]->as<uint32_t>());
     }
-    pk->b2.alloc(m * 128);
-    fixed_base_g2(c, outs[1], (uint32_t)m, pk->b2.as<uint32_t>());                   // Pk.B                 :192-194
-    pk->g1t.alloc((m - 1) * 64);
-    fixed_base_g1(c, pw.as<uint32_t>(), (uint32_t)(m - 1), pk->g1t.as<uint32_t>());
+    pk->b2().alloc(m * 128);
+    fixed_base_g2(c, outs[1], (uint32_t)m, pk->b2().as<uint32_t>());                   // Pk.B                 :192-194
+    pk->g1t().alloc((m - 1) * 64);
+    fixed_base_g1(c, pw.as<uint32_t>(), (uint32_t)(m - 1), pk->g1t().as<uint32_t>());
     // evaluation-basis copy of G1T (prove.h): g1t_eval[j-1] = l_j(tau) * G over the nodes n+1 .. 2n
     DevBuf lag2(n * 32), qe(n * 32);
     if (eval_basis_scalars(c, n, T, one, lag2, qe)) {
-      pk->g1t_eval.alloc(n * 64);
-      fixed_base_g1(c, qe.as<uint32_t>(), (uint32_t)n, pk->g1t_eval.as<uint32_t>());
+      pk->g1t_eval().alloc(n * 64);
+      fixed_base_g1(c, qe.as<uint32_t>(), (uint32_t)n, pk->g1t_eval().as<uint32_t>());
       pk->n_eval = n; pk->e_lo = 0; pk->n_e = n;
     }
     DevBuf zc((m - 1) * 32);
@@ -267,7 +267,7 @@ int gs_pinocchio_setup(size_t n, size_t m, size_t npublic,
       GS_HIP(hipMemcpyAsync(s1.p, s1h, 64, hipMemcpyHostToDevice, c.stream));
       GS_HIP(hipMemcpyAsync(s2.p, s2h, 160, hipMemcpyHostToDevice, c.stream));
       fixed_base_g1(c, s1.as<uint32_t>(), 2, p1.as<uint32_t>());
-      GS_HIP(hipMemcpyAsync(p1.as<uint32_t>() + 32, pk->a.p, nic * 64, hipMemcpyDeviceToDevice, c.stream));    // IC = A[0..NPublic]
+      GS_HIP(hipMemcpyAsync(p1.as<uint32_t>() + 32, pk->a().p, nic * 64, hipMemcpyDeviceToDevice, c.stream));    // IC = A[0..NPublic]
       fixed_base_g2(c, s2.as<uint32_t>(), 5, p2.as<uint32_t>());
       affine_to_jacobian_std_g1(c, p1.as<uint32_t>(), (uint32_t)(2 + nic), j1.as<uint32_t>());
       affine_to_jacobian_std_g2(c, p2.as<uint32_t>(), 5, j2.as<uint32_t>());
@@ -285,10 +285,10 @@ int gs_pinocchio_setup(size_t n, size_t m, size_t npublic,
       cp(o + 288, J1 + 48, nic * 24);   // IC
       GS_HIP(hipStreamSynchronize(c.stream));
     }
-    force_infinity_points(c, pk->a, npublic + 1, 16);                               // the prover sums A, Ap over i > NPublic (snark.go:265)
-    force_infinity_points(c, pk->ap, npublic + 1, 16);
+    force_infinity_points(c, pk->a(), npublic + 1, 16);                               // the prover sums A, Ap over i > NPublic (snark.go:265)
+    force_infinity_points(c, pk->ap(), npublic + 1, 16);
     GS_HIP(hipStreamSynchronize(c.stream));
-    pinocchio_pk_scan_sparsity(c, *pk);
+    pk_scan_sparsity(c, *pk);
     *pk_out = c.put(std::move(pk));
     return GS_OK;
   });
@@ -317,12 +317,12 @@ int gs_groth16_pk_export(gs_handle hpk, int which, uint64_t* jacobian, size_t co
       return GS_OK;
     }
     switch (which) {
-      case 0: src = &pk->at; break;
-      case 1: src = &pk->bacgamma1; break;
-      case 2: src = &pk->bacgamma2; g2 = true; break;
-      case 3: src = &pk->bacdelta; break;
-      case 4: src = &pk->ptd; have = pk->n_h; break;
-      case 7: src = &pk->ptd_eval; have = pk->n_e; break;       // evaluation-basis copy of PowersTauDelta (0 points when the key has none)
+      case 0: src = &pk->at(); break;
+      case 1: src = &pk->bacgamma1(); break;
+      case 2: src = &pk->bacgamma2(); g2 = true; break;
+      case 3: src = &pk->bacdelta(); break;
+      case 4: src = &pk->ptd(); have = pk->n_h; break;
+      case 7: src = &pk->ptd_eval(); have = pk->n_e; break;       // evaluation-basis copy of PowersTauDelta (0 points when the key has none)
       default: return fail(GS_ERR_ARG, "gs_groth16_pk_export: which must be 0..7");
     }
     if (count != have || (count && !jacobian)) return fail(GS_ERR_ARG, "gs_groth16_pk_export: array has %zu points, asked for %zu", have, count);
@@ -342,7 +342,7 @@ int gs_pinocchio_pk_export(gs_handle hpk, int which, uint64_t* jacobian, size_t 
     PinocchioPkObj* pk = c.get<PinocchioPkObj>(hpk, Kind::PinocchioPk);
     if (!pk) return fail(GS_ERR_ARG, "gs_pinocchio_pk_export: bad proving-key handle");
     if (pk->shard_count != 1) return fail(GS_ERR_ARG, "gs_pinocchio_pk_export: the key is a slice (export the full key)");
-    const DevBuf* arr[10] = {&pk->a, &pk->ap, &pk->b2, &pk->bp, &pk->c, &pk->cp, &pk->kp, &pk->g1t, nullptr, &pk->g1t_eval};
+    const DevBuf* arr[10] = {&pk->a(), &pk->ap(), &pk->b2(), &pk->bp(), &pk->c(), &pk->cp(), &pk->kp(), &pk->g1t(), nullptr, &pk->g1t_eval()};
     if (which == 8) {           // pk.Z: nz coefficients, 4 x u64 each
       if (count != pk->nz || !jacobian) return fail(GS_ERR_ARG, "gs_pinocchio_pk_export: Z has %zu coefficients, asked for %zu", pk->nz, count);
       GS_HIP(hipMemcpyAsync(jacobian, pk->z.b_std.p, count * 32, hipMemcpyDeviceToHost, c.stream));
@@ -351,7 +351,7 @@ int gs_pinocchio_pk_export(gs_handle hpk, int which, uint64_t* jacobian, size_t 
     }
     if (which < 0 || which > 9) return fail(GS_ERR_ARG, "gs_pinocchio_pk_export: which must be 0..9");
     const bool g2 = which == 2;
-    const size_t have = which == 7 ? pk->ng1t : which == 9 ? pk->n_eval : pk->nvars;     // 9: evaluation-basis copy of G1T (0 points when there is none)
+    const size_t have = which == 7 ? pk->len_h : which == 9 ? pk->n_eval : pk->nvars;     // 9: evaluation-basis copy of G1T (0 points when there is none)
     if (count != have || (count && !jacobian)) return fail(GS_ERR_ARG, "gs_pinocchio_pk_export: array has %zu points, asked for %zu", have, count);
     if (!count) return GS_OK;
     const size_t words = g2 ? 48 : 24;
@@ -369,50 +369,40 @@ int gs_pinocchio_pk_export(gs_handle hpk, int which, uint64_t* jacobian, size_t 
 //   Groth16:   l_j(tau) Z(tau) / delta * G,     Pinocchio:   l_j(tau) * G        (l_j: Lagrange basis over the nodes n+1 .. 2n).
 // The library cannot check the points against tau (nobody knows tau any more); a wrong array gives proofs that do not verify,
 // exactly as a wrong PowersTauDelta does.  n_constraints must be len(Z) - 1 or len(Z).
+static int pk_set_eval_impl(Ctx& c, const char* fn, Kind kind, const char* slice_hint, gs_handle hpk, gs_handle hbases) {
+  ProverKey* pk = c.get<ProverKey>(hpk, kind);
+  Bases* b = c.get<Bases>(hbases, Kind::G1Bases);
+  if (!pk || !b) return fail(GS_ERR_ARG, "%s: bad handle", fn);
+  if (pk->shard_count != 1) return fail(GS_ERR_ARG, "%s: the key is a slice%s", fn, slice_hint);
+  const size_t n = b->n;
+  if (n < 2 || pk->nz == 0 || (pk->nz - 1 != n - 1 && pk->nz - 1 != n))
+    return fail(GS_ERR_SHAPE, "%s: %zu points, but deg Z = %zu needs n = deg Z or deg Z + 1 constraints", fn, n, pk->nz ? pk->nz - 1 : 0);
+  table_settle(c, pk->h_eval.table, false);
+  pk->h_eval.table.drop();
+  pk->h_eval.pts.alloc(n * 64);
+  GS_HIP(hipMemcpyAsync(pk->h_eval.pts.p, b->buf.p, n * 64, hipMemcpyDeviceToDevice, c.stream));
+  GS_HIP(hipStreamSynchronize(c.stream));
+  pk->n_eval = n; pk->e_lo = 0; pk->n_e = n;
+  return GS_OK;
+}
 int gs_groth16_pk_set_eval(gs_handle hpk, gs_handle hbases) {
+  return guarded([&](Ctx& c) -> int { return pk_set_eval_impl(c, "gs_groth16_pk_set_eval", Kind::GrothPk, "", hpk, hbases); }, true, false, hpk);
+}
+int gs_pinocchio_pk_set_eval(gs_handle hpk, gs_handle hbases) {
   return guarded([&](Ctx& c) -> int {
-    GrothPkObj* pk = c.get<GrothPkObj>(hpk, Kind::GrothPk);
-    Bases* b = c.get<Bases>(hbases, Kind::G1Bases);
-    if (!pk || !b) return fail(GS_ERR_ARG, "gs_groth16_pk_set_eval: bad handle");
-    if (pk->shard_count != 1) return fail(GS_ERR_ARG, "gs_groth16_pk_set_eval: the key is a slice");
-    const size_t n = b->n;
-    if (n < 2 || pk->nz == 0 || (pk->nz - 1 != n - 1 && pk->nz - 1 != n))
-      return fail(GS_ERR_SHAPE, "gs_groth16_pk_set_eval: %zu points, but deg Z = %zu needs n = deg Z or deg Z + 1 constraints", n, pk->nz ? pk->nz - 1 : 0);
-    table_settle(c, pk->t_ptd_eval, false);
-    pk->t_ptd_eval.drop();
-    pk->ptd_eval.alloc(n * 64);
-    GS_HIP(hipMemcpyAsync(pk->ptd_eval.p, b->buf.p, n * 64, hipMemcpyDeviceToDevice, c.stream));
-    GS_HIP(hipStreamSynchronize(c.stream));
-    pk->n_eval = n; pk->e_lo = 0; pk->n_e = n;
-    return GS_OK;
+    return pk_set_eval_impl(c, "gs_pinocchio_pk_set_eval", Kind::PinocchioPk, " (attach the array to the full key, then cut it)", hpk, hbases);
   }, true, false, hpk);
 }
 // number of evaluation-basis points a resident Groth16 or Pinocchio key holds (0 = none; a slice: its own share)
 int gs_pk_eval_count(gs_handle hpk, size_t* count) {
   return guarded([&](Ctx& c) -> int {
     if (!count) return fail(GS_ERR_ARG, "gs_pk_eval_count: null output");
-    if (GrothPkObj* g = c.get<GrothPkObj>(hpk, Kind::GrothPk)) { *count = g->n_e; return GS_OK; }
-    if (PinocchioPkObj* p = c.get<PinocchioPkObj>(hpk, Kind::PinocchioPk)) { *count = p->n_e; return GS_OK; }
-    return fail(GS_ERR_ARG, "gs_pk_eval_count: not a proving-key handle");
-  }, true, true, hpk);
-}
-int gs_pinocchio_pk_set_eval(gs_handle hpk, gs_handle hbases) {
-  return guarded([&](Ctx& c) -> int {
-    PinocchioPkObj* pk = c.get<PinocchioPkObj>(hpk, Kind::PinocchioPk);
-    Bases* b = c.get<Bases>(hbases, Kind::G1Bases);
-    if (!pk || !b) return fail(GS_ERR_ARG, "gs_pinocchio_pk_set_eval: bad handle");
-    if (pk->shard_count != 1) return fail(GS_ERR_ARG, "gs_pinocchio_pk_set_eval: the key is a slice (attach the array to the full key, then cut it)");
-    const size_t n = b->n;
-    if (n < 2 || pk->nz == 0 || (pk->nz - 1 != n - 1 && pk->nz - 1 != n))
-      return fail(GS_ERR_SHAPE, "gs_pinocchio_pk_set_eval: %zu points, but deg Z = %zu needs n = deg Z or deg Z + 1 constraints", n, pk->nz ? pk->nz - 1 : 0);
-    table_settle(c, pk->t_g1t_eval, false);
-    pk->t_g1t_eval.drop();
-    pk->g1t_eval.alloc(n * 64);
-    GS_HIP(hipMemcpyAsync(pk->g1t_eval.p, b->buf.p, n * 64, hipMemcpyDeviceToDevice, c.stream));
-    GS_HIP(hipStreamSynchronize(c.stream));
-    pk->n_eval = n; pk->e_lo = 0; pk->n_e = n;
+    auto it = c.objs.find(hpk);
+    ProverKey* pk = it == c.objs.end() ? nullptr : as_prover_key(it->second.get());
+    if (!pk) return fail(GS_ERR_ARG, "gs_pk_eval_count: not a proving-key handle");
+    *count = pk->n_e;
     return GS_OK;
-  }, true, false, hpk);
+  }, true, true, hpk);
 }
 
 }  // extern "C"

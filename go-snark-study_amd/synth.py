@@ -377,7 +377,7 @@ def gates_r1cs(n, seed, mul_share=0.5):
         `*`:   A = [u],     B = [v],    C = [out]
         `+`:   A = [u, v],  B = [one],  C = [out]
     so a signal enters B only as the second operand of a multiplication: with half the gates additions, ~60 % of the variables have
-    b_i(x) = 0 and their G1.BACGamma / G2.BACGamma points are the point at infinity (what GrothPkObj::b_mask is for).
+    b_i(x) = 0 and their G1.BACGamma / G2.BACGamma points are the point at infinity (what ProverKey::b_index is for).
     Variables [one, x (public), v_2 .. v_n] (m = n + 1, NPublic = 1); constraint j = 1..n-1 defines v_{j+1} from two uniformly chosen
     earlier variables (index 1..j); constraint n is one * one = one.  The values are full-width field elements after a few products.
     Returns (a_csr, b_csr, c_csr, w [m,4] uint64, counts)."""
@@ -476,7 +476,7 @@ class SqchainPinocchioInstance:
 
 
 class GatesPinocchioInstance(SqchainPinocchioInstance):
-    """gates_r1cs under the Pinocchio protocol: B (G2) and B' of its key are mostly the point at infinity (PinocchioPkObj::b_index)."""
+    """gates_r1cs under the Pinocchio protocol: B (G2) and B' of its key are mostly the point at infinity (ProverKey::b_index)."""
 
     def __init__(self, n, seed, mul_share=0.5):
         from . import r1csqap, snark

@@ -1,4 +1,4 @@
-"""A/B of how a host-buffer ticket's arrays reach its slot (GS_HOST_STAGE = 0 / 1 / 2, csrc/prove.hip) -- dev tool.
+"""A/B of how a host-buffer ticket's arrays reach its slot (GS_HOST_STAGE = 0 / 1 / 2, csrc/prove.hip, host_stage_mode) -- dev tool.
 One process per mode (the switch is read once); prints the ms per proof of bench.py's distinct-witness streams."""
 import json
 import os
