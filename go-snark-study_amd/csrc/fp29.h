@@ -13,10 +13,17 @@
 // of v_mad_u64_u32 with NO carry instructions: 162 mads + ~35 shift/mask ops per product.
 // Additions are 9 independent full-rate v_add_u32 plus a carry-save "nearly normal" fix-up.
 //
-// Invariants ("nearly normal"): limbs 0..7 < 2^29 + 8, limb 8 (top) < 2^29; the VALUE of an
-// Fe<M,B> is < B*p (B is a compile-time bound, so every formula is overflow-checked by the
-// type system: mul needs Ba*Bb <= 160 and returns a value < 2p).  Values are only made
-// canonical ([0,p)) at the C-ABI boundary.
+// The contract of an Fe<M,B> ("nearly normal"), stated once -- kNearlyNormalMax below is the same number, every static check
+// assumes exactly this, and tests/device/limit_ops.h feeds operands AT these limits:
+//   limbs: limbs 0..7 < kNearlyNormalMax = 2^29 + 8.  That is what carry_save leaves (limb 0 < 2^29 exactly, limbs 1..7 < 2^29 + 8:
+//          the carry of a limb below 2^32 is at most 7) and every other producer is fully normal (Montgomery results, sub_ripple,
+//          reduce2, canon, unpack32, the constants).  The bias tables tolerate more (tools/gen_constants.py: subtrahend limbs
+//          below 2^29 + 16), the lazy limb weights do NOT: two limbs of an add_lazy / dbl_lazy must stay below limb_max(2).
+//   value: < B*p, B a compile-time bound, so every formula is overflow-checked by the type system (mul needs Ba*Bb <= 160 and
+//          returns a value < 2p; limb 8, the top one, follows from the value).  One value sits AT its bound: neg / neg_lazy of
+//          zero is K p itself.  Every consumer takes that: 160 p^2 / 2^261 + p < 1.95 p, the bias rows are built for subtrahends
+//          <= (K - 1) p, canon subtracts B times, is_zero and reduce2 divide the top limb.
+// Values are only made canonical ([0,p)) at the C-ABI boundary.
 #pragma once
 #include <stdint.h>
 #include <hip/hip_runtime.h>
@@ -179,7 +186,8 @@ GS_HD Fe<M, B + 1> neg(const Fe<M, B>& a) {
 // are used exactly once, as ONE operand of a Montgomery product.  The 64-bit column accumulator has room for that: a column
 // is 9 T products of nearly-normal limbs (T terms, each < 2^58 (1 + 2^-25)) + 9 reduction products (< 2^58) + the carry of the
 // previous column (< 2^36), and 2^64 / (9 * 2^58) = 7.1.  Lz<M, B, W> is a field element of VALUE < B p whose limbs are only
-// bounded by W * 2^29 + 16 (W = 2: an un-carried add / dbl / neg, 3: an un-carried sub): a product term with operand limb
+// bounded by limb_max(W) = W * 2^29 + 16, which follows from the Fe contract at the top (static_assert below: 2 kNearlyNormalMax and
+// kNearlyNormalMax + 2^30 fit) (W = 2: an un-carried add / dbl / neg, 3: an un-carried sub): a product term with operand limb
 // weights (wa, wb) counts wa * wb instead of 1, and every dot product statically checks  9 * sum_t maxa_t * maxb_t + 9 * 2^58 +
 // 2^36 < 2^64  with the exact limb maxima (dot_of below).  Nothing but dot_of (and select / normalize) accepts an Lz.
 template <class M, int B, int W>
@@ -187,8 +195,11 @@ struct Lz {
   static_assert(B >= 1 && B <= M::kMaxBiasK && W >= 1 && W <= 3, "lazy element out of range");
   uint32_t l[NL];
 };
-constexpr uint64_t kNearlyNormalMax = (1ull << LB) + 16;          // limbs 0..7 of a nearly-normal Fe stay below this
-constexpr uint64_t limb_max(int w) { return (uint64_t)w * (1ull << LB) + 16; }
+constexpr uint64_t kNearlyNormalMax = (1ull << LB) + 8;           // limbs 0..7 of a nearly-normal Fe stay below this (the contract at the top)
+constexpr uint64_t limb_max(int w) { return (uint64_t)w * (1ull << LB) + 16; }     // limbs of an Lz of weight w stay below this
+static_assert(kNearlyNormalMax <= limb_max(1) && 2 * kNearlyNormalMax <= limb_max(2) &&      // Fe | add_lazy, dbl_lazy
+              (1ull << 30) <= limb_max(2) && kNearlyNormalMax + (1ull << 30) <= limb_max(3),  // neg_lazy (tbias limbs < 2^30) | sub_lazy
+              "the limb weights of the lazy ops follow from the nearly-normal contract");
 
 template <class X> struct Operand;                                 // value bound + limb weight of a product operand
 template <class M, int B> struct Operand<Fe<M, B>> { using Mod = M; static constexpr int bound = B, weight = 1; };
@@ -221,7 +232,7 @@ template <class M, int B, int W> GS_HD Fe<M, B> normalize(const Lz<M, B, W>& a) 
   carry_save(r);
   return r;
 }
-// a + b, limbs < 2^30 + 32
+// a + b, limbs < 2 kNearlyNormalMax = 2^30 + 16
 template <class M, int Ba, int Bb>
 GS_HD Lz<M, Ba + Bb, 2> add_lazy(const Fe<M, Ba>& a, const Fe<M, Bb>& b) {
   Lz<M, Ba + Bb, 2> r;
@@ -244,7 +255,7 @@ GS_HD Lz<M, M::tbias_k(B + 1), 2> neg_lazy(const Fe<M, B>& a) {
   for (int i = 0; i < NL; ++i) r.l[i] = M::tbias(B + 1, i) - a.l[i];
   return r;
 }
-// a - b + K p, limbs < 3 * 2^29 + 16
+// a - b + K p, limbs < kNearlyNormalMax + 2^30 = 3 * 2^29 + 8
 template <class M, int Ba, int Bb>
 GS_HD Lz<M, Ba + M::tbias_k(Bb + 1), 3> sub_lazy(const Fe<M, Ba>& a, const Fe<M, Bb>& b) {
   Lz<M, Ba + M::tbias_k(Bb + 1), 3> r;
@@ -704,8 +715,8 @@ GS_HD Fe<M, 1> canon(const Fe<M, B>& a) {
   return r;
 }
 
-// Cheap necessary condition for value == 0 (mod p) on a NEARLY-NORMAL element (limb 0 < 2^29 exactly, limbs 1..7 < 2^29 + 16: what
-// every carry_save leaves), without the rippling carry pass: value = k p has k = floor(top / p_top) for the fully carried top limb,
+// Cheap necessary condition for value == 0 (mod p) on a NEARLY-NORMAL element (the contract at the top; limb 0 is masked, so it
+// need not be below 2^29), without the rippling carry pass: value = k p has k = floor(top / p_top) for the fully carried top limb,
 // which is l[8] or l[8] + 1, so k is one of two candidates and limb 0 -- exact as it stands -- must equal (k p) mod 2^29 for one of
 // them.  Wrong with probability 2^-28 per candidate on a random element; is_zero then decides exactly.  (The zero test of P in
 // every mixed addition took a full carry pass + the multiple check: ~30 instructions; this is ~9.)

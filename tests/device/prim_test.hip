@@ -7,6 +7,7 @@
 
 #include "../../go-snark-study_amd/csrc/ec.h"
 #include "../../go-snark-study_amd/csrc/point_io.h"
+#include "limit_ops.h"
 
 using namespace gs;
 
@@ -143,7 +144,44 @@ int run(int kind, int op, const void* a, const void* b, void* out, uint32_t n, s
   return e == hipSuccess ? 0 : -3;
 }
 
+// raw limbs in, raw limbs out: one record of tests/device/limit_ops.h per thread (plain uint32 loads and stores)
+template <int KIND>
+__global__ void k_raw(int op, const uint32_t* in, uint32_t* out, uint32_t n) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  limits::run_case(KIND, op, in + (size_t)i * limits::in_words(KIND), out + (size_t)i * limits::out_words(KIND));
+}
+
+int run_raw(int kind, int op, const void* in, void* out, uint32_t n) {
+  const size_t bi = (size_t)n * limits::in_words(kind) * 4, bo = (size_t)n * limits::out_words(kind) * 4;
+  uint32_t *din = nullptr, *dout = nullptr;
+  if (n == 0) return 0;
+  if (hipMalloc(&din, bi) != hipSuccess) return -1;
+  if (hipMalloc(&dout, bo) != hipSuccess) { (void)hipFree(din); return -1; }
+  bool ok = hipMemcpy(din, in, bi, hipMemcpyHostToDevice) == hipSuccess && hipMemset(dout, 0, bo) == hipSuccess;
+  if (ok) {
+    const dim3 grid((n + 63) / 64), block(64);
+    switch (kind) {
+      case 0: hipLaunchKernelGGL(k_raw<0>, grid, block, 0, 0, op, din, dout, n); break;
+      case 1: hipLaunchKernelGGL(k_raw<1>, grid, block, 0, 0, op, din, dout, n); break;
+      case 2: hipLaunchKernelGGL(k_raw<2>, grid, block, 0, 0, op, din, dout, n); break;
+      case 3: hipLaunchKernelGGL(k_raw<3>, grid, block, 0, 0, op, din, dout, n); break;
+      case 4: hipLaunchKernelGGL(k_raw<4>, grid, block, 0, 0, op, din, dout, n); break;
+    }
+    ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess && hipMemcpy(out, dout, bo, hipMemcpyDeviceToHost) == hipSuccess;
+  }
+  ok = (hipFree(din) == hipSuccess) & (hipFree(dout) == hipSuccess) & ok;
+  return ok ? 0 : -3;
+}
+
 }  // namespace
+
+// the op table of tests/device/limit_ops.h on raw limbs: n records of limits::in_words(kind) words in, limits::out_words(kind) out
+extern "C" __attribute__((visibility("default")))
+int gs_prim_run_raw(int kind /* 0 Fq, 1 Fr, 2 Fq2, 3 G1, 4 G2 */, int op, const void* in, void* out, uint32_t n) {
+  if (kind < 0 || kind > 4) return -2;
+  return run_raw(kind, op, in, out, n);
+}
 
 extern "C" __attribute__((visibility("default")))
 int gs_prim_run(int kind /* 0 Fq, 1 Fr, 2 Fq2, 3 G1, 4 G2 */, int op, const void* a, const void* b, void* out, uint32_t n) {

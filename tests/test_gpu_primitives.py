@@ -16,6 +16,8 @@ import pytest
 import gosnark_amd  # noqa: F401
 from gosnark_amd import capi
 import gpu_util as U
+import hostbuild
+import limits_util as L
 from oracle import ref_py as O
 
 pytestmark = pytest.mark.gpu
@@ -34,6 +36,8 @@ def lib():
         _lib = ctypes.CDLL(LIB)
         _lib.gs_prim_run.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32]
         _lib.gs_prim_run.restype = ctypes.c_int
+        _lib.gs_prim_run_raw.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32]
+        _lib.gs_prim_run_raw.restype = ctypes.c_int
     return _lib
 
 
@@ -154,3 +158,57 @@ def test_g2_point_operations_on_the_device():
     kq = [c for k in ks for c in (k, 0, 0, 0, 0, 0)]
     got = run(4, 4, flat(P), kq, 6)
     assert got == [c for p, k in zip(P, ks) for c in aff(G.MulScalar(p, k))]
+
+
+# ---- the raw-limb op table (tests/device/limit_ops.h) at the limits of the bound types: the device twins of tests/test_limits_host.py ----
+def run_raw(kind, op, records):
+    """n records of L.in_words(kind) uint32 -> n x L.out_words(kind), through gs_prim_run_raw"""
+    a = np.ascontiguousarray(records, dtype=np.uint32)
+    assert a.shape == (len(a), L.in_words(kind))
+    out = np.zeros((len(a), L.out_words(kind)), dtype=np.uint32)
+    rc = lib().gs_prim_run_raw(kind, op, a.ctypes.data, out.ctypes.data, len(a))
+    assert rc == 0, rc
+    return out
+
+
+@pytest.fixture(scope="module")
+def limits_exe():
+    return hostbuild.build("fp_limits_host_test")
+
+
+def _same_limbs(dev, host, name):
+    bad = np.argwhere(dev != host)
+    assert len(bad) == 0, "%s: device and host builds differ, first at record %d word %d: %d != %d" % (
+        name, bad[0][0], bad[0][1], dev[tuple(bad[0])], host[tuple(bad[0])])
+
+
+@pytest.mark.parametrize("kind", [0, 1, 2], ids=["q", "r", "fq2"])
+def test_field_ops_at_their_limits_on_the_device(limits_exe, kind):
+    """Every op of the table on raw limbs at the contract's edge (saturated limbs, largest top limb, k p +- 1, underflow pairs): the
+    device result satisfies the same exact integer checks as the host build's and equals it limb for limb (same source, both
+    integer-exact: a difference is a code-generation difference -- GS_STEP / GS_PIN asm, v_mad_u64_u32 chains, device-only paths)."""
+    tb = L.Tables(0 if kind == 2 else kind, run_raw)
+    tb.check()
+    plan = L.field_plan(kind, tb, 2024 + kind)
+    host = L.host_run(limits_exe, [(kind, op.id, L.pack_field([s for s, _ in cases])) for op, cases in plan])
+    for (op, cases), h in zip(plan, host):
+        dev = run_raw(kind, op.id, L.pack_field([s for s, _ in cases]))
+        L.check_field_op(op, kind, tb, cases, dev)
+        _same_limbs(dev, h, op.name)
+
+
+@pytest.mark.parametrize("kind", [3, 4], ids=["g1", "g2"])
+def test_point_ops_with_accumulators_at_the_top_of_their_types_on_the_device(limits_exe, kind):
+    """xyzz_madd (+ negate), xyzz_add, xyzz_add_mem, xyzz_dbl and -- its first device test -- the tight accumulator XyzzAcc<Fq2Tag> with
+    its own xyzz_madd (the mixed addition of k_bucket_accumulate<G2>), on raw XYZZ limbs with every coordinate shifted up to the largest
+    multiple of p its type admits: P + Q, P + P, P + (-P), infinity on either side.  Types, ZZ^3 == ZZZ^2, the oracle's affine sum,
+    and limb-for-limb equality with the host build."""
+    plan = L.point_plan(kind, 4040 + kind)
+    ops = sorted(plan)
+    assert (5 in ops and 6 in ops) == (kind == 4)
+    recs = {op: np.array([r for r, _, _ in plan[op]], dtype=np.uint32) for op in ops}
+    host = L.host_run(limits_exe, [(kind, op, recs[op]) for op in ops])
+    for op, h in zip(ops, host):
+        dev = run_raw(kind, op, recs[op])
+        L.check_point_op(kind, op, plan[op], dev)
+        _same_limbs(dev, h, L.POINT_OPS[op])
