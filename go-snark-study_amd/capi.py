@@ -86,6 +86,11 @@ _SIGS = {
     "gs_groth16_pk_set_eval": [Handle, Handle],
     "gs_pk_eval_count": [Handle, ctypes.POINTER(ctypes.c_size_t)],
     "gs_pinocchio_pk_set_eval": [Handle, Handle],
+    "gs_groth16_pk_set_quot": [Handle, Handle],
+    "gs_pinocchio_pk_set_quot": [Handle, Handle],
+    "gs_pk_quot_count": [Handle, ctypes.POINTER(ctypes.c_size_t)],
+    "gs_groth16_pk_derive_quot": [Handle],
+    "gs_pinocchio_pk_derive_quot": [Handle],
     "gs_pinocchio_prove_witness_begin": [Handle, Handle, Handle, u64p],
     "gs_groth16_prove_begin": [Handle, Handle, Handle, u64p, u64p, u64p],
     "gs_groth16_prove_end": [ctypes.c_uint64, u64p, intp],
@@ -345,6 +350,13 @@ def pk_eval_count(pk_handle):
     """gs_pk_eval_count: evaluation-basis points a resident Groth16 / Pinocchio key holds (0 = none)."""
     n = ctypes.c_size_t(0)
     check(load_library().gs_pk_eval_count(Handle(_raw(pk_handle)), ctypes.byref(n)))
+    return int(n.value)
+
+
+def pk_quot_count(pk_handle):
+    """gs_pk_quot_count: quotient-basis points a resident Groth16 / Pinocchio key holds (0 = none: the h-sum divides px by Z)."""
+    n = ctypes.c_size_t(0)
+    check(load_library().gs_pk_quot_count(Handle(_raw(pk_handle)), ctypes.byref(n)))
     return int(n.value)
 
 

@@ -149,7 +149,8 @@ int gs_set_table_policy(int policy) {
 
 // Build the window tables of a key or base array NOW (a server that loads a key it will prove with for hours; bench.py's steady
 // state): blocking, whatever the policy.  route (keys only): 0 = everything the key can use, 1 = the arrays of the px routes
-// (PowersTauDelta / G1T), 2 = those of the witness routes (the evaluation-basis array when the key has one).  The widths are the
+// (PowersTauDelta / G1T -- or the quotient-basis array in their place, when the key has one), 2 = those of the witness routes (the
+// evaluation-basis array when the key has one).  The widths are the
 // ones a full-range proof / MSM picks; a later call with another width (gs_set_window_bits, a shard of a full key) rebuilds or goes
 // table-free as the policy says.
 int gs_build_tables(gs_handle h, int route) {
@@ -178,7 +179,10 @@ int gs_build_tables(gs_handle h, int route) {
         for_each_table(o, [&](BaseTable& t) { t.last_use = c.call_clock; });      // none of them is this call's eviction victim
         for (int i = 0; i < k->n_g1w; ++i) build(k->g1w[i].table, k->g1w[i].pts, k->n_w, false);
         build(k->g2w.table, k->g2w.pts, k->n_w, true);
-        if (route != 2) build(k->h.table, k->h.pts, k->n_h, false);
+        // the px routes: over the quotient-basis array when the key serves them from it (prove.h) -- then h gets no table here; a call
+        // that still needs h (px shorter than Z's range allows, a witness proof on the coefficient route) builds it as the policy says
+        if (route != 2 && k->serves_quot()) build(k->h_quot.table, k->h_quot.pts, k->n_q, false);
+        else if (route != 2) build(k->h.table, k->h.pts, k->n_h, false);
         if (route != 1 && k->n_e) build(k->h_eval.table, k->h_eval.pts, k->n_e, false);
         return GS_OK;
       }

@@ -1,0 +1,149 @@
+// The quotient-basis array (prove.h, ProverKey::h_quot) of a key that was built elsewhere: nobody knows tau, the key has only its h
+// array T, and  Q[m] = sum_{d <= m} g_d T[m - d]  (g = 1 / rev(Z)) is a convolution of a scalar series with a POINT sequence -- computed
+// like any convolution, with the transform carried out in the group: T is zero-padded (points at infinity) to N = 2^ceil(log2(2 len_h - 1))
+// XYZZ points, radix-2 stages whose butterflies are (P + Q, w (P - Q)) forwards and (P + w Q, P - w Q) backwards run over it in
+// global memory (one butterfly is a 254-bit scalar multiplication, ~340 point operations: the stages are compute-bound), the spectrum
+// is multiplied point by point with the spectrum of g (the polynomial engine's own transform of the divisor's series, 1 / N folded in),
+// and the first len_h points of the result are normalised to affine.  The stages index exactly as ntt_forward / ntt_inverse_unscaled
+// do (natural in, bit-reversed out, and back), so the two spectra meet without a permutation pass.  Every addition is the complete
+// one: the padding is made of infinities, and a key may hold equal or opposite points.
+// N / 2 * log2 N + N scalar multiplications -- seconds for a 2^20 key, once per key; explicit only (no policy derives the array).
+#include <algorithm>
+
+#include "point_io.h"
+#include "prove.h"
+
+using namespace gs;
+
+namespace {
+
+constexpr int kPw = PointIO<FqTag>::kXyzzWords;
+
+static inline dim3 grid1(size_t n, int block = 256) { return dim3((unsigned)((n + block - 1) / block)); }
+
+GS_HD void load_words(const uint32_t* __restrict__ p, uint32_t (&k)[8]) {
+#pragma unroll
+  for (int i = 0; i < 8; ++i) k[i] = p[i];
+}
+
+// pts[i] = T[i] for i < n, the point at infinity for n <= i < total
+__global__ void __launch_bounds__(256) k_ec_load(const uint32_t* __restrict__ affine, uint32_t n, uint32_t* __restrict__ pts, uint32_t total) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  G1Xyzz p = xyzz_inf<FqTag>();
+  if (i < n) p = xyzz_from_affine(PointIO<FqTag>::load_affine(affine + (size_t)i * 16));
+  store_xyzz<FqTag>(pts + (size_t)i * kPw, p);
+}
+
+// One radix-2 stage over `total` = 2 * nbf points, butterflies of span `half` (a power of two), twiddle of butterfly j within its
+// block: tw[j * tstep] (8 standard-form words each; tw[0] = 1 is not multiplied).
+//   forward (decimation in frequency):  (a, b) -> (a + b, (a - b) w)       inverse (decimation in time):  (a, b) -> (a + w b, a - w b)
+template <bool kInverse>
+__global__ void __launch_bounds__(64) k_ec_stage(uint32_t* __restrict__ pts, uint32_t nbf, uint32_t half, uint32_t tstep, const uint32_t* __restrict__ tw) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= nbf) return;
+  const uint32_t j = t & (half - 1);
+  const size_t i0 = (size_t)(t - j) * 2 + j, i1 = i0 + half;
+  G1Xyzz a = load_xyzz<FqTag>(pts + i0 * kPw), b = load_xyzz<FqTag>(pts + i1 * kPw);
+  const uint32_t e = j * tstep;
+  uint32_t k[8];
+  if (e) load_words(tw + (size_t)e * 8, k);
+  if (kInverse) {
+    if (e && !is_inf(b)) b = xyzz_mul_words_w4(b, k);
+    G1Xyzz d = a;
+    xyzz_add(a, b);
+    xyzz_add(d, xyzz_neg(b));
+    store_xyzz<FqTag>(pts + i0 * kPw, a);
+    store_xyzz<FqTag>(pts + i1 * kPw, d);
+  } else {
+    G1Xyzz d = a;
+    xyzz_add(a, b);
+    xyzz_add(d, xyzz_neg(b));
+    if (e && !is_inf(d)) d = xyzz_mul_words_w4(d, k);
+    store_xyzz<FqTag>(pts + i0 * kPw, a);
+    store_xyzz<FqTag>(pts + i1 * kPw, d);
+  }
+}
+
+// pts[i] = spec[i] * pts[i]
+__global__ void __launch_bounds__(64) k_ec_scale(uint32_t* __restrict__ pts, const uint32_t* __restrict__ spec, uint32_t total) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  G1Xyzz p = load_xyzz<FqTag>(pts + (size_t)i * kPw);
+  if (is_inf(p)) return;
+  uint32_t k[8];
+  load_words(spec + (size_t)i * 8, k);
+  store_xyzz<FqTag>(pts + (size_t)i * kPw, xyzz_mul_words_w4(p, k));
+}
+
+__global__ void __launch_bounds__(256) k_ec_to_affine(const uint32_t* __restrict__ pts, uint32_t n, uint32_t* __restrict__ affine) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  PointIO<FqTag>::store_affine(affine + (size_t)i * 16, xyzz_to_affine(load_xyzz<FqTag>(pts + (size_t)i * kPw)));
+}
+
+// omega_N^(+-1) as standard-form words, N = 2^logn
+void root_words(int logn, bool inverse, uint64_t out[4]) {
+  Fe<ModR, 2> w;
+  for (int i = 0; i < NL; ++i) w.l[i] = inverse ? ModR::omega28_inv_mont(i) : ModR::omega28_mont(i);
+  for (int i = 0; i < ModR::kTwoAdicity - logn; ++i) w = sqr(w);
+  fr_words_from_mont(w, out);
+}
+
+int pk_derive_quot_impl(Ctx& c, const char* fn, Kind kind, gs_handle hpk) {
+  ProverKey* pk = c.get<ProverKey>(hpk, kind);
+  if (!pk) return fail(GS_ERR_ARG, "%s: bad proving-key handle", fn);
+  if (pk->shard_count != 1) return fail(GS_ERR_ARG, "%s: the key is a slice (key slices carry no quotient-basis array)", fn);
+  const size_t n = pk->len_h;
+  if (n == 0 || pk->nz == 0) return fail(GS_ERR_SHAPE, "%s: the key has no h array or no Z", fn);
+  const int logn = ceil_log2(2 * n - 1);
+  if (logn > ModR::kTwoAdicity) return fail(GS_ERR_ARG, "%s: key too large", fn);
+  const size_t N = (size_t)1 << logn, half_n = std::max<size_t>(N / 2, 1);
+  c.drain();
+  // the scalar side, by the polynomial engine: spectrum of g (/ N, standard words) and the two twiddle tables
+  divisor_ensure(c, pk->z, n);
+  DevBuf gp(N * 32), spec(N * 32), twf(half_n * 32), twi(half_n * 32);
+  GS_HIP(hipMemcpyAsync(gp.p, pk->z.inv_rev_mont.p, n * 32, hipMemcpyDeviceToDevice, c.stream));
+  if (N > n) GS_HIP(hipMemsetAsync(gp.as<uint32_t>() + n * 8, 0, (N - n) * 32, c.stream));
+  ntt_forward(c, gp.as<uint32_t>(), logn, logn);
+  const uint64_t one[4] = {1, 0, 0, 0}, nn[4] = {(uint64_t)N, 0, 0, 0};
+  uint64_t inv_n[4], w[4], wi[4];
+  fr_inv_words(nn, inv_n);
+  scale_mont_by_std_dev(c, gp.as<uint32_t>(), inv_n, N, spec.as<uint32_t>());
+  root_words(logn, false, w);
+  root_words(logn, true, wi);
+  scaled_powers_dev(c, w, one, half_n, twf.as<uint32_t>());
+  scaled_powers_dev(c, wi, one, half_n, twi.as<uint32_t>());
+  // the group side
+  DevBuf pts(N * kPw * 4);
+  hipLaunchKernelGGL(k_ec_load, grid1(N), dim3(256), 0, c.stream, pk->h.pts.as<uint32_t>(), (uint32_t)n, pts.as<uint32_t>(), (uint32_t)N);
+  const uint32_t nbf = (uint32_t)(N / 2);
+  for (int s = 0; s < logn; ++s)                       // spans N/2, N/4, .., 1
+    hipLaunchKernelGGL((k_ec_stage<false>), grid1(nbf, 64), dim3(64), 0, c.stream, pts.as<uint32_t>(), nbf, (uint32_t)(N >> (s + 1)), 1u << s, twf.as<uint32_t>());
+  hipLaunchKernelGGL(k_ec_scale, grid1(N, 64), dim3(64), 0, c.stream, pts.as<uint32_t>(), spec.as<uint32_t>(), (uint32_t)N);
+  for (int s = logn - 1; s >= 0; --s)                  // spans 1, 2, .., N/2
+    hipLaunchKernelGGL((k_ec_stage<true>), grid1(nbf, 64), dim3(64), 0, c.stream, pts.as<uint32_t>(), nbf, (uint32_t)(N >> (s + 1)), 1u << s, twi.as<uint32_t>());
+  GS_HIP(hipGetLastError());
+  table_settle(c, pk->h_quot.table, false);
+  pk->h_quot.table.drop();
+  pk->n_q = 0;
+  pk->h_quot.pts.alloc(n * 64);
+  hipLaunchKernelGGL(k_ec_to_affine, grid1(n), dim3(256), 0, c.stream, pts.as<uint32_t>(), (uint32_t)n, pk->h_quot.pts.as<uint32_t>());
+  GS_HIP(hipGetLastError());
+  GS_HIP(hipStreamSynchronize(c.stream));
+  pk->n_q = n;
+  return GS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gs_groth16_pk_derive_quot(gs_handle hpk) {
+  return guarded([&](Ctx& c) -> int { return pk_derive_quot_impl(c, "gs_groth16_pk_derive_quot", Kind::GrothPk, hpk); }, true, false, hpk);
+}
+int gs_pinocchio_pk_derive_quot(gs_handle hpk) {
+  return guarded([&](Ctx& c) -> int { return pk_derive_quot_impl(c, "gs_pinocchio_pk_derive_quot", Kind::PinocchioPk, hpk); }, true, false, hpk);
+}
+
+}  // extern "C"

@@ -38,6 +38,8 @@ struct Divisor {
   DevBuf inv_spec;         // NTT of inv_rev_mont[:k_spec] zero padded (bit-reversed order)
 };
 void divisor_init(Ctx& c, Divisor& d, const uint32_t* b_std_dev, size_t nb);
+// make inv_rev_mont hold at least k coefficients of 1 / rev(b) (synchronises the stream when it has to compute them)
+void divisor_ensure(Ctx& c, Divisor& d, size_t k);
 // quo (na - nb + 1 coefficients, standard form, values < 2r) = floor(a / b); a standard form.
 void poly_quotient_dev(Ctx& c, Divisor& d, const uint32_t* a_std, size_t na, uint32_t* quo_std);
 

@@ -257,7 +257,7 @@ void divisor_init(Ctx& c, Divisor& d, const uint32_t* b_std_dev, size_t nb) {
   d.k_spec = 0;
 }
 
-static void divisor_ensure(Ctx& c, Divisor& d, size_t k) {
+void divisor_ensure(Ctx& c, Divisor& d, size_t k) {
   if (k <= d.k) return;
   // f = rev(b) in Montgomery form, only the first min(nb, k) coefficients matter
   const size_t fl = std::min(d.nb, k);

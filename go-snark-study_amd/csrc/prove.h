@@ -38,6 +38,15 @@ struct ProverKey : Object {
   // the witness route runs the h-MSM over H's VALUES and never interpolates H.  A slice holds entries [e_lo, e_lo + n_e).
   size_t n_eval = 0, e_lo = 0, n_e = 0;
   KeyArray h_eval;
+  // Quotient-basis twin of h (optional; the setups build it, gs_*_pk_set_quot attaches one): with D = deg Z and g = 1 / rev(Z) as a
+  // power series (z.inv_rev_mont),  h_quot[m] = sum_{d <= m} g_d h[m - d],  m < n_q = len_h.  floor(x^i / Z) = sum_d g_d x^(i-D-d), so
+  // for every px with nh = len(px) - D >= 1 coefficients of floor(px / Z):
+  //   sum_{j < nh} floor(px / Z)_j h[j] = sum_{m < nh} px[D + m] h_quot[m]:
+  // the h-MSM runs over the top coefficients of px as they are and nothing is divided by Z (prove.hip, proof_enqueue).  A key that
+  // holds the array serves the px routes from it and builds no window table of h for them.  Full keys only: the key slices
+  // (gs_*_pk_shard*) carry no quotient-basis array and keep the division.
+  size_t n_q = 0;
+  KeyArray h_quot;
   // The workspace sets (of the eight a ticket slot owns; the G1 group over w takes set 0) of the G2 group, of the B' group of a
   // proof with split B, and of the h group.  They decide which grow-only buffers a proof touches, hence gs_memory.
   const int ws_g2, ws_b, ws_h;
@@ -53,10 +62,16 @@ struct ProverKey : Object {
   std::vector<uint32_t> b_index_host;
   size_t b_finite = 0;
 
-  // every array with its held length, in the fixed order  g1w .. | h | g2w | h_eval  (f(KeyArray&, size_t n, bool g2))
+  // every array with its held length, in the fixed order  g1w .. | h | g2w | h_eval | h_quot  (f(KeyArray&, size_t n, bool g2))
   template <class F> void for_each_array(F f) {
     for (int i = 0; i < n_g1w; ++i) f(g1w[i], n_w, false);
-    f(h, n_h, false); f(g2w, n_w, true); f(h_eval, n_e, false);
+    f(h, n_h, false); f(g2w, n_w, true); f(h_eval, n_e, false); f(h_quot, n_q, false);
+  }
+  // the px routes of this key sum h over px's top coefficients against h_quot (GS_NO_QUOT_BASIS: divide by Z although the key has
+  // the array -- same proofs, for A/B runs)
+  bool serves_quot() const {
+    static const bool off = run_flag("GS_NO_QUOT_BASIS");
+    return n_q != 0 && !off;
   }
  protected:
   ProverKey(Kind k, const char* scheme_, const char* hx_too_long_, int n_g1w_, int b_g1_, int ws_g2_, int ws_b_, int ws_h_)
@@ -76,6 +91,7 @@ struct GrothPkObj : ProverKey {   // groth16.Pk (groth16/groth16.go:15-32), resi
   DevBuf& bacgamma2() { return g2w.pts; }
   DevBuf& ptd() { return h.pts; }                       // PowersTauDelta
   DevBuf& ptd_eval() { return h_eval.pts; }             // l_j(tau) * Z(tau) / delta * G
+  DevBuf& ptd_quot() { return h_quot.pts; }
   G1Affine alpha, beta, delta;             // host, Montgomery
   G2Affine beta2, delta2;
   // host-side window tables of delta / delta2 for the tail's result-independent products (built on the first proof of the key)
@@ -99,6 +115,7 @@ struct PinocchioPkObj : ProverKey {  // snark.Pk (snark.go:16-26), resident
   DevBuf& b2() { return g2w.pts; }
   DevBuf& g1t() { return h.pts; }
   DevBuf& g1t_eval() { return h_eval.pts; }             // l_j(tau) * G
+  DevBuf& g1t_quot() { return h_quot.pts; }
   PinocchioPkObj() : ProverKey(kKind, "pinocchio", "len(hx) = %zu exceeds len(G1T) = %zu (snark.go:284-286)", 6, kBp, 6, 5, 7) {}
 };
 

@@ -218,6 +218,10 @@ int proof_enqueue(Ctx& c, ProverKey* pk, DevScalars w, DevScalars px, const Shar
   const size_t nh = eval ? pk->n_eval : quotient_len(px.n, pk->nz);
   if (!eval && nh > pk->len_h) return fail(GS_ERR_SHAPE, pk->hx_too_long, nh, pk->len_h);
   const bool sliced = pk->shard_count > 1;
+  // Quotient-basis route (prove.h, h_quot): px is given, or comes out of px.produce, and the key holds the array -- the h-sum runs over
+  // px[D ..] directly.  Decided here because it decides which array's table the call prepares.  (A witness proof that may compute H
+  // itself -- produce_hx -- keeps its route, and with it the division when that route does not apply.)
+  const bool quot = !eval && !px.produce_hx && !sliced && nh >= 1 && pk->serves_quot() && nh <= pk->n_q;
   if (sliced && (shard.index != pk->shard_index || shard.count != pk->shard_count))
     return fail(GS_ERR_ARG, "this key holds shard %zu of %zu of the term ranges only: call gs_%s_prove_partials with that shard "
                 "(asked for %zu of %zu)", pk->shard_index, pk->shard_count, pk->scheme, shard.index, shard.count);
@@ -241,8 +245,8 @@ int proof_enqueue(Ctx& c, ProverKey* pk, DevScalars w, DevScalars px, const Shar
   }
   int cw = 0, ch = 0;
   const int ng = pk->n_g1w, bg = pk->b_g1;
-  KeyArray& harr = eval ? pk->h_eval : pk->h;
-  const size_t n_harr = eval ? pk->n_e : pk->n_h;
+  KeyArray& harr = eval ? pk->h_eval : quot ? pk->h_quot : pk->h;
+  const size_t n_harr = eval ? pk->n_e : quot ? pk->n_q : pk->n_h;
   // every table of the call is stamped before one is built (an allocation for the first group must not evict the second group's), and
   // under policy `auto` the call grants itself a build credit for its job-units over w and h (a G1 sum = 1, the G2 sum = 2.76: ~6.8
   // for a Groth16 proof; msm.h, prepare_tables)
@@ -258,7 +262,7 @@ int proof_enqueue(Ctx& c, ProverKey* pk, DevScalars w, DevScalars px, const Shar
   double credit = build_credit((double)ng + 2.76 + 1.0, whi - wlo);
   const bool tab_w = prepare_tables(c, refs_w, (uint32_t)(whi - wlo), &cw, &credit);
   const bool tab_h = prepare_tables(c, {TableRef{&harr.table, harr.pts.as<uint32_t>(), n_harr, false}}, (uint32_t)(hhi - hlo), &ch, &credit);
-  hxbuf.ensure(std::max<size_t>(nh, 1) * 32);
+  if (!quot) hxbuf.ensure(std::max<size_t>(nh, 1) * 32);
   auto base_w = [&](KeyArray& a) { return MsmBase{&a.table, wbase, a.pts.as<uint32_t>(), pk->n_w}; };
   st.pk = pk;
   st.total = std::make_unique<PhaseTimer>(c.main_stream);
@@ -336,7 +340,8 @@ int proof_enqueue(Ctx& c, ProverKey* pk, DevScalars w, DevScalars px, const Shar
       th.stop();
       c.timing.h2d_ms += th.ms();
     }
-    st.tpoly = std::make_shared<PhaseTimer>(c.stream);
+    const bool no_poly = quot && !px.produce;                                    // nothing between px and plan(h): no polynomial phase to time
+    if (!no_poly) st.tpoly = std::make_shared<PhaseTimer>(c.stream);
     bool have_hx = false;
     if (px.hv_slice) have_hx = true;                                           // H's values came from another rank
     else if (eval) {                                                           // H's values, for the evaluation-basis table
@@ -348,11 +353,13 @@ int proof_enqueue(Ctx& c, ProverKey* pk, DevScalars w, DevScalars px, const Shar
     if (!have_hx && px.produce_hx && nh) have_hx = px.produce_hx(c, hxbuf.as<uint32_t>());  // H from the constraint values (satisfying witness)
     if (!have_hx) {
       if (px.produce) px.produce(c);                                           // r1csqap.go:161-210 on the sparse system
-      if (nh) poly_quotient_dev(c, pk->z, px.p, px.n, hxbuf.as<uint32_t>());    // groth16.go:266, snark.go:280
+      if (nh && !quot) poly_quotient_dev(c, pk->z, px.p, px.n, hxbuf.as<uint32_t>());    // groth16.go:266, snark.go:280
     }
-    st.tpoly->stop();
+    if (st.tpoly) st.tpoly->stop();
     st.tplanh = std::make_shared<PhaseTimer>(c.stream);
-    build_plan(c, 1 + 2 * parity, px.hv_slice ? px.hv_slice : hxbuf.as<uint32_t>() + hlo * 8, (uint32_t)(hhi - hlo), plan_h, {{1, false}}, ch, !tab_h);
+    // the scalars of the h-sum: H's values of this slice, px's coefficients from deg Z up (any 256-bit words: k_digits canonicalises), or hx
+    const uint32_t* hscal = px.hv_slice ? px.hv_slice : quot ? px.p + (pk->nz - 1 + hlo) * 8 : hxbuf.as<uint32_t>() + hlo * 8;
+    build_plan(c, 1 + 2 * parity, hscal, (uint32_t)(hhi - hlo), plan_h, {{1, false}}, ch, !tab_h);
     st.tplanh->stop();
     GS_HIP(hipEventRecord(st.planh, c.stream));
   };
@@ -408,7 +415,7 @@ int proof_collect(Ctx& c, ProofInFlight& st, ProofSums& sums) {
   if (host_trace()) fprintf(stderr, "[gs host] collect: wait %.3f ms, fold %.3f ms\n", t1 - t0, host_now_ms() - t1);
   msm_book_timing(c, st.pend_g1w); msm_book_timing(c, st.pend_g2w); msm_book_timing(c, st.pend_h);
   if (st.split_b) { msm_book_timing(c, st.pend_g1b); c.timing.plan_ms += st.tplanb->ms(); }
-  c.timing.poly_ms += st.tpoly->ms();
+  if (st.tpoly) c.timing.poly_ms += st.tpoly->ms();
   c.timing.plan_ms += st.tplanw->ms() + st.tplanh->ms();
   c.timing.total_ms += st.total->ms();
   if (st.in.th2d) c.timing.h2d_ms += st.in.th2d->ms();

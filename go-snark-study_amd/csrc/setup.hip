@@ -77,6 +77,23 @@ bool eval_basis_scalars(Ctx& c, size_t n, const uint64_t tau[4], const uint64_t 
   return true;
 }
 
+// Quotient-basis array of a key whose h array is  h[i] = pw[i] G  (prove.h, h_quot):  h_quot[m] = u_m G  with
+//   u_m = sum_{d <= m} g_d pw[m - d],   g = 1 / rev(Z):
+// the first len_h coefficients of the product of the two series, by the polynomial engine's NTT product (for pw[i] = kappa tau^i that
+// is the recurrence u_m = tau u_{m-1} + kappa g_m; the product needs no 1 / tau and no scan of its own), then one more fixed-base batch.
+void build_quot_basis(Ctx& c, ProverKey& pk, const uint32_t* pw_std) {
+  const size_t n = pk.len_h;
+  if (!n) return;
+  divisor_ensure(c, pk.z, n);
+  DevBuf u((2 * n - 1) * 32);
+  poly_mul_dev(c, pk.z.inv_rev_mont.as<uint32_t>(), n, Form::Mont, pw_std, n, Form::Std, u.as<uint32_t>());
+  poly_canon_dev(c, u.as<uint32_t>(), n, 0);
+  pk.h_quot.pts.alloc(n * 64);
+  fixed_base_g1(c, u.as<uint32_t>(), (uint32_t)n, pk.h_quot.pts.as<uint32_t>());
+  GS_HIP(hipStreamSynchronize(c.stream));
+  pk.n_q = n;
+}
+
 template <class T>
 Affine<T> download_point(Ctx& c, const uint32_t* packed_dev) {
   uint32_t w[PointIO<T>::kAffineWords];
@@ -180,6 +197,7 @@ int gs_groth16_setup(size_t n, size_t m, size_t npublic,
     DevBuf zc((m - 1) * 32);
     zpoly_dev(c, m - 2, zc.as<uint32_t>());
     divisor_init(c, pk->z, zc.as<uint32_t>(), m - 1);
+    build_quot_basis(c, *pk, pw.as<uint32_t>());
     // --- verification key (alpha | beta2 | gamma2 | delta2 | IC[0..NPublic]) as affine Jacobian triples --------
     if (vk_out) {
       const size_t nic = npublic + 1;
@@ -257,6 +275,7 @@ int gs_pinocchio_setup(size_t n, size_t m, size_t npublic,
     DevBuf zc((m - 1) * 32);
     zpoly_dev(c, m - 2, zc.as<uint32_t>());
     divisor_init(c, pk->z, zc.as<uint32_t>(), m - 1);
+    build_quot_basis(c, *pk, pw.as<uint32_t>());
     if (vk_out) {
       // Vka (G2) | Vkb (G1) | Vkc (G2) | G1Kbg | G2Kbg | G2Kg | Vkz | IC[0..NPublic]       :162-175, 186-188, 236
       const size_t nic = npublic + 1;
@@ -323,7 +342,8 @@ int gs_groth16_pk_export(gs_handle hpk, int which, uint64_t* jacobian, size_t co
       case 3: src = &pk->bacdelta(); break;
       case 4: src = &pk->ptd(); have = pk->n_h; break;
       case 7: src = &pk->ptd_eval(); have = pk->n_e; break;       // evaluation-basis copy of PowersTauDelta (0 points when the key has none)
-      default: return fail(GS_ERR_ARG, "gs_groth16_pk_export: which must be 0..7");
+      case 10: src = &pk->ptd_quot(); have = pk->n_q; break;      // quotient-basis array (0 points when the key has none)
+      default: return fail(GS_ERR_ARG, "gs_groth16_pk_export: which must be 0..7 or 10");
     }
     if (count != have || (count && !jacobian)) return fail(GS_ERR_ARG, "gs_groth16_pk_export: array has %zu points, asked for %zu", have, count);
     if (!count) return GS_OK;
@@ -342,16 +362,17 @@ int gs_pinocchio_pk_export(gs_handle hpk, int which, uint64_t* jacobian, size_t 
     PinocchioPkObj* pk = c.get<PinocchioPkObj>(hpk, Kind::PinocchioPk);
     if (!pk) return fail(GS_ERR_ARG, "gs_pinocchio_pk_export: bad proving-key handle");
     if (pk->shard_count != 1) return fail(GS_ERR_ARG, "gs_pinocchio_pk_export: the key is a slice (export the full key)");
-    const DevBuf* arr[10] = {&pk->a(), &pk->ap(), &pk->b2(), &pk->bp(), &pk->c(), &pk->cp(), &pk->kp(), &pk->g1t(), nullptr, &pk->g1t_eval()};
+    const DevBuf* arr[11] = {&pk->a(), &pk->ap(), &pk->b2(), &pk->bp(), &pk->c(), &pk->cp(), &pk->kp(), &pk->g1t(), nullptr, &pk->g1t_eval(), &pk->g1t_quot()};
     if (which == 8) {           // pk.Z: nz coefficients, 4 x u64 each
       if (count != pk->nz || !jacobian) return fail(GS_ERR_ARG, "gs_pinocchio_pk_export: Z has %zu coefficients, asked for %zu", pk->nz, count);
       GS_HIP(hipMemcpyAsync(jacobian, pk->z.b_std.p, count * 32, hipMemcpyDeviceToHost, c.stream));
       GS_HIP(hipStreamSynchronize(c.stream));
       return GS_OK;
     }
-    if (which < 0 || which > 9) return fail(GS_ERR_ARG, "gs_pinocchio_pk_export: which must be 0..9");
+    if (which < 0 || which > 10) return fail(GS_ERR_ARG, "gs_pinocchio_pk_export: which must be 0..10");
     const bool g2 = which == 2;
-    const size_t have = which == 7 ? pk->len_h : which == 9 ? pk->n_eval : pk->nvars;     // 9: evaluation-basis copy of G1T (0 points when there is none)
+    // 9: evaluation-basis copy of G1T, 10: quotient-basis array (0 points when there is none)
+    const size_t have = which == 7 ? pk->len_h : which == 9 ? pk->n_eval : which == 10 ? pk->n_q : pk->nvars;
     if (count != have || (count && !jacobian)) return fail(GS_ERR_ARG, "gs_pinocchio_pk_export: array has %zu points, asked for %zu", have, count);
     if (!count) return GS_OK;
     const size_t words = g2 ? 48 : 24;
@@ -392,6 +413,44 @@ int gs_pinocchio_pk_set_eval(gs_handle hpk, gs_handle hbases) {
   return guarded([&](Ctx& c) -> int {
     return pk_set_eval_impl(c, "gs_pinocchio_pk_set_eval", Kind::PinocchioPk, " (attach the array to the full key, then cut it)", hpk, hbases);
   }, true, false, hpk);
+}
+// Attach a quotient-basis array to a key that was not built here (a key file that carries one: utils.py's binary container, sections
+// "PowersTauDeltaQuot" / "G1TQuot"): `bases` holds len_h G1 points  Q[m] = sum_{d <= m} g_d h[m - d],  g = 1 / rev(Z)  (prove.h).  The
+// px routes of the key then sum h over px's top coefficients.  bases = 0 detaches the array: the key divides px by Z again.  Not
+// checked against h (that is the len_h MSMs the array saves); a wrong array gives proofs that do not verify.
+static int pk_set_quot_impl(Ctx& c, const char* fn, Kind kind, gs_handle hpk, gs_handle hbases) {
+  ProverKey* pk = c.get<ProverKey>(hpk, kind);
+  Bases* b = hbases ? c.get<Bases>(hbases, Kind::G1Bases) : nullptr;
+  if (!pk || (hbases && !b)) return fail(GS_ERR_ARG, "%s: bad handle", fn);
+  if (pk->shard_count != 1) return fail(GS_ERR_ARG, "%s: the key is a slice (key slices carry no quotient-basis array)", fn);
+  if (b && (b->n == 0 || b->n != pk->len_h)) return fail(GS_ERR_SHAPE, "%s: %zu points, but the key's h array has %zu", fn, b->n, pk->len_h);
+  c.drain();                                  // an outstanding ticket may read the array that goes
+  table_settle(c, pk->h_quot.table, false);
+  pk->h_quot.table.drop();
+  pk->n_q = 0;
+  if (!b) { pk->h_quot.pts.release(); return GS_OK; }
+  pk->h_quot.pts.alloc(b->n * 64);
+  GS_HIP(hipMemcpyAsync(pk->h_quot.pts.p, b->buf.p, b->n * 64, hipMemcpyDeviceToDevice, c.stream));
+  GS_HIP(hipStreamSynchronize(c.stream));
+  pk->n_q = b->n;
+  return GS_OK;
+}
+int gs_groth16_pk_set_quot(gs_handle hpk, gs_handle hbases) {
+  return guarded([&](Ctx& c) -> int { return pk_set_quot_impl(c, "gs_groth16_pk_set_quot", Kind::GrothPk, hpk, hbases); }, true, false, hpk);
+}
+int gs_pinocchio_pk_set_quot(gs_handle hpk, gs_handle hbases) {
+  return guarded([&](Ctx& c) -> int { return pk_set_quot_impl(c, "gs_pinocchio_pk_set_quot", Kind::PinocchioPk, hpk, hbases); }, true, false, hpk);
+}
+// number of quotient-basis points a resident Groth16 or Pinocchio key holds (0 = none)
+int gs_pk_quot_count(gs_handle hpk, size_t* count) {
+  return guarded([&](Ctx& c) -> int {
+    if (!count) return fail(GS_ERR_ARG, "gs_pk_quot_count: null output");
+    auto it = c.objs.find(hpk);
+    ProverKey* pk = it == c.objs.end() ? nullptr : as_prover_key(it->second.get());
+    if (!pk) return fail(GS_ERR_ARG, "gs_pk_quot_count: not a proving-key handle");
+    *count = pk->n_q;
+    return GS_OK;
+  }, true, true, hpk);
 }
 // number of evaluation-basis points a resident Groth16 or Pinocchio key holds (0 = none; a slice: its own share)
 int gs_pk_eval_count(gs_handle hpk, size_t* count) {

@@ -102,13 +102,16 @@ def GenerateTrustedSetupSparse(n, nvars, npublic, a_csr, b_csr, c_csr, toxic):
 
 # "PowersTauDeltaEval": the evaluation-basis copy of PowersTauDelta (include/gosnark_hip.h, gs_groth16_pk_set_eval) -- not a field
 # of the reference's Pk; keys built by gs_groth16_setup carry it, the binary key container stores it as an extra section.
-PK_ARRAYS = {"G1_At": 0, "G1_BACGamma": 1, "G2_BACGamma": 2, "BACDelta": 3, "PowersTauDelta": 4, "PowersTauDeltaEval": 7}
+# "PowersTauDeltaQuot": the quotient-basis array Q_m = sum_{d <= m} g_d PowersTauDelta[m - d], g = 1 / rev(Z) (gs_groth16_pk_set_quot):
+# with it the h-sum of a proof runs over the top coefficients of px and nothing is divided by Z.
+PK_ARRAYS = {"G1_At": 0, "G1_BACGamma": 1, "G2_BACGamma": 2, "BACDelta": 3, "PowersTauDelta": 4, "PowersTauDeltaEval": 7, "PowersTauDeltaQuot": 10}
 
 
 def ExportPkArray(dev_pk, name):
     """One array of a resident key as affine Jacobian int tuples (testing / serialisation)."""
     which = PK_ARRAYS[name]
-    count = capi.pk_eval_count(dev_pk.handle) if which == 7 else dev_pk.nvars if which != 4 else dev_pk.nvars - 1
+    count = (capi.pk_eval_count(dev_pk.handle) if which == 7 else capi.pk_quot_count(dev_pk.handle) if which == 10 else
+             dev_pk.nvars if which != 4 else dev_pk.nvars - 1)
     if count == 0:
         return []
     words = 24 if which == 2 else 12
@@ -409,6 +412,19 @@ def SetEvalBasis(dev_pk, points):
     arr = capi.ints_to_u64([c for p in points for c in p]).reshape(-1, 12)
     b = capi.g1_upload(arr)
     capi.check(capi.load_library().gs_groth16_pk_set_eval(capi.Handle(dev_pk.handle.h), capi.Handle(b.h)))
+
+
+def SetQuotBasis(dev_pk, points):
+    """Attach a quotient-basis array (len(PowersTauDelta) Jacobian int triples, PK_ARRAYS above) to a resident key:
+    gs_groth16_pk_set_quot.  points = None detaches it: the key divides px by Z again."""
+    b = None if points is None else capi.g1_upload(capi.ints_to_u64([c for p in points for c in p]).reshape(-1, 12))
+    capi.check(capi.load_library().gs_groth16_pk_set_quot(capi.Handle(dev_pk.handle.h), capi.Handle(b.h if b is not None else 0)))
+
+
+def DeriveQuotBasis(dev_pk):
+    """Compute the quotient-basis array of a resident key from its PowersTauDelta and Z (gs_groth16_pk_derive_quot: a transform in
+    the group, seconds for a 2^20 key) and attach it."""
+    capi.check(capi.load_library().gs_groth16_pk_derive_quot(capi.Handle(dev_pk.handle.h)))
 
 
 def prove_partials(dev_pk, w_handle, px_handle, shard_index, shard_count):

@@ -212,6 +212,18 @@ def SetEvalBasis(dev_pk, points):
     capi.check(capi.load_library().gs_pinocchio_pk_set_eval(capi.Handle(dev_pk.h), capi.Handle(b.h)))
 
 
+def SetQuotBasis(dev_pk, points):
+    """Attach a quotient-basis array (len(G1T) Jacobian int triples, PK_ARRAYS) to a resident key: gs_pinocchio_pk_set_quot.
+    points = None detaches it: the key divides px by Z again."""
+    b = None if points is None else capi.g1_upload(capi.ints_to_u64([c for p in points for c in p]).reshape(-1, 12))
+    capi.check(capi.load_library().gs_pinocchio_pk_set_quot(capi.Handle(dev_pk.h), capi.Handle(b.h if b is not None else 0)))
+
+
+def DeriveQuotBasis(dev_pk):
+    """Compute the quotient-basis array of a resident key from its G1T and Z (gs_pinocchio_pk_derive_quot) and attach it."""
+    capi.check(capi.load_library().gs_pinocchio_pk_derive_quot(capi.Handle(dev_pk.h)))
+
+
 def prove_begin(dev_pk, w_handle, px_handle):
     """Enqueue one Pinocchio proof (gs_pinocchio_prove_begin) -> ticket.  Up to three operations may be outstanding."""
     t = ctypes.c_uint64(0)
@@ -329,7 +341,8 @@ class Vk:
             setattr(self, k, kw[k])
 
 
-PK_ARRAYS = {"A": 0, "Ap": 1, "B": 2, "Bp": 3, "C": 4, "Cp": 5, "Kp": 6, "G1T": 7, "G1TEval": 9}   # G1TEval: evaluation-basis copy of G1T
+# G1TEval: evaluation-basis copy of G1T; G1TQuot: quotient-basis array Q_m = sum_{d <= m} g_d G1T[m - d], g = 1 / rev(Z)
+PK_ARRAYS = {"A": 0, "Ap": 1, "B": 2, "Bp": 3, "C": 4, "Cp": 5, "Kp": 6, "G1T": 7, "G1TEval": 9, "G1TQuot": 10}
 
 
 class DevicePk:
@@ -365,7 +378,8 @@ def GenerateTrustedSetupSparse(n, nvars, npublic, a_csr, b_csr, c_csr, toxic):
 
 def ExportPkArray(dev_pk, name):
     which = PK_ARRAYS[name]
-    count = capi.pk_eval_count(dev_pk.handle) if which == 9 else dev_pk.nvars - 1 if which == 7 else dev_pk.nvars
+    count = (capi.pk_eval_count(dev_pk.handle) if which == 9 else capi.pk_quot_count(dev_pk.handle) if which == 10 else
+             dev_pk.nvars - 1 if which == 7 else dev_pk.nvars)
     if count == 0:
         return []
     words = 24 if which == 2 else 12

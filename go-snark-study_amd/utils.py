@@ -315,6 +315,11 @@ def GrothSetupToBinary(path, circuit, pk, vk):
             e = np.zeros((ne, 12), dtype=np.uint64)
             capi.check(lib.gs_groth16_pk_export(capi.Handle(pk.handle.h), 7, capi.ptr64(e), ne))
             sec["PowersTauDeltaEval"] = e
+        nq = capi.pk_quot_count(pk.handle)
+        if nq:           # optional section: the quotient-basis array (h-sum over px's top coefficients, no division by Z)
+            q = np.zeros((nq, 12), dtype=np.uint64)
+            capi.check(lib.gs_groth16_pk_export(capi.Handle(pk.handle.h), 10, capi.ptr64(q), nq))
+            sec["PowersTauDeltaQuot"] = q
     else:
         sec["G1.At"] = capi.g1_points_to_u64(pk.G1_At)
         sec["G1.BACGamma"] = capi.g1_points_to_u64(pk.G1_BACGamma)
@@ -387,6 +392,10 @@ def UploadGrothPkBinary(path, shard=None):
             e = capi.g1_upload(np.ascontiguousarray(sec["PowersTauDeltaEval"], dtype=np.uint64))
             capi.check(capi.load_library().gs_groth16_pk_set_eval(capi.Handle(dev.handle.h), capi.Handle(e.h)))
             e.free()
+        if "PowersTauDeltaQuot" in sec:          # the px routes then sum h over px's top coefficients (gs_groth16_pk_set_quot)
+            q = capi.g1_upload(np.ascontiguousarray(sec["PowersTauDeltaQuot"], dtype=np.uint64))
+            capi.check(capi.load_library().gs_groth16_pk_set_quot(capi.Handle(dev.handle.h), capi.Handle(q.h)))
+            q.free()
     else:
         dev = groth16.device_pk_shard_from_handles(at, b1, b2, cd, pt, abd[0], abd[1], abd[2], bd[0], bd[1], z, nvars, npublic, nptd,
                                                    shard[0], shard[1])
@@ -416,6 +425,11 @@ def SetupToBinary(path, circuit, pk, vk=None):
             e = np.zeros((ne, 12), dtype=np.uint64)
             capi.check(lib.gs_pinocchio_pk_export(capi.Handle(pk.h), 9, capi.ptr64(e), ne))
             sec["G1TEval"] = e
+        nq = capi.pk_quot_count(pk.handle)
+        if nq:           # optional section: the quotient-basis array of G1T
+            q = np.zeros((nq, 12), dtype=np.uint64)
+            capi.check(lib.gs_pinocchio_pk_export(capi.Handle(pk.h), 10, capi.ptr64(q), nq))
+            sec["G1TQuot"] = q
     else:
         for name, _, words in _PIN_ARRAYS:
             pts = getattr(pk, name)
@@ -460,4 +474,8 @@ def UploadPkBinary(path):
         e = capi.g1_upload(np.ascontiguousarray(sec["G1TEval"], dtype=np.uint64))
         capi.check(capi.load_library().gs_pinocchio_pk_set_eval(capi.Handle(dev.h), capi.Handle(e.h)))
         e.free()
+    if "G1TQuot" in sec:
+        q = capi.g1_upload(np.ascontiguousarray(sec["G1TQuot"], dtype=np.uint64))
+        capi.check(capi.load_library().gs_pinocchio_pk_set_quot(capi.Handle(dev.h), capi.Handle(q.h)))
+        q.free()
     return snark.Circuit(nvars, npublic), dev

@@ -353,6 +353,52 @@ func (k *PinocchioKey) SetEvalBasis(points [][3]*big.Int) error {
 	return call(func() C.int { return C.gs_pinocchio_pk_set_eval(C.gs_handle(k.h), C.gs_handle(h)) })
 }
 
+// SetQuotBasis attaches a quotient-basis array (len(PowersTauDelta) points Q[m] = sum_{d <= m} g_d PowersTauDelta[m-d], g = 1/rev(Z),
+// read from a key file) to a resident key: the h-sum of a proof then runs over the top coefficients of px and nothing is divided by
+// Z (gs_groth16_pk_set_quot).  nil detaches the array.
+func (k *Groth16Key) SetQuotBasis(points [][3]*big.Int) error {
+	if points == nil {
+		return call(func() C.int { return C.gs_groth16_pk_set_quot(C.gs_handle(k.h), C.gs_handle(0)) })
+	}
+	h, err := UploadG1(DeviceOf(k.h), points)
+	if err != nil {
+		return err
+	}
+	defer Free(h)
+	return call(func() C.int { return C.gs_groth16_pk_set_quot(C.gs_handle(k.h), C.gs_handle(h)) })
+}
+
+// QuotBasisCount is the number of quotient-basis points the key holds (0 = none: the key divides px by Z).
+func (k *Groth16Key) QuotBasisCount() (int, error) {
+	var n C.size_t
+	err := call(func() C.int { return C.gs_pk_quot_count(C.gs_handle(k.h), &n) })
+	return int(n), err
+}
+
+// SetQuotBasis for a Pinocchio key: Q[m] = sum_{d <= m} g_d G1T[m-d] (gs_pinocchio_pk_set_quot).  nil detaches the array.
+func (k *PinocchioKey) SetQuotBasis(points [][3]*big.Int) error {
+	if points == nil {
+		return call(func() C.int { return C.gs_pinocchio_pk_set_quot(C.gs_handle(k.h), C.gs_handle(0)) })
+	}
+	h, err := UploadG1(DeviceOf(k.h), points)
+	if err != nil {
+		return err
+	}
+	defer Free(h)
+	return call(func() C.int { return C.gs_pinocchio_pk_set_quot(C.gs_handle(k.h), C.gs_handle(h)) })
+}
+
+// DeriveQuotBasis computes the quotient-basis array of a key that was built elsewhere from its PowersTauDelta and Z -- a
+// number-theoretic transform in the group, seconds for a 2^20 key, once per key -- and attaches it (gs_groth16_pk_derive_quot).
+func (k *Groth16Key) DeriveQuotBasis() error {
+	return call(func() C.int { return C.gs_groth16_pk_derive_quot(C.gs_handle(k.h)) })
+}
+
+// DeriveQuotBasis for a Pinocchio key, from G1T and Z (gs_pinocchio_pk_derive_quot).
+func (k *PinocchioKey) DeriveQuotBasis() error {
+	return call(func() C.int { return C.gs_pinocchio_pk_derive_quot(C.gs_handle(k.h)) })
+}
+
 // ProveWitnessBegin enqueues one witness -> proof and returns its ticket (collect with ProveEnd; abandon with CancelTicket).
 func (k *Groth16Key) ProveWitnessBegin(q *R1CS, w Handle, r, s, order *big.Int) (Groth16Ticket, error) {
 	rs, err := Scalars([]*big.Int{r, s}, order)

@@ -230,6 +230,23 @@ int gs_groth16_prove_witness(gs_handle pk, gs_handle r1cs, gs_handle w, const ui
 int gs_groth16_pk_set_eval(gs_handle pk, gs_handle bases);
 int gs_pk_eval_count(gs_handle pk, size_t* count);     /* Groth16 or Pinocchio key: evaluation-basis points it holds (0 = none) */
 int gs_groth16_prove_witness_begin(gs_handle pk, gs_handle r1cs, gs_handle w, const uint64_t r[4], const uint64_t s[4], uint64_t* ticket);
+/* Keys with a QUOTIENT-BASIS array divide nothing by Z.  h = floor(px / Z) is linear in px and only ever enters the proof through
+ * sum_j h_j PowersTauDelta[j]; with D = deg Z, g = 1 / rev(Z) as a power series and Q[m] = sum_{d <= m} g_d PowersTauDelta[m - d]
+ * (m < len(PowersTauDelta)) that element is sum_{m < len(hx)} px[D + m] Q[m] for every px, whatever the remainder: ONE MSM over the top
+ * coefficients of px as they are -- no transforms, no hx.  Every entry point that is handed px (or builds it: gs_groth16_prove_r1cs)
+ * takes this route when the key holds the array; the witness routes above and px shorter than Z are as before.  gs_groth16_setup builds
+ * Q (64 B per point; the key then keeps no window table of PowersTauDelta for these routes, so its table bytes do not grow);
+ * gs_groth16_pk_set_quot attaches one to a key loaded from a file (`bases`: len(PowersTauDelta) G1 points; not checked -- a wrong array
+ * yields proofs that do not verify) and bases = 0 detaches it; gs_groth16_pk_export which = 10 reads it back.  Key slices
+ * (gs_groth16_pk_create_shard / gs_groth16_pk_shard) carry no such array and divide.  Bit-identical proofs either way; the environment
+ * variable GS_NO_QUOT_BASIS (any value, read once) makes every key divide. */
+int gs_groth16_pk_set_quot(gs_handle pk, gs_handle bases);
+int gs_pk_quot_count(gs_handle pk, size_t* count);     /* Groth16 or Pinocchio key: quotient-basis points it holds (0 = none) */
+/* Compute the quotient-basis array of a key that was built elsewhere (only T = PowersTauDelta is known): Q is the convolution of
+ * the scalar series g with the point sequence T, by a number-theoretic transform carried out in the group (csrc/ecntt.hip):
+ * N / 2 * log2 N + N scalar multiplications for N = 2^ceil(log2(2 len(T) - 1)) -- seconds for a 2^20 key, once per key; explicit
+ * only, nothing derives the array on its own.  Blocking; replaces an attached array. */
+int gs_groth16_pk_derive_quot(gs_handle pk);
 
 /* Pipelined proving (inputs resident): gs_groth16_prove_begin enqueues the whole device side of one proof and returns a
  * ticket without waiting; gs_groth16_prove_end waits for THAT proof only, then runs the host tail and writes the proof
@@ -309,13 +326,15 @@ int gs_pinocchio_setup(size_t n, size_t m, size_t npublic,
                        const uint32_t* c_rowptr, const uint32_t* c_col, const uint64_t* c_val,
                        const uint64_t toxic[32], gs_handle* pk_out, uint64_t* vk_out);
 /* Read one array of a resident Pinocchio key back (which = 0 A, 1 Ap, 2 B (G2, 24 words per point), 3 Bp, 4 C, 5 Cp,
- * 6 Kp, 7 G1T; 8 = pk.Z, count coefficients of 4 x u64; 9 = the evaluation-basis copy of G1T, n points or none).  Note A and Ap hold infinity for i <= NPublic (what the
+ * 6 Kp, 7 G1T; 8 = pk.Z, count coefficients of 4 x u64; 9 = the evaluation-basis copy of G1T, n points or none; 10 = the
+ * quotient-basis array, len(G1T) points or none).  Note A and Ap hold infinity for i <= NPublic (what the
  * prover sums, snark.go:265). */
 int gs_pinocchio_pk_export(gs_handle pk, int which, uint64_t* jacobian, size_t count);
 /* Read one array of a resident Groth16 key back as affine Jacobian triples: which = 0 G1.At, 1 G1.BACGamma,
  * 2 G2.BACGamma (24 words per point), 3 BACDelta, 4 PowersTauDelta; 5 = the single elements (count = 5: G1 Alpha, Beta,
  * Delta as 3 x 12 words, then G2 Beta, Delta as 2 x 24 words); 6 = pk.Z (count coefficients of 4 x u64); 7 = the
- * evaluation-basis copy of PowersTauDelta (n points, or 0 when the key has none).  count must equal the array length.  With 0..6 a resident key can be written out in full (utils.GrothSetupToString). */
+ * evaluation-basis copy of PowersTauDelta (n points, or 0 when the key has none); 10 = the quotient-basis array (len(PowersTauDelta)
+ * points, or 0).  count must equal the array length.  With 0..6 a resident key can be written out in full (utils.GrothSetupToString). */
 int gs_groth16_pk_export(gs_handle pk, int which, uint64_t* jacobian, size_t count);
 
 /* ---- Pinocchio prover (snark.go) ------------------------------------------------------------ */
@@ -336,6 +355,10 @@ int gs_pinocchio_prove_witness(gs_handle pk, gs_handle r1cs, gs_handle w, uint64
  * sum_i h_i G1T[i], snark.go:239-247, 284-286) when the key has one: gs_pinocchio_setup builds it, gs_pinocchio_pk_set_eval attaches
  * one, gs_pinocchio_pk_export which = 9 reads it back.  gs_pinocchio_prove_witness_begin: pipelined, collect with gs_pinocchio_prove_end. */
 int gs_pinocchio_pk_set_eval(gs_handle pk, gs_handle bases);
+/* ... and a quotient-basis array of G1T, Q[m] = sum_{d <= m} g_d G1T[m - d] (see gs_groth16_pk_set_quot): gs_pinocchio_setup builds it,
+ * this attaches (bases = 0: detaches) one, gs_pinocchio_pk_export which = 10 reads it back. */
+int gs_pinocchio_pk_set_quot(gs_handle pk, gs_handle bases);
+int gs_pinocchio_pk_derive_quot(gs_handle pk);          /* as gs_groth16_pk_derive_quot, from G1T */
 int gs_pinocchio_prove_witness_begin(gs_handle pk, gs_handle r1cs, gs_handle w, uint64_t* ticket);
 /* Pipelined Pinocchio proving: same tickets as gs_groth16_prove_begin / _end (the three in-flight slots are shared between
  * Groth16 proofs, Pinocchio proofs and MSMs). */
