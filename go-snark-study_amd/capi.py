@@ -91,6 +91,8 @@ _SIGS = {
     "gs_pk_quot_count": [Handle, ctypes.POINTER(ctypes.c_size_t)],
     "gs_groth16_pk_derive_quot": [Handle],
     "gs_pinocchio_pk_derive_quot": [Handle],
+    "gs_groth16_pk_derive_eval": [Handle, ctypes.c_size_t],
+    "gs_pinocchio_pk_derive_eval": [Handle, ctypes.c_size_t],
     "gs_pinocchio_prove_witness_begin": [Handle, Handle, Handle, u64p],
     "gs_groth16_prove_begin": [Handle, Handle, Handle, u64p, u64p, u64p],
     "gs_groth16_prove_end": [ctypes.c_uint64, u64p, intp],

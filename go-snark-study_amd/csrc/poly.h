@@ -1,6 +1,8 @@
 // Internal C++ interface of the Fr polynomial engine (implemented in poly.hip).
 // All pointers are DEVICE pointers to packed elements (8 x u32 words each, value < 2^256).
 #pragma once
+#include <vector>
+
 #include "fp29.h"
 #include "runtime.h"
 
@@ -45,6 +47,11 @@ void poly_quotient_dev(Ctx& c, Divisor& d, const uint32_t* a_std, size_t na, uin
 
 // Z(x) = prod_{i=1}^{deg} (x - i), deg + 1 canonical standard-form coefficients (subproduct tree of NTT products)
 void zpoly_dev(Ctx& c, size_t deg, uint32_t* out_std);
+
+// Scalar side of the evaluation-basis derivation (ecntt.hip): the reversed node tree over the nodes n+1 .. 2n whose padding leaves are
+// the polynomial 1.  spec_std[l] (l < ceil_log2(n)): per node of level l the transform of rev(M_node) at the parent's size 2^(l+1),
+// divided by that size, canonical standard form; weights_std[j-1] = 1 / M'(n + j).  Caller-owned buffers; synchronises the stream.
+void shifted_tree_spectra_dev(Ctx& c, size_t n, std::vector<DevBuf>& spec_std, DevBuf& weights_std);
 
 // Lagrange interpolation on the nodes 1..n of nvec value vectors (nvec x n, standard form) -> nvec x n coefficients
 // (standard form, values < 2r); O(n log^2 n) on a cached subproduct tree.

@@ -389,6 +389,44 @@ static NodeTree& ensure_tree(Ctx& c, size_t n, bool need_weights) {
   return *t;
 }
 
+// The scalar side of the evaluation-basis derivation (ecntt.hip): the node tree over x_j = n + j, j = 1..n, with 2^L leaf slots whose
+// padding leaves are the polynomial 1 (NOT the factor x of ensure_tree: the push-down starts from n power sums, not 2^L), kept as
+// REVERSED polynomials rev(M) = prod (1 - x_j x) -- a product of reversed polynomials is the reversed product whatever the degrees, and
+// the reversed ones are what the push-down multiplies by.  spec_std[l], l < L: for every node of level l the transform of its rev(M)
+// at the PARENT's size 2^(l+1) (bit-reversed within the block, as ntt_forward leaves it), times 1 / 2^(l+1), canonical standard form
+// -- 2 * 2^L elements per level.  weights_std[j-1] = 1 / M'(x_j) (translation invariant: the weights of the nodes 1..n).  Buffers of
+// the caller: nothing here enters PolyState's caches but the factorial tables.  Synchronises the stream.
+void shifted_tree_spectra_dev(Ctx& c, size_t n, std::vector<DevBuf>& spec_std, DevBuf& weights_std) {
+  const int L = ceil_log2(std::max<size_t>(n, 1));
+  const size_t total = (size_t)1 << L;
+  const uint64_t one[4] = {1, 0, 0, 0};
+  ensure_factorials(c, std::max<size_t>(n, 1));
+  DevBuf wm(n * 32);
+  hipLaunchKernelGGL(k_bary_weights, grid1(n), dim3(256), 0, c.stream, poly_state(c).invfact.as<uint32_t>(), (uint32_t)n, wm.as<uint32_t>());
+  weights_std.alloc(n * 32);
+  scale_mont_by_std_dev(c, wm.as<uint32_t>(), one, n, weights_std.as<uint32_t>());
+  DevBuf cur(total * 32), nxt(total * 32), wide(2 * total * 32);
+  hipLaunchKernelGGL(k_rt_leaves, grid1(total), dim3(256), 0, c.stream, cur.as<uint32_t>(), (uint32_t)n, (uint32_t)total);
+  spec_std.clear();
+  spec_std.resize(L);
+  for (int j = 0; j < L; ++j) {
+    const uint32_t d = 1u << j;
+    hipLaunchKernelGGL(k_rt_expand, grid1(2 * total), dim3(256), 0, c.stream, cur.as<uint32_t>(), wide.as<uint32_t>(), d, (uint32_t)(2 * total));
+    ntt_forward(c, wide.as<uint32_t>(), L + 1, j + 1);
+    const uint64_t nn[4] = {2ull * d, 0, 0, 0};
+    uint64_t inv_n[4];
+    fr_inv_words(nn, inv_n);
+    spec_std[j].alloc(2 * total * 32);
+    scale_mont_by_std_dev(c, wide.as<uint32_t>(), inv_n, 2 * total, spec_std[j].as<uint32_t>());
+    if (j + 1 == L) break;                                     // the root's polynomial multiplies nothing
+    hipLaunchKernelGGL(k_pw_mul_pairs, grid1(total), dim3(256), 0, c.stream, wide.as<uint32_t>(), nxt.as<uint32_t>(), 2 * d, (uint32_t)total);
+    ntt_inverse_unscaled(c, nxt.as<uint32_t>(), L, j + 1);
+    hipLaunchKernelGGL(k_rt_combine, grid1(total), dim3(256), 0, c.stream, nxt.as<uint32_t>(), inv_n_const(j + 1, 0), cur.as<uint32_t>(), 2 * d, (uint32_t)total);
+  }
+  GS_HIP(hipGetLastError());
+  GS_HIP(hipStreamSynchronize(c.stream));
+}
+
 // Z(x) = prod_{i=1}^{deg} (x - i): deg + 1 coefficients, canonical standard form.
 void zpoly_dev(Ctx& c, size_t deg, uint32_t* out_std) {
   const uint32_t one[8] = {1, 0, 0, 0, 0, 0, 0, 0};

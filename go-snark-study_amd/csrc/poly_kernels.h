@@ -415,6 +415,44 @@ __global__ void __launch_bounds__(256) k_monic_combine(const uint32_t* __restric
   store_fr(out + (size_t)i * 8, v);
 }
 
+// ---- reversed node tree over the nodes n+1 .. 2n (evaluation-basis derivation, poly.hip shifted_tree_spectra_dev) ----------------
+// A node with r real leaves holds rev(M) = prod (1 - x_j x) = 1 + c_1 x + .. + c_r x^r: the constant 1 is implicit, a block of d =
+// 2^level elements holds c_1 .. c_d (zeros above c_r; a padding leaf is the polynomial 1, all zeros).  Montgomery form.
+// leaves: out[i] = -(n + 1 + i) for i < n, 0 above
+__global__ void __launch_bounds__(256) k_rt_leaves(uint32_t* __restrict__ out, uint32_t n, uint32_t total) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  if (i >= n) { store_fr(out + (size_t)i * 8, fe_zero<ModR, 2>()); return; }
+  uint32_t w[8] = {n + 1u + i, 0, 0, 0, 0, 0, 0, 0};
+  store_fr_canon(out + (size_t)i * 8, canon(neg(to_mont(unpack32<ModR>(w)))));
+}
+// dst[blk * 2d + t] = 1, c_1 .. c_d, 0 ..     (blocks of d -> the whole polynomial in a block of 2d: d + 1 <= 2d)
+__global__ void __launch_bounds__(256) k_rt_expand(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst, uint32_t d, uint32_t total2) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total2) return;
+  const uint32_t blk = i / (2 * d), t = i - blk * 2 * d;
+  uint4* q = reinterpret_cast<uint4*>(dst + (size_t)i * 8);
+  if (t == 0) {
+    store_fr_canon(dst + (size_t)i * 8, fe_one<ModR>());
+  } else if (t <= d) {
+    const uint4* s = reinterpret_cast<const uint4*>(src + ((size_t)blk * d + t - 1) * 8);
+    q[0] = s[0]; q[1] = s[1];
+  } else {
+    q[0] = make_uint4(0, 0, 0, 0); q[1] = q[0];
+  }
+}
+// prod = the cyclic product of two children in a block of d2 (un-scaled): the parent has degree <= d2, so its top coefficient wrapped
+// onto the constant 1:  out[p * d2 + t] = c_(t+1) = prod[t + 1] * scale for t + 1 < d2,  c_d2 = prod[0] * scale - 1
+__global__ void __launch_bounds__(256) k_rt_combine(const uint32_t* __restrict__ prod, FrConst scale, uint32_t* __restrict__ out, uint32_t d2, uint32_t total) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const uint32_t t = i & (d2 - 1);
+  const bool top = t + 1 == d2;
+  Fr2 v = mul(load_fr(prod + (size_t)(top ? i - t : i + 1) * 8), from_const(scale));
+  if (top) v = reduce2(sub(v, relax<2>(fe_one<ModR>())));
+  store_fr(out + (size_t)i * 8, v);
+}
+
 // The same combination for the interpolation tree, writing the result twice: compact (the next level's P_L / P_R source) and
 // already zero-padded to blocks of 4d (the next level's NTT input) -- no separate copy and expansion passes.
 __global__ void __launch_bounds__(256) k_interp_combine(const uint32_t* __restrict__ prod, const uint32_t* __restrict__ src, FrConst scale,

@@ -427,6 +427,12 @@ def DeriveQuotBasis(dev_pk):
     capi.check(capi.load_library().gs_groth16_pk_derive_quot(capi.Handle(dev_pk.handle.h)))
 
 
+def DeriveEvalBasis(dev_pk, n):
+    """Compute the evaluation-basis array of a resident key from its PowersTauDelta alone (gs_groth16_pk_derive_eval: a transposed
+    subproduct tree in the group over the nodes n+1..2n) and attach it as SetEvalBasis would.  n = the number of constraints."""
+    capi.check(capi.load_library().gs_groth16_pk_derive_eval(capi.Handle(dev_pk.handle.h), int(n)))
+
+
 def prove_partials(dev_pk, w_handle, px_handle, shard_index, shard_count):
     """This rank's five raw MSM sums (gs_groth16_prove_partials): [At, G1.BACGamma, G2.BACGamma, BACDelta, h.PTD] as affine
     points / None, plus the g2 flags parallel.allgather_points wants."""

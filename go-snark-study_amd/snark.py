@@ -224,6 +224,12 @@ def DeriveQuotBasis(dev_pk):
     capi.check(capi.load_library().gs_pinocchio_pk_derive_quot(capi.Handle(dev_pk.h)))
 
 
+def DeriveEvalBasis(dev_pk, n):
+    """Compute the evaluation-basis array of a resident key from its G1T alone (gs_pinocchio_pk_derive_eval) and attach it as
+    SetEvalBasis would.  n = the number of constraints."""
+    capi.check(capi.load_library().gs_pinocchio_pk_derive_eval(capi.Handle(dev_pk.h), int(n)))
+
+
 def prove_begin(dev_pk, w_handle, px_handle):
     """Enqueue one Pinocchio proof (gs_pinocchio_prove_begin) -> ticket.  Up to three operations may be outstanding."""
     t = ctypes.c_uint64(0)

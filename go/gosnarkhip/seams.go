@@ -399,6 +399,18 @@ func (k *PinocchioKey) DeriveQuotBasis() error {
 	return call(func() C.int { return C.gs_pinocchio_pk_derive_quot(C.gs_handle(k.h)) })
 }
 
+// DeriveEvalBasis computes the evaluation-basis array of a key that was built elsewhere from its PowersTauDelta alone -- a transposed
+// subproduct tree over the nodes n+1..2n with the transforms carried out in the group, once per key -- and attaches it as SetEvalBasis
+// would (gs_groth16_pk_derive_eval).  n is the number of constraints: len(Z) when the circuit has n + 1 variables, len(Z) - 1 when n + 2.
+func (k *Groth16Key) DeriveEvalBasis(n int) error {
+	return call(func() C.int { return C.gs_groth16_pk_derive_eval(C.gs_handle(k.h), C.size_t(n)) })
+}
+
+// DeriveEvalBasis for a Pinocchio key, from G1T (gs_pinocchio_pk_derive_eval).
+func (k *PinocchioKey) DeriveEvalBasis(n int) error {
+	return call(func() C.int { return C.gs_pinocchio_pk_derive_eval(C.gs_handle(k.h), C.size_t(n)) })
+}
+
 // ProveWitnessBegin enqueues one witness -> proof and returns its ticket (collect with ProveEnd; abandon with CancelTicket).
 func (k *Groth16Key) ProveWitnessBegin(q *R1CS, w Handle, r, s, order *big.Int) (Groth16Ticket, error) {
 	rs, err := Scalars([]*big.Int{r, s}, order)

@@ -247,6 +247,14 @@ int gs_pk_quot_count(gs_handle pk, size_t* count);     /* Groth16 or Pinocchio k
  * N / 2 * log2 N + N scalar multiplications for N = 2^ceil(log2(2 len(T) - 1)) -- seconds for a 2^20 key, once per key; explicit
  * only, nothing derives the array on its own.  Blocking; replaces an attached array. */
 int gs_groth16_pk_derive_quot(gs_handle pk);
+/* Compute the evaluation-basis array of a key that was built elsewhere, from its PowersTauDelta alone, and attach it as
+ * gs_groth16_pk_set_eval would:  E[j-1] = sum_{i < n} coeff_i(l_j) PowersTauDelta[i], l_j the Lagrange basis over the nodes n+1..2n --
+ * the transposed Vandermonde system  sum_j E[j-1] (n+j)^i = PowersTauDelta[i], solved by pushing the point sequence down a subproduct
+ * tree with the transforms carried out in the group (csrc/ecntt.hip): about 0.75 n log2^2 n + 2 n log2 n scalar multiplications, once
+ * per key.  n_constraints cannot be read off the key: it is len(Z) when nvars = n + 1 and len(Z) - 1 when nvars = n + 2, and at most
+ * len(PowersTauDelta); anything else is GS_ERR_SHAPE.  Full keys only.  Explicit only, nothing derives the array on its own.
+ * Blocking; replaces an attached array. */
+int gs_groth16_pk_derive_eval(gs_handle pk, size_t n_constraints);
 
 /* Pipelined proving (inputs resident): gs_groth16_prove_begin enqueues the whole device side of one proof and returns a
  * ticket without waiting; gs_groth16_prove_end waits for THAT proof only, then runs the host tail and writes the proof
@@ -359,6 +367,7 @@ int gs_pinocchio_pk_set_eval(gs_handle pk, gs_handle bases);
  * this attaches (bases = 0: detaches) one, gs_pinocchio_pk_export which = 10 reads it back. */
 int gs_pinocchio_pk_set_quot(gs_handle pk, gs_handle bases);
 int gs_pinocchio_pk_derive_quot(gs_handle pk);          /* as gs_groth16_pk_derive_quot, from G1T */
+int gs_pinocchio_pk_derive_eval(gs_handle pk, size_t n_constraints);   /* as gs_groth16_pk_derive_eval, from G1T */
 int gs_pinocchio_prove_witness_begin(gs_handle pk, gs_handle r1cs, gs_handle w, uint64_t* ticket);
 /* Pipelined Pinocchio proving: same tickets as gs_groth16_prove_begin / _end (the three in-flight slots are shared between
  * Groth16 proofs, Pinocchio proofs and MSMs). */

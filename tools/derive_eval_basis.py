@@ -12,6 +12,11 @@ transposed subproduct tree in the group -- checks the rows it derives against th
     python tools/derive_eval_basis.py --log2n 10             every row (full check)
     python tools/derive_eval_basis.py --log2n 16 --rows 24   a sample of rows; the whole derivation is extrapolated from them
 
+Since then the library derives the array itself: gs_groth16_pk_derive_eval / gs_pinocchio_pk_derive_eval (csrc/ecntt.hip) push the
+point sequence down a transposed subproduct tree with the transforms carried out in the group, O(n log^2 n) scalar multiplications
+(tools/time_eval_basis_derive.py, profiles/eval_basis_derive.txt).  This tool stays as the naive cross-check and as the price of
+doing without it.
+
 The per-row figure is split into the scalar row (host-driven polynomial division here; a synthetic-division kernel in a real
 implementation) and the MSM, which is the part that cannot shrink."""
 import argparse
