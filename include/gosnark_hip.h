@@ -167,7 +167,11 @@ int gs_zpoly(size_t deg, uint64_t* out);
 /* Sparse R1CS -> P(x): the scalable replacement of R1CSToQAP + CombinePolynomials
  * (r1csqap.go:161-210).  A, B, C in CSR over n constraints x m variables (row_ptr n+1,
  * col idx, val nnz x 4); w: m scalars.  Outputs ax, bx, cx (n coeffs each, may be NULL) and
- * px = ax*bx - cx (2n - 1 coeffs). */
+ * px = ax*bx - cx (2n - 1 coeffs).
+ * What a matrix may contain (here, in gs_r1cs_upload and in both setups): a row holds any number of entries, 0 .. 2^32 - 1 in
+ * all; its column indices need not be sorted, and an index may occur more than once -- repeated (row, column) entries ADD;
+ * every value, and every witness entry, is any 256-bit integer and counts mod r (outputs are canonical).  Only an index >= m
+ * or a row_ptr that is not monotone from 0 is refused (GS_ERR_ARG).  tests/test_gpu_r1cs_shapes.py holds each of these. */
 int gs_r1cs_to_px(size_t n, size_t m,
                   const uint32_t* a_rowptr, const uint32_t* a_col, const uint64_t* a_val,
                   const uint32_t* b_rowptr, const uint32_t* b_col, const uint64_t* b_val,

@@ -17,6 +17,7 @@ import pytest
 import gosnark_amd  # noqa: F401
 from gosnark_amd import capi, groth16, snark, synth
 import golden_util as GU
+from r1cs_shapes import lagrange_at
 from oracle import c_oracle as C
 from oracle import ref_py as O
 
@@ -92,23 +93,6 @@ def test_pinocchio_setup_emits_the_same_convolution():
 
 
 # ---- proofs: with the array == after detaching it == closed form ----------------------------------------------------------------
-def lagrange_at(n, tau):
-    """L_j(tau), j = 1..n, over the nodes 1..n"""
-    fact = [1] * (n + 1)
-    for k in range(1, n + 1):
-        fact[k] = fact[k - 1] * k % R
-    mt = 1
-    for j in range(1, n + 1):
-        mt = mt * (tau - j) % R
-    out = []
-    for j in range(1, n + 1):
-        d = (tau - j) * fact[j - 1] % R * fact[n - j] % R
-        if (n - j) % 2:
-            d = R - d
-        out.append(mt * pow(d, R - 2, R) % R)
-    return out
-
-
 def qap_at_tau(r1cs, n, w, lag, npublic):
     """(A(tau), B(tau), C(tau)) over the whole witness, and per matrix the column values a_i(tau) of the variables i <= npublic"""
     sums, cols = [], []
