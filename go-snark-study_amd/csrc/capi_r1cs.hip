@@ -1,5 +1,6 @@
 // Sparse R1CS on the device (include/gosnark_hip.h, "R1CS"): upload, and witness -> constraint values -> ax, bx, cx, px.
 #include "prove.h"
+#include "domain.h"
 
 #include <algorithm>
 
@@ -41,24 +42,28 @@ static int r1cs_upload_impl(Ctx& c, size_t n, size_t m, const uint32_t* const rp
   return GS_OK;
 }
 
-// w (standard form, m elements, device) -> o.vals = [A w | B w | C w] (n each, standard form): the values of ax, bx, cx at the
-// nodes 1..n (CombinePolynomials' sum_i w_i alpha_i(x) evaluated there, r1csqap.go:191-210)
+// w (standard form, m elements, device) -> o.vals = [A w | B w | C w] (o.points() each, standard form): the values of ax, bx, cx at the
+// nodes 1..n (CombinePolynomials' sum_i w_i alpha_i(x) evaluated there, r1csqap.go:191-210) -- or, for a domain R1CS, at omega^0 ..
+// omega^(n-1), followed by the zeros of the empty rows up to 2^k
 void gs::r1cs_values_dev(Ctx& c, R1csObj& o, const uint32_t* w_dev) {
-  const size_t n = o.n, m = o.m;
-  o.w_mont.ensure(m * 32); o.vals.ensure(3 * n * 32);
+  const size_t n = o.n, m = o.m, np = o.points();
+  o.w_mont.ensure(m * 32); o.vals.ensure(3 * np * 32);
   GS_HIP(hipMemcpyAsync(o.w_mont.p, w_dev, m * 32, hipMemcpyDeviceToDevice, c.stream));
   poly_canon_dev(c, o.w_mont.as<uint32_t>(), m, 1);                                         // w -> Montgomery
-  for (int k = 0; k < 3; ++k)
-    spmv_dev(c, o.rowptr[k].as<uint32_t>(), o.col[k].as<uint32_t>(), o.val[k].as<uint32_t>(), o.w_mont.as<uint32_t>(), n, m,
-             o.vals.as<uint32_t>() + k * n * 8);
+  for (int k = 0; k < 3; ++k) {
+    uint32_t* out = o.vals.as<uint32_t>() + k * np * 8;
+    spmv_dev(c, o.rowptr[k].as<uint32_t>(), o.col[k].as<uint32_t>(), o.val[k].as<uint32_t>(), o.w_mont.as<uint32_t>(), n, m, out);
+    if (np > n) GS_HIP(hipMemsetAsync(out + n * 8, 0, (np - n) * 32, c.stream));
+  }
 }
 
-// w -> o.coef = [ax | bx | cx] (n each) and px_out (2n - 1), canonical standard form
+// w -> o.coef = [ax | bx | cx] (o.points() each) and px_out (o.npx()), canonical standard form
 void gs::r1cs_px_dev(Ctx& c, R1csObj& o, const uint32_t* w_dev, uint32_t* px_out) {
-  const size_t n = o.n, npx = 2 * n - 1;
+  const size_t n = o.points(), npx = o.npx();
   r1cs_values_dev(c, o, w_dev);
   o.coef.ensure(3 * n * 32); o.prod.ensure(npx * 32);
-  interpolate_dev(c, o.vals.as<uint32_t>(), n, 3, o.coef.as<uint32_t>());
+  if (o.domain_log2) domain_coeffs_dev(c, o.vals.as<uint32_t>(), o.domain_log2, 3, o.coef.as<uint32_t>());   // one transform each (domain.h)
+  else interpolate_dev(c, o.vals.as<uint32_t>(), n, 3, o.coef.as<uint32_t>());
   uint32_t* A = o.coef.as<uint32_t>();
   uint32_t* B = A + n * 8;
   uint32_t* C = B + n * 8;
@@ -115,6 +120,29 @@ int gs_r1cs_upload(size_t n, size_t m,
   });
 }
 
+// The same system as a QAP over the domain of the 2^log2_domain-th roots of unity (domain.h): what snarkjs / circom keys are built on.
+int gs_r1cs_upload_domain(size_t log2_domain, size_t n, size_t m,
+                          const uint32_t* a_rowptr, const uint32_t* a_col, const uint64_t* a_val,
+                          const uint32_t* b_rowptr, const uint32_t* b_col, const uint64_t* b_val,
+                          const uint32_t* c_rowptr, const uint32_t* c_col, const uint64_t* c_val, gs_handle* out) {
+  return guarded([&](Ctx& c) -> int {
+    if (!out) return fail(GS_ERR_ARG, "gs_r1cs_upload_domain: null output");
+    if (log2_domain < 1 || log2_domain > (size_t)kDomainMaxLog2)
+      return fail(GS_ERR_ARG, "gs_r1cs_upload_domain: log2_domain = %zu, must be 1 .. %d", log2_domain, kDomainMaxLog2);
+    if (n > ((size_t)1 << log2_domain))
+      return fail(GS_ERR_SHAPE, "gs_r1cs_upload_domain: %zu constraints do not fit the domain of 2^%zu points", n, log2_domain);
+    const uint32_t* rp[3] = {a_rowptr, b_rowptr, c_rowptr};
+    const uint32_t* cl[3] = {a_col, b_col, c_col};
+    const uint64_t* vl[3] = {a_val, b_val, c_val};
+    auto o = std::make_unique<R1csObj>();
+    const int rc = r1cs_upload_impl(c, n, m, rp, cl, vl, *o);
+    if (rc != GS_OK) return rc;
+    o->domain_log2 = (int)log2_domain;
+    *out = c.put(std::move(o));
+    return GS_OK;
+  });
+}
+
 // ... and every proof only turns its resident witness into the resident px (nothing crosses PCIe).  *px_inout: 0 to create the
 // 2n - 1 coefficient vector, or a handle from an earlier call to overwrite.
 int gs_r1cs_px(gs_handle hr1cs, gs_handle hw, gs_handle* px_inout) {
@@ -123,7 +151,7 @@ int gs_r1cs_px(gs_handle hr1cs, gs_handle hw, gs_handle* px_inout) {
     Scalars* w = c.get<Scalars>(hw, Kind::Scalars);
     if (!o || !w || !px_inout) return fail(GS_ERR_ARG, "gs_r1cs_px: bad handle");
     if (w->n != o->m) return fail(GS_ERR_SHAPE, "len(w) = %zu but the system has %zu variables", w->n, o->m);
-    const size_t npx = 2 * o->n - 1;
+    const size_t npx = o->npx();
     Scalars* px = nullptr;
     if (*px_inout) {
       px = c.get<Scalars>(*px_inout, Kind::Scalars);

@@ -12,6 +12,7 @@
 // transposed subproduct tree: second half of this file, pk_derive_eval_impl.
 #include <algorithm>
 
+#include "domain.h"
 #include "evaltree.h"
 #include "point_io.h"
 #include "prove.h"
@@ -263,7 +264,56 @@ int pk_derive_eval_impl(Ctx& c, const char* fn, Kind kind, gs_handle hpk, size_t
   hipLaunchKernelGGL(k_ec_leaves, grid1(n, 64), dim3(64), 0, c.stream, cur.as<uint32_t>(), weights.as<uint32_t>(), (uint32_t)n, pk->h_eval.pts.as<uint32_t>());
   GS_HIP(hipGetLastError());
   GS_HIP(hipStreamSynchronize(c.stream));
-  pk->n_eval = n; pk->n_e = n;
+  pk->n_eval = n; pk->n_e = n; pk->eval_domain_log2 = 0;
+  return GS_OK;
+}
+
+// pts[p] = T[bitrev(p)] for bitrev(p) < n, the point at infinity otherwise (p < 2^k): the permuting load of the derivation below
+__global__ void __launch_bounds__(256) k_ec_load_bitrev(const uint32_t* __restrict__ affine, uint32_t n, uint32_t* __restrict__ pts, int k) {
+  const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= (1u << k)) return;
+  const uint32_t i = dom_bitrev(k, p);
+  G1Xyzz v = xyzz_inf<FqTag>();
+  if (i < n) v = xyzz_from_affine(PointIO<FqTag>::load_affine(affine + (size_t)i * 16));
+  store_xyzz<FqTag>(pts + (size_t)p * kPw, v);
+}
+
+// The coset evaluation-basis array of a key over the power-of-two domain 2^k (domain.h), from its h array T alone:
+//   E_j = -(1/(2m)) sum_{i<m} (g omega^j)^(-i) T_i = sum_i omega^(-ij) [(-(1/(2m)) g^(-i)) T_i]:
+// ONE transform of size m in the group with the root omega^(-1).  Term i is loaded into slot bitrev(i) and multiplied by its scalar,
+// then the decimation-in-time stages leave E in natural order: m + m/2 * k scalar multiplications, every addition the complete one
+// (T may hold infinities, equal and opposite points).  A key with only m - 1 points in T takes T[m-1] as infinity.
+int pk_derive_eval_domain_impl(Ctx& c, gs_handle hpk, size_t log2_domain) {
+  const char* fn = "gs_groth16_pk_derive_eval_domain";
+  GrothPkObj* pk = c.get<GrothPkObj>(hpk, Kind::GrothPk);
+  if (!pk) return fail(GS_ERR_ARG, "%s: bad proving-key handle", fn);
+  if (pk->shard_count != 1) return fail(GS_ERR_ARG, "%s: the key is a slice", fn);
+  if (log2_domain < 1 || pk->domain_log2 == 0 || (size_t)pk->domain_log2 != log2_domain)
+    return fail(GS_ERR_SHAPE, "%s: the key's Z (%zu coefficients) is not x^(2^%zu) - 1", fn, pk->nz, log2_domain);
+  const int k = (int)log2_domain;
+  const size_t m = (size_t)1 << k, half_m = m / 2;
+  if (pk->len_h + 1 < m) return fail(GS_ERR_SHAPE, "%s: the key's h array has %zu points, the domain needs %zu", fn, pk->len_h, m - 1);
+  c.drain();
+  DevBuf scal(m * 32), twi(half_m * 32), pts(m * kPw * 4);
+  const uint64_t one[4] = {1, 0, 0, 0};
+  uint64_t wi[4];
+  root_words(k, true, wi);
+  domain_derive_scalars_dev(c, k, scal.as<uint32_t>());
+  scaled_powers_dev(c, wi, one, half_m, twi.as<uint32_t>());
+  hipLaunchKernelGGL(k_ec_load_bitrev, grid1(m), dim3(256), 0, c.stream, pk->h.pts.as<uint32_t>(), (uint32_t)std::min(pk->len_h, m), pts.as<uint32_t>(), k);
+  hipLaunchKernelGGL(k_ec_scale, grid1(m, 64), dim3(64), 0, c.stream, pts.as<uint32_t>(), scal.as<uint32_t>(), (uint32_t)m);
+  const uint32_t nbf = (uint32_t)half_m;
+  for (int s = k - 1; s >= 0; --s)                     // spans 1, 2, .., m/2
+    hipLaunchKernelGGL((k_ec_stage<true>), grid1(nbf, 64), dim3(64), 0, c.stream, pts.as<uint32_t>(), nbf, (uint32_t)(m >> (s + 1)), 1u << s, twi.as<uint32_t>());
+  GS_HIP(hipGetLastError());
+  table_settle(c, pk->h_eval.table, false);
+  pk->h_eval.table.drop();
+  pk->n_eval = 0; pk->e_lo = 0; pk->n_e = 0;
+  pk->h_eval.pts.alloc(m * 64);
+  hipLaunchKernelGGL(k_ec_to_affine, grid1(m), dim3(256), 0, c.stream, pts.as<uint32_t>(), (uint32_t)m, pk->h_eval.pts.as<uint32_t>());
+  GS_HIP(hipGetLastError());
+  GS_HIP(hipStreamSynchronize(c.stream));
+  pk->n_eval = m; pk->n_e = m; pk->eval_domain_log2 = k;
   return GS_OK;
 }
 
@@ -279,6 +329,9 @@ int gs_pinocchio_pk_derive_quot(gs_handle hpk) {
 }
 int gs_groth16_pk_derive_eval(gs_handle hpk, size_t n_constraints) {
   return guarded([&](Ctx& c) -> int { return pk_derive_eval_impl(c, "gs_groth16_pk_derive_eval", Kind::GrothPk, hpk, n_constraints); }, true, false, hpk);
+}
+int gs_groth16_pk_derive_eval_domain(gs_handle hpk, size_t log2_domain) {
+  return guarded([&](Ctx& c) -> int { return pk_derive_eval_domain_impl(c, hpk, log2_domain); }, true, false, hpk);
 }
 int gs_pinocchio_pk_derive_eval(gs_handle hpk, size_t n_constraints) {
   return guarded([&](Ctx& c) -> int { return pk_derive_eval_impl(c, "gs_pinocchio_pk_derive_eval", Kind::PinocchioPk, hpk, n_constraints); }, true, false, hpk);

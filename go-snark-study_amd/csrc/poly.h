@@ -67,6 +67,17 @@ bool hx_direct_dev(Ctx& c, const uint32_t* vals_std, size_t n, size_t dz, uint32
 bool hx_values_dev(Ctx& c, const uint32_t* vals_std, size_t n, size_t dz, uint32_t* hv_out_std);
 void r1cs_check_dev(Ctx& c, const uint32_t* vals_std, size_t n, size_t dz, uint32_t* bad_dev);
 void hx_from_values_dev(Ctx& c, const uint32_t* hv_std, size_t n, size_t dz, uint32_t* hx_out_std);
+// The same stage for a QAP over the power-of-two domain 2^k (domain.h; snarkjs / circom keys).  vals: [A w | B w | C w], m = 2^k each
+// (rows past the last constraint zero), standard form, natural order.  All three work IN PLACE on vals:
+//   domain_coeffs_dev         nvec value vectors -> their interpolants' coefficients (nvec x m, standard form, < 2r): one transform each
+//   r1cs_check_domain_dev     *bad_dev = number of points of the domain at which a b != c (enqueue only)
+//   hx_values_domain_dev      u[j] = (a b - c)(g omega^j), j < m, canonical standard form: the scalars of the h-sum against the coset
+//                             evaluation-basis array; three forward and three inverse transforms of size m and one point-wise kernel
+//   domain_derive_scalars_dev the m scalars -(1/(2m)) g^(-bitrev(p)) of the array's derivation (ecntt.hip), standard form
+void domain_coeffs_dev(Ctx& c, uint32_t* vals_std, int k, uint32_t nvec, uint32_t* coef_std);
+void r1cs_check_domain_dev(Ctx& c, const uint32_t* vals_std, int k, uint32_t* bad_dev);
+void hx_values_domain_dev(Ctx& c, uint32_t* vals_std, int k, uint32_t* u_out_std);
+void domain_derive_scalars_dev(Ctx& c, int k, uint32_t* out_std);
 // CSR sparse matrix (standard-form values) times a Montgomery-form vector -> standard-form vector
 void spmv_dev(Ctx& c, const uint32_t* rowptr, const uint32_t* col, const uint32_t* val_std, const uint32_t* x_mont, size_t nrows, size_t ncols,
               uint32_t* out_std);

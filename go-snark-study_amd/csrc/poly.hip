@@ -72,6 +72,15 @@ struct PolyState {
   // constraints): 3 N, n, n elements and the violated-constraint word, grown to the largest size seen.  Every user enqueues on the
   // polynomial stream (aux 1), so stream order keeps consecutive proofs of different sizes apart.
   DevBuf hx_conv, hx_hv, hx_g, hx_bad;
+  // coset-extension spectra of the power-of-two domains (domain.h), per k; cached beside the twiddles, a few sizes side by side
+  struct DomainTable {
+    int k = 0;
+    uint64_t stamp = 0;
+    DevBuf spec;                                 // slot p: g^dom_coset_exp(k, p) / m, Montgomery
+  };
+  static constexpr int kDomSlots = 4;
+  DomainTable dom[kDomSlots];
+  uint64_t dom_clock = 0;
 };
 static PolyState& poly_state(Ctx& c) { return c.state<PolyState>(c.poly_state); }
 
@@ -594,6 +603,71 @@ bool hx_direct_dev(Ctx& c, const uint32_t* vals_std, size_t n, size_t dz, uint32
   hx_values_dev(c, vals_std, n, dz, poly_state(c).hx_hv.as<uint32_t>());
   hx_from_values_dev(c, poly_state(c).hx_hv.as<uint32_t>(), n, dz, hx_out);
   return true;
+}
+
+// ---- the QAP over a power-of-two domain (domain.h) ------------------------------------------------------------------------------
+static FrConst r2_const() {
+  Fe<ModR, 1> r2;
+  for (int i = 0; i < NL; ++i) r2.l[i] = ModR::r2(i);
+  return to_const(relax<2>(r2));
+}
+// the coset-extension spectrum of the domain 2^k: once per k (synchronises the stream when it builds)
+static const uint32_t* domain_table(Ctx& c, int k) {
+  PolyState& ps = poly_state(c);
+  PolyState::DomainTable* slot = &ps.dom[0];
+  for (auto& e : ps.dom) {
+    if (e.k == k) { e.stamp = ++ps.dom_clock; return e.spec.as<uint32_t>(); }
+    if (e.k == 0 ? slot->k != 0 : (slot->k != 0 && e.stamp < slot->stamp)) slot = &e;      // an empty slot, else the least recently used
+  }
+  if (slot->k != 0) {                                   // queued transforms of earlier tickets may still read the victim
+    GS_HIP(hipStreamSynchronize(c.stream));
+    if (c.aux_stream[1] && c.aux_stream[1] != c.stream) GS_HIP(hipStreamSynchronize(c.aux_stream[1]));
+  }
+  const size_t m = (size_t)1 << k;
+  *slot = PolyState::DomainTable{};
+  slot->spec.alloc(m * 32);
+  hipLaunchKernelGGL(k_domain_table, grid1(m), dim3(256), 0, c.stream, slot->spec.as<uint32_t>(), k, 0, to_const(dom_coset_gen(k)), inv_n_const(k, 0));
+  GS_HIP(hipGetLastError());
+  GS_HIP(hipStreamSynchronize(c.stream));
+  slot->k = k;
+  slot->stamp = ++ps.dom_clock;
+  return slot->spec.as<uint32_t>();
+}
+
+void domain_coeffs_dev(Ctx& c, uint32_t* vals_std, int k, uint32_t nvec, uint32_t* coef_std) {
+  const size_t m = (size_t)1 << k;
+  ntt_forward_n(c, vals_std, nvec * m, k);
+  hipLaunchKernelGGL(k_domain_coeffs, grid1(nvec * m), dim3(256), 0, c.stream, vals_std, k, nvec, inv_n_const(k, 0), coef_std);
+  GS_HIP(hipGetLastError());
+}
+
+void r1cs_check_domain_dev(Ctx& c, const uint32_t* vals_std, int k, uint32_t* bad_dev) {
+  const size_t m = (size_t)1 << k;
+  r1cs_check_dev(c, vals_std, m, m, bad_dev);           // every point of the domain is a root of Z
+}
+
+void hx_values_domain_dev(Ctx& c, uint32_t* vals_std, int k, uint32_t* u_out_std) {
+  const size_t m = (size_t)1 << k;
+  const uint32_t* spec = domain_table(c, k);
+  ntt_forward_n(c, vals_std, 3 * m, k);
+  ntt_inverse_unscaled_of_product_n(c, vals_std, 3 * m, k, spec);
+  hipLaunchKernelGGL(k_hx_domain, grid1(m), dim3(256), 0, c.stream, vals_std, (uint32_t)m, r2_const(), u_out_std);
+  GS_HIP(hipGetLastError());
+}
+
+void domain_derive_scalars_dev(Ctx& c, int k, uint32_t* out_std) {
+  const size_t m = (size_t)1 << k;
+  const uint64_t two_m[4] = {2ull * m, 0, 0, 0}, zero[4] = {0, 0, 0, 0};
+  uint64_t inv2m[4], neg[4];
+  fr_inv_words(two_m, inv2m);
+  fr_sub_words(zero, inv2m, neg);                       // -1 / (2m), standard words, used raw
+  FrConst sc;
+  uint32_t u[8];
+  for (int i = 0; i < 4; ++i) { u[2 * i] = (uint32_t)neg[i]; u[2 * i + 1] = (uint32_t)(neg[i] >> 32); }
+  const Fe<ModR, 6> raw = unpack32<ModR>(u);
+  for (int i = 0; i < NL; ++i) sc.l[i] = raw.l[i];
+  hipLaunchKernelGGL(k_domain_table, grid1(m), dim3(256), 0, c.stream, out_std, k, 1, to_const(dom_coset_gen(k)), sc);
+  GS_HIP(hipGetLastError());
 }
 
 const uint32_t* interpolation_weights_dev(Ctx& c, size_t n) { return ensure_tree(c, n, true).weights.as<uint32_t>(); }

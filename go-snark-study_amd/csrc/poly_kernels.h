@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "domain.h"
 #include "fp29.h"
 
 namespace gs {
@@ -731,6 +732,34 @@ __global__ void __launch_bounds__(256) k_hx_shift_out(const uint32_t* __restrict
   const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= nh) return;
   store_fr_canon(h + (size_t)j * 8, canon(mul(mul(load_fr(conv + (size_t)(n - 1 - j) * 8), load_fr(invfact + (size_t)j * 8)), from_const(inv_N))));
+}
+
+// ---- the QAP over a power-of-two domain (domain.h) ------------------------------------------------------------------------------
+// The two scaling tables of a domain 2^k, one thread per slot: out[p] = scale * g^e(p).
+//   mode 0  the coset-extension spectrum, e = dom_coset_exp, scale = 1 / m in Montgomery form: Montgomery out (canonical)
+//   mode 1  the scalars of the evaluation-basis derivation, e = dom_derive_exp, scale = -1 / (2m) as RAW standard limbs: standard out
+__global__ void __launch_bounds__(256) k_domain_table(uint32_t* __restrict__ out, int k, int mode, FrConst g, FrConst scale) {
+  const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= (1u << k)) return;
+  const uint32_t e = mode == 0 ? dom_coset_exp(k, p) : dom_derive_exp(k, p);
+  store_fr_canon(out + (size_t)p * 8, canon(dom_scaled_pow(from_const(g), e, from_const(scale))));
+}
+// coefficients from the bit-reversed spectra of nvec value vectors of m = 2^k: coef[v m + i] = spec[v m + dom_coeff_slot(i)] / m
+__global__ void __launch_bounds__(256) k_domain_coeffs(const uint32_t* __restrict__ spec, int k, uint32_t nvec, FrConst inv_m, uint32_t* __restrict__ coef) {
+  wave_priority<GS_PRIO_POLY>();
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  if ((t >> k) >= nvec) return;
+  const uint32_t i = t & ((1u << k) - 1u);
+  store_fr(coef + (size_t)t * 8, mul(load_fr(spec + ((size_t)(t - i) + dom_coeff_slot(k, i)) * 8), from_const(inv_m)));
+}
+// u[j] = a_j b_j - c_j from the coset values [a | b | c] (m each, standard form), canonical standard form: the scalars of the h-sum
+// against the coset evaluation-basis array (the -1/2 of Z(y_j) and the 1/m of the transforms live in that array and in the table)
+__global__ void __launch_bounds__(256) k_hx_domain(const uint32_t* __restrict__ ext, uint32_t m, const FrConst r2, uint32_t* __restrict__ u) {
+  wave_priority<GS_PRIO_POLY>();
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= m) return;
+  const Fr2 ab = mul(mul(load_fr(ext + (size_t)j * 8), load_fr(ext + ((size_t)m + j) * 8)), from_const(r2));      // standard a b
+  store_fr_canon(u + (size_t)j * 8, canon(reduce2(sub(ab, load_fr(ext + ((size_t)2 * m + j) * 8)))));
 }
 
 // ---- trusted setup helpers (groth16.go:94-222 on a sparse R1CS) ---------------------------------------------------

@@ -38,6 +38,11 @@ struct ProverKey : Object {
   // the witness route runs the h-MSM over H's VALUES and never interpolates H.  A slice holds entries [e_lo, e_lo + n_e).
   size_t n_eval = 0, e_lo = 0, n_e = 0;
   KeyArray h_eval;
+  // Keys over a power-of-two domain (domain.h; snarkjs / circom Groth16 keys).  domain_log2 = k >= 1: a full key whose Z is exactly
+  // x^m - 1, m = 2^k (read off Z on the host when the key is created; 0 otherwise) -- the only keys a domain R1CS proves with.
+  // eval_domain_log2 says which basis h_eval holds: 0 = the Lagrange basis over the nodes n+1 .. 2n above, k = the coset
+  // evaluation basis of the domain 2^k (m points, natural order).  The evaluation-basis route is taken only when it matches the R1CS.
+  int domain_log2 = 0, eval_domain_log2 = 0;
   // Quotient-basis twin of h (optional; the setups build it, gs_*_pk_set_quot attaches one): with D = deg Z and g = 1 / rev(Z) as a
   // power series (z.inv_rev_mont),  h_quot[m] = sum_{d <= m} g_d h[m - d],  m < n_q = len_h.  floor(x^i / Z) = sum_d g_d x^(i-D-d), so
   // for every px with nh = len(px) - D >= 1 coefficients of floor(px / Z):

@@ -11,6 +11,7 @@
 #include <future>
 #include <vector>
 
+#include "domain.h"
 #include "hostcopy.h"
 #include "point_io.h"
 
@@ -647,10 +648,42 @@ void mark_ticket_reads(const ProofStreams& ps, Scalars* w, Scalars* px_or_hv) {
 // the reference would.  Same result as the resident px of capi_r1cs.hip + gs_*_prove_resident either way.
 bool hx_shape(size_t n, size_t nz) { return n >= 2 && nz >= 1 && (nz - 1 == n - 1 || nz - 1 == n); }
 
-// the three ways to the h-scalars of a witness proof, in the order the prover tries them
+// A domain R1CS (domain.h) proves only with a full Groth16 key whose Z is x^m - 1 for the same m = 2^k and whose h array reaches
+// H's m - 1 coefficients; a nodes-1..n R1CS proves with any key, as ever.
+int check_domain_pair(const char* fn, const ProverKey* pk, const R1csObj* o) {
+  if (!o->domain_log2) return GS_OK;
+  const int k = o->domain_log2;
+  if (pk->kind != Kind::GrothPk) return fail(GS_ERR_SHAPE, "%s: an R1CS over a power-of-two domain proves with Groth16 keys only", fn);
+  if (pk->shard_count != 1) return fail(GS_ERR_SHAPE, "%s: an R1CS over a power-of-two domain proves with a full key, not with a key slice", fn);
+  if (pk->domain_log2 != k)
+    return fail(GS_ERR_SHAPE, "%s: the R1CS lives on the domain of 2^%d points, but the key's Z (%zu coefficients) is not x^(2^%d) - 1", fn, k, pk->nz, k);
+  if (pk->len_h + 1 < ((size_t)1 << k))
+    return fail(GS_ERR_SHAPE, "%s: the key's h array has %zu points, H needs 2^%d - 1", fn, pk->len_h, k);
+  return GS_OK;
+}
+// the evaluation-basis route is open when the key's array is the basis of this R1CS (and gs_set_eval_basis has not closed it)
+bool eval_route(const Ctx& c, const ProverKey* pk, const R1csObj* o) {
+  if (!c.eval_basis || pk->n_eval == 0) return false;
+  if (o->domain_log2) return pk->eval_domain_log2 == o->domain_log2 && pk->n_eval == o->points();
+  return pk->eval_domain_log2 == 0 && pk->n_eval == o->n && hx_shape(o->n, pk->nz);
+}
+
+// the three ways to the h-scalars of a witness proof, in the order the prover tries them (a domain R1CS has two: the coset
+// evaluation-basis route, then px -- its quotient by x^m - 1 goes through the key's Divisor / quotient-basis array like any Z)
 DevScalars witness_scalars(R1csObj* o, const uint32_t* wdev, size_t nz, bool eval, std::function<uint32_t*(Ctx&)> px_buffer) {
-  const size_t npx = 2 * o->n - 1, dz = nz - 1;
+  const size_t npx = o->npx(), dz = nz - 1;
   DevScalars dp{nullptr, npx};
+  if (o->domain_log2) {
+    const int k = o->domain_log2;
+    if (eval)
+      dp.produce_hv = [o, wdev, k](Ctx& cc, uint32_t* hv, uint32_t* bad) {
+        r1cs_values_dev(cc, *o, wdev);
+        r1cs_check_domain_dev(cc, o->vals.as<uint32_t>(), k, bad);
+        hx_values_domain_dev(cc, o->vals.as<uint32_t>(), k, hv);
+      };
+    dp.produce = [o, wdev, px_buffer](Ctx& cc) { r1cs_px_dev(cc, *o, wdev, px_buffer(cc)); };
+    return dp;
+  }
   if (eval)
     dp.produce_hv = [o, wdev, dz](Ctx& cc, uint32_t* hv, uint32_t* bad) {
       r1cs_values_dev(cc, *o, wdev);
@@ -666,7 +699,7 @@ DevScalars witness_scalars(R1csObj* o, const uint32_t* wdev, size_t nz, bool eva
 // leaned on all polynomial stages being serialised on one stream; a slot's buffer is only ever touched by the
 // operation that owns the slot, and a slot is re-used only after its operation was collected.
 uint32_t* exact_px_buffer(Ctx& c, R1csObj* o, int slot) {
-  const size_t npx = 2 * o->n - 1;
+  const size_t npx = o->npx();
   o->prod.ensure(npx * 32);
   DevBuf& b = prove_state(c).exact_px[slot % Ctx::kSlots];
   b.ensure(npx * 32);
@@ -688,13 +721,14 @@ struct WitnessChecks {
 };
 // The preamble of the blocking witness entry points, after the handle / null checks: shapes, the witness onto the device (`w`
 // resident, or `w_host` uploaded as part of the call), the route.
-int witness_blocking_inputs(Ctx& c, ProverKey* pk, R1csObj* o, const Scalars* w, const uint64_t* w_host, size_t nw, const WitnessChecks& chk,
+int witness_blocking_inputs(Ctx& c, const char* fn, ProverKey* pk, R1csObj* o, const Scalars* w, const uint64_t* w_host, size_t nw, const WitnessChecks& chk,
                             DevScalars& dw, DevScalars& dp) {
   if (nw != o->m) return fail(GS_ERR_SHAPE, "len(w) = %zu but the system has %zu variables", nw, o->m);
   if (chk.need_z && pk->nz == 0) return fail(GS_ERR_SHAPE, "the key has no Z");
+  if (int rc = check_domain_pair(fn, pk, o)) return rc;
   reset_timing(c);
   const uint32_t* wdev = w ? w->buf.as<uint32_t>() : upload_tmp(c, prove_state(c).up_w, w_host, nw);
-  const bool eval = c.eval_basis && !(chk.eval_full_key_only && pk->shard_count != 1) && pk->n_eval == o->n && hx_shape(o->n, pk->nz);
+  const bool eval = !(chk.eval_full_key_only && pk->shard_count != 1) && eval_route(c, pk, o);
   dw = DevScalars{wdev, nw};
   dp = witness_scalars_blocking(c, o, wdev, pk->nz, eval);
   return GS_OK;
@@ -738,6 +772,7 @@ int begin_ticket(Ctx& c, const TicketRequest& q, const std::function<std::unique
   if ((host || q.witness) && nw != pk->nvars) return fail(GS_ERR_SHAPE, "len(w) = %zu but the key has %zu variables", nw, pk->nvars);   // before anything is staged
   if (q.refuse_slice && pk->shard_count != 1) return fail(GS_ERR_ARG, "%s: the key is a slice", q.fn);
   if (q.need_z && pk->nz == 0) return fail(GS_ERR_SHAPE, "the key has no Z");
+  if (q.witness) if (int rc = check_domain_pair(q.fn, pk, o)) return rc;
   const int parity = c.free_parity();
   if (parity < 0) return fail(GS_ERR_BUSY, "%s: three operations are already outstanding; call gs_%s_prove_end first", q.fn, pk->scheme);
   std::unique_ptr<ProofInFlight> st = make(pk);
@@ -753,7 +788,7 @@ int begin_ticket(Ctx& c, const TicketRequest& q, const std::function<std::unique
   DevScalars dp;
   if (!q.witness) dp = host ? slot_px_from_host(c, parity, q.px_host, q.npx, st->in) : resident(px);
   else {
-    const bool eval = c.eval_basis && pk->n_eval == o->n && hx_shape(o->n, pk->nz);
+    const bool eval = eval_route(c, pk, o);
     const uint32_t* wdev = dw.p;
     const size_t nz = pk->nz;
     dp = witness_scalars(o, wdev, nz, eval, [o, parity](Ctx& cc) { return exact_px_buffer(cc, o, parity); });
@@ -853,7 +888,7 @@ static int pk_shard_impl(Ctx& c, Ctx& from, const char* scheme, Pk* full, size_t
   for (int i = 0; i < pk->n_g1w; ++i) copy_slice(c, from, PkSrc{&full->g1w[i].pts, pk->w_lo}, pk->n_w, kG1Aff, pk->g1w[i].pts);
   copy_slice(c, from, PkSrc{&full->h.pts, pk->h_lo}, pk->n_h, kG1Aff, pk->h.pts);
   copy_slice(c, from, PkSrc{&full->g2w.pts, pk->w_lo}, pk->n_w, kG2Aff, pk->g2w.pts);
-  if (full->n_eval) {                                   // the evaluation-basis array is cut like the other term ranges (its own split of [0, n))
+  if (full->n_eval && !full->eval_domain_log2) {        // the evaluation-basis array is cut like the other term ranges (its own split of [0, n)); a coset basis (domain.h) stays behind
     Shard sh; sh.index = shard_index; sh.count = shard_count;
     size_t lo, hi;
     shard_range(full->n_eval, sh, lo, hi);
@@ -877,6 +912,7 @@ bool bad_shard(size_t shard_index, size_t shard_count) { return shard_count == 0
 // gs_*_prove_partials_values: the vector must hold exactly the values of the shard's evaluation-basis range
 int check_values_slice(const char* fn, ProverKey* pk, const Scalars* hv, const Shard& sh, bool say_shard) {
   if (pk->n_eval == 0) return fail(GS_ERR_SHAPE, "%s: the key has no evaluation-basis array", fn);
+  if (pk->eval_domain_log2) return fail(GS_ERR_SHAPE, "%s: the key's evaluation-basis array is the coset basis of a power-of-two domain, which the multi-device entry points do not serve", fn);
   size_t lo, hi;
   if (pk->shard_count > 1) { lo = pk->e_lo; hi = pk->e_lo + pk->n_e; } else shard_range(pk->n_eval, sh, lo, hi);
   if (hv->n == hi - lo) return GS_OK;
@@ -898,6 +934,24 @@ void gs::pk_scan_sparsity(Ctx& c, ProverKey& pk) {
 extern "C" {
 
 // ---- Groth16 ----------------------------------------------------------------------------------------------
+// k >= 1 when Z (nz coefficients, any representatives mod r) is exactly x^m - 1 with m = 2^k <= 2^27, else 0: the keys of a QAP over a
+// power-of-two domain (domain.h).  Host work, once per key.
+static int z_domain_log2(const uint64_t* z, size_t nz) {
+  if (nz < 3 || ((nz - 1) & (nz - 2)) != 0 || nz - 1 > ((size_t)1 << kDomainMaxLog2)) return 0;
+  const size_t m = nz - 1;
+  const uint64_t zero[4] = {0, 0, 0, 0}, one[4] = {1, 0, 0, 0};
+  uint64_t d[4];
+  fr_sub_words(z + 4 * m, one, d);
+  if (!fr_is_zero_words(d)) return 0;
+  fr_sub_words(zero, z, d);                              // -z[0] - 1
+  fr_sub_words(d, one, d);
+  if (!fr_is_zero_words(d)) return 0;
+  for (size_t i = 1; i < m; ++i) {
+    const uint64_t* v = z + 4 * i;
+    if ((v[0] | v[1] | v[2] | v[3]) != 0 && !fr_is_zero_words(v)) return 0;
+  }
+  return ceil_log2(m);
+}
 static int groth_pk_create_impl(Ctx& c, gs_handle g1_at, gs_handle g1_bacgamma, gs_handle g2_bacgamma, gs_handle bacdelta, gs_handle ptd,
                                 const uint64_t g1_alpha[12], const uint64_t g1_beta[12], const uint64_t g1_delta[12],
                                 const uint64_t g2_beta[24], const uint64_t g2_delta[24], const uint64_t* z, size_t nz,
@@ -933,6 +987,7 @@ static int groth_pk_create_impl(Ctx& c, gs_handle g1_at, gs_handle g1_bacgamma, 
   pk->delta = g1_affine_from_jacobian_std(g1_delta);
   pk->beta2 = g2_affine_from_jacobian_std(g2_beta);
   pk->delta2 = g2_affine_from_jacobian_std(g2_delta);
+  if (shard_count == 1) pk->domain_log2 = z_domain_log2(z, nz);
   const uint32_t* dz = upload_tmp(c, prove_state(c).up_a, z, nz);
   divisor_init(c, pk->z, dz, nz);
   GS_HIP(hipStreamSynchronize(c.stream));
@@ -1088,7 +1143,8 @@ static int witness_values_impl(Ctx& c, const char* fn, Kind kind, gs_handle hpk,
   Scalars* w = c.get<Scalars>(hw, Kind::Scalars);
   if (!o || !w || !hv_inout || !violated) return fail(GS_ERR_ARG, "%s: bad handle or null output", fn);
   if (w->n != o->m) return fail(GS_ERR_SHAPE, "len(w) = %zu but the system has %zu variables", w->n, o->m);
-  if (!hx_shape(o->n, nz) || pk->n_eval != o->n)
+  if (o->domain_log2) return fail(GS_ERR_SHAPE, "%s: an R1CS over a power-of-two domain is not served by the multi-device entry points", fn);
+  if (!hx_shape(o->n, nz) || pk->n_eval != o->n || pk->eval_domain_log2)
     return fail(GS_ERR_SHAPE, "%s: the key has no evaluation-basis array for a system of %zu constraints", fn, o->n);
   Scalars* hv = nullptr;
   if (*hv_inout) {
@@ -1215,7 +1271,8 @@ int gs_groth16_prove_r1cs(gs_handle hpk, gs_handle hr1cs, gs_handle hw, gs_handl
     if (!pk || !o || !w || !px_inout) return fail(GS_ERR_ARG, "gs_groth16_prove_r1cs: bad handle");
     if (!r || !s || !out_proof || !inf) return fail(GS_ERR_ARG, "null argument");
     if (w->n != o->m) return fail(GS_ERR_SHAPE, "len(w) = %zu but the system has %zu variables", w->n, o->m);
-    const size_t npx = 2 * o->n - 1;
+    if (int rc = check_domain_pair("gs_groth16_prove_r1cs", pk, o)) return rc;
+    const size_t npx = o->npx();
     Scalars* px = nullptr;
     if (*px_inout) {
       px = c.get<Scalars>(*px_inout, Kind::Scalars);
@@ -1246,7 +1303,7 @@ static int groth16_prove_witness_impl(Ctx& c, const char* fn, gs_handle hpk, gs_
   if (!pk || !o || (!host && !w)) return fail(GS_ERR_ARG, "%s: bad handle", fn);
   if ((host && !w_host) || !r || !s || !out_proof || !inf) return fail(GS_ERR_ARG, "null argument");
   DevScalars dw, dp;
-  if (int rc = witness_blocking_inputs(c, pk, o, w, w_host, w ? w->n : nw_host, WitnessChecks{false, true}, dw, dp)) return rc;
+  if (int rc = witness_blocking_inputs(c, fn, pk, o, w, w_host, w ? w->n : nw_host, WitnessChecks{false, true}, dw, dp)) return rc;
   return groth16_prove_impl(c, pk, dw, dp, r, s, out_proof, inf);
 }
 int gs_groth16_prove_witness(gs_handle hpk, gs_handle hr1cs, gs_handle hw, const uint64_t r[4], const uint64_t s[4], uint64_t out_proof[32], int inf[3]) {
@@ -1467,7 +1524,7 @@ static int pinocchio_prove_witness_impl(Ctx& c, const char* fn, gs_handle hpk, g
   if (!pk || !o || (!host && !w)) return fail(GS_ERR_ARG, "%s: bad handle", fn);
   if ((host && !w_host) || !out_proof || !inf) return fail(GS_ERR_ARG, "null argument");
   DevScalars dw, dp;
-  if (int rc = witness_blocking_inputs(c, pk, o, w, w_host, w ? w->n : nw_host, WitnessChecks{true, false}, dw, dp)) return rc;
+  if (int rc = witness_blocking_inputs(c, fn, pk, o, w, w_host, w ? w->n : nw_host, WitnessChecks{true, false}, dw, dp)) return rc;
   return pinocchio_prove_impl(c, pk, dw, dp, out_proof, inf);
 }
 int gs_pinocchio_prove_witness(gs_handle hpk, gs_handle hr1cs, gs_handle hw, uint64_t out_proof[72], int inf[8]) {

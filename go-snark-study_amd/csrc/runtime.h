@@ -139,6 +139,11 @@ struct R1csObj : Object {        // sparse R1CS resident on the device: A, B, C 
   size_t n = 0, m = 0, nnz[3] = {0, 0, 0};
   DevBuf rowptr[3], col[3], val[3];
   DevBuf w_mont, vals, coef, prod;       // grow-once workspaces of gs_r1cs_px
+  // 0: the reference's QAP, row j at the node j + 1.  k >= 1: the QAP over the domain of the 2^k-th roots of unity (domain.h), row j at
+  // omega^j, n <= 2^k; the value and coefficient vectors then have 2^k elements each (rows n .. 2^k - 1 are zero).
+  int domain_log2 = 0;
+  size_t points() const { return domain_log2 ? (size_t)1 << domain_log2 : n; }      // elements per value / coefficient vector
+  size_t npx() const { return 2 * points() - 1; }                                    // coefficients of px = ax bx - cx
   R1csObj() : Object(Kind::R1cs) {}
 };
 struct Scalars : Object {        // n x 8 u32 words, standard form, resident

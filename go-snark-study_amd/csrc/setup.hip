@@ -403,8 +403,32 @@ static int pk_set_eval_impl(Ctx& c, const char* fn, Kind kind, const char* slice
   pk->h_eval.pts.alloc(n * 64);
   GS_HIP(hipMemcpyAsync(pk->h_eval.pts.p, b->buf.p, n * 64, hipMemcpyDeviceToDevice, c.stream));
   GS_HIP(hipStreamSynchronize(c.stream));
-  pk->n_eval = n; pk->e_lo = 0; pk->n_e = n;
+  pk->n_eval = n; pk->e_lo = 0; pk->n_e = n; pk->eval_domain_log2 = 0;
   return GS_OK;
+}
+// The same for the coset evaluation basis of a key over the power-of-two domain 2^k (domain.h): `bases` holds m = 2^k G1 points,
+// E_j = -(1/(2m)) sum_i (g omega^j)^(-i) PowersTauDelta[i], natural order.  Not checked, as above.
+int gs_groth16_pk_set_eval_domain(gs_handle hpk, gs_handle hbases, size_t log2_domain) {
+  return guarded([&](Ctx& c) -> int {
+    const char* fn = "gs_groth16_pk_set_eval_domain";
+    GrothPkObj* pk = c.get<GrothPkObj>(hpk, Kind::GrothPk);
+    Bases* b = c.get<Bases>(hbases, Kind::G1Bases);
+    if (!pk || !b) return fail(GS_ERR_ARG, "%s: bad handle", fn);
+    if (pk->shard_count != 1) return fail(GS_ERR_ARG, "%s: the key is a slice", fn);
+    if (log2_domain < 1 || pk->domain_log2 == 0 || (size_t)pk->domain_log2 != log2_domain)
+      return fail(GS_ERR_SHAPE, "%s: the key's Z (%zu coefficients) is not x^(2^%zu) - 1", fn, pk->nz, log2_domain);
+    const size_t n = (size_t)1 << log2_domain;
+    if (b->n != n) return fail(GS_ERR_SHAPE, "%s: %zu points, the domain has %zu", fn, b->n, n);
+    c.drain();                                  // an outstanding ticket may read the array that goes
+    table_settle(c, pk->h_eval.table, false);
+    pk->h_eval.table.drop();
+    pk->n_eval = 0; pk->n_e = 0;
+    pk->h_eval.pts.alloc(n * 64);
+    GS_HIP(hipMemcpyAsync(pk->h_eval.pts.p, b->buf.p, n * 64, hipMemcpyDeviceToDevice, c.stream));
+    GS_HIP(hipStreamSynchronize(c.stream));
+    pk->n_eval = n; pk->e_lo = 0; pk->n_e = n; pk->eval_domain_log2 = (int)log2_domain;
+    return GS_OK;
+  }, true, false, hpk);
 }
 int gs_groth16_pk_set_eval(gs_handle hpk, gs_handle hbases) {
   return guarded([&](Ctx& c) -> int { return pk_set_eval_impl(c, "gs_groth16_pk_set_eval", Kind::GrothPk, "", hpk, hbases); }, true, false, hpk);

@@ -187,6 +187,32 @@ int gs_r1cs_upload(size_t n, size_t m,
                    const uint32_t* b_rowptr, const uint32_t* b_col, const uint64_t* b_val,
                    const uint32_t* c_rowptr, const uint32_t* c_col, const uint64_t* c_val, gs_handle* out);
 int gs_r1cs_px(gs_handle r1cs, gs_handle w, gs_handle* px_inout);
+/* The same sparse system as a QAP over a POWER-OF-TWO DOMAIN -- what snarkjs / circom Groth16 keys (proving_key.json: polsA/B/C, A,
+ * B1, B2, C, hExps) are built on.  m = 2^log2_domain, 1 <= log2_domain <= 27, n <= m constraints; omega = 5^((r-1)/m); row c of the
+ * system sits at omega^c (rows n .. m-1 are empty); ax, bx, cx are the interpolants of degree < m, Z = x^m - 1, and
+ * H = floor((ax bx - cx) / Z) = coefficients m .. 2m-2 of px.  Same CSR rules and validation as gs_r1cs_upload.  The handle is accepted
+ * by gs_r1cs_px (px has 2m - 1 coefficients: one transform per polynomial, no subproduct tree) and by every Groth16 witness entry point
+ * (gs_groth16_prove_r1cs, gs_groth16_prove_witness, _witness_begin, _witness_host_begin, _witness_host) -- together with a FULL key whose
+ * Z is exactly x^m - 1 for the same m and whose PowersTauDelta (hExps) holds at least m - 1 points: anything else is GS_ERR_SHAPE, and
+ * so are Pinocchio keys, key slices and the multi-device entry points (gs_*_witness_values, *_values).  gs_r1cs_to_px stays nodes-only.
+ * The root convention is confirmed against snarkjs for log2_domain = 2 (the reference's externalVerif/circom-test fixture) and is the
+ * same formula above that.
+ * COSET EVALUATION BASIS.  With g = 5^((r-1)/(2m)), y_j = g omega^j and T = PowersTauDelta[0..m):
+ *     sum_j (ax bx - cx)(y_j) E[j] = sum_i h_i T[i]    for    E[j] = -(1/(2m)) sum_{i<m} y_j^(-i) T[i]    (Z(y_j) = -2 for every j),
+ * so a key that holds E (m G1 points, natural order j <-> y_j) proves a witness with three forward and three inverse transforms of size
+ * m and one point-wise kernel: no product of size 2m, no division; the violated-constraint count is read when the proof is collected and a
+ * non-zero count repeats the proof on the exact route (px, floor quotient), as for the node basis.  gs_groth16_pk_derive_eval_domain
+ * computes E from the key's PowersTauDelta alone -- ONE transform of size m carried out in the group, m + m/2 log2 m scalar
+ * multiplications, once per key, blocking, explicit only; GS_ERR_SHAPE unless the key's Z is x^(2^log2_domain) - 1.
+ * gs_groth16_pk_set_eval_domain attaches an array from a file (not checked against tau, as gs_groth16_pk_set_eval);
+ * gs_groth16_pk_export which = 7 reads it back; gs_handle_bytes / gs_memory_query account for it like the node basis.  A key holds ONE
+ * evaluation-basis array: the route is taken only when the array's basis matches the R1CS of the call; gs_set_eval_basis(0) closes it. */
+int gs_r1cs_upload_domain(size_t log2_domain, size_t n, size_t m,
+                          const uint32_t* a_rowptr, const uint32_t* a_col, const uint64_t* a_val,
+                          const uint32_t* b_rowptr, const uint32_t* b_col, const uint64_t* b_val,
+                          const uint32_t* c_rowptr, const uint32_t* c_col, const uint64_t* c_val, gs_handle* out);
+int gs_groth16_pk_derive_eval_domain(gs_handle pk, size_t log2_domain);
+int gs_groth16_pk_set_eval_domain(gs_handle pk, gs_handle bases, size_t log2_domain);
 
 /* ---- Groth16 prover (groth16/groth16.go) --------------------------------------------------- */
 /* Device-resident proving key: groth16.Pk (groth16.go:15-32).  At, BACGamma (G1), BACDelta:
