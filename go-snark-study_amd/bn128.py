@@ -2,6 +2,10 @@
 (bn128/g1.go:140 MulScalar + :32 Add; bn128/g2.go:142 / :32), backed by the HIP MSM kernels.
 Points are Jacobian tuples of Python ints exactly like the reference's [3]*big.Int /
 [3][2]*big.Int; results come back in the affine normal form [x, y, 1]."""
+import ctypes
+
+import numpy as np
+
 from . import capi
 
 Q = 21888242871839275222246405745257275088696311157297823662689037894645226208583      # bn128.go:40-45
@@ -65,22 +69,19 @@ G2 = _Group(True)
 def Pairing(p1, p2):
     """bn128.Pairing(p1, p2) (bn128.go:179-186): the reduced optimal ate pairing as the reference's nested
     [2][3][2] integers (gs_pairing, host side)."""
-    import numpy as np
     out = np.zeros(48, dtype=np.uint64)
     a, b = capi.g1_points_to_u64([p1]), capi.g2_points_to_u64([p2])
-    capi.check(capi.load_library().gs_pairing(capi.ptr64(a), capi.ptr64(b), capi.ptr64(out)))
+    capi.call("gs_pairing", capi.ptr64(a), capi.ptr64(b), capi.ptr64(out))
     v = capi.u64_to_ints(out)
     return tuple(tuple((v[6 * i + 2 * j], v[6 * i + 2 * j + 1]) for j in range(3)) for i in range(2))
 
 
 def PairingCheck(g1_points, g2_points):
     """prod_i e(g1_i, g2_i) == 1 with one shared final exponentiation (gs_pairing_check)."""
-    import ctypes
-    import numpy as np
     if len(g1_points) != len(g2_points):
         raise ValueError("PairingCheck: %d G1 points, %d G2 points" % (len(g1_points), len(g2_points)))
     a = capi.g1_points_to_u64(g1_points) if g1_points else np.zeros((1, 12), dtype=np.uint64)
     b = capi.g2_points_to_u64(g2_points) if g2_points else np.zeros((1, 24), dtype=np.uint64)
     ok = ctypes.c_int(0)
-    capi.check(capi.load_library().gs_pairing_check(capi.ptr64(a), capi.ptr64(b), len(g1_points), ctypes.byref(ok)))
+    capi.call("gs_pairing_check", capi.ptr64(a), capi.ptr64(b), len(g1_points), ctypes.byref(ok))
     return bool(ok.value)

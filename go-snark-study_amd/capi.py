@@ -232,11 +232,83 @@ def check(status):
         raise GosnarkHipError(status, load_library().gs_last_error().decode("utf-8", "replace"))
 
 
+# ---- the call layer: every module of the package reaches a status-returning gs_* entry point through these ---------------------
+def call(name, *args):
+    """Entry point `name` of the library on args as its _SIGS row takes them; a non-zero status raises GosnarkHipError."""
+    check(getattr(load_library(), name)(*args))
+
+
+def raw(x):
+    """The gs_handle integer of a DeviceHandle, either scheme's DevicePk, a DeviceR1CS (anything with .handle or .h), an int, or
+    None (0: 'no object')."""
+    x = getattr(x, "handle", x)
+    return 0 if x is None else int(getattr(x, "h", x))
+
+
+def harr(xs):
+    """Handle array of a list of whatever raw() takes."""
+    return (Handle * len(xs))(*[raw(x) for x in xs])
+
+
+def result(words, flags=1, rows=1):
+    """(uint64 result buffer of rows x words, its rows x flags infinity flags) for a call that writes affine points."""
+    return np.zeros(words if rows == 1 else (rows, words), dtype=np.uint64), (ctypes.c_int * (flags * rows))()
+
+
+def rs_limbs(r, s):
+    """The randomness of a Groth16 proof reduced mod r -> its two limb pointers."""
+    rs = ints_to_u64([r % R, s % R])
+    return ptr64(rs[0]), ptr64(rs[1])
+
+
+def ticket_cell():
+    """Out-parameter of a *_begin call: pass ctypes.byref(t), the ticket is t.value."""
+    return ctypes.c_uint64(0)
+
+
+class HandleCell:
+    """gs_handle in/out parameter.  Pass .ref; .result() is `existing` when the caller gave an object to overwrite, else a new
+    DeviceHandle of what the library created."""
+
+    def __init__(self, existing=None):
+        self.existing, self.cell = existing, Handle(raw(existing))
+        self.ref = ctypes.byref(self.cell)
+
+    def result(self):
+        return self.existing if self.existing is not None else DeviceHandle(self.cell.value)
+
+
+def csr_args(csrs):
+    """Three CSR triples (row_ptr, col, val) -> the nine pointers of gs_r1cs_upload* / gs_r1cs_to_px / gs_*_setup (an empty matrix
+    still hands over one readable element)."""
+    args = []
+    for rp, cl, vl in csrs:
+        rp = np.ascontiguousarray(rp, dtype=np.uint32)
+        cl = np.ascontiguousarray(cl, dtype=np.uint32)
+        vl = np.ascontiguousarray(vl, dtype=np.uint64).reshape(-1, 4)
+        if cl.size == 0:
+            cl, vl = np.zeros(1, dtype=np.uint32), np.zeros((1, 4), dtype=np.uint64)
+        args += [ptr32(rp), ptr32(cl), ptr64(vl)]
+    return args
+
+
+def affine_words(points, g2_flags):
+    """Affine tuples or None (infinity), points[i] in G2 where g2_flags[i] -> (flat uint64 limbs, c_int infinity flags)."""
+    flat, infs = [], []
+    for p, g2 in zip(points, g2_flags):
+        if p is None:
+            flat += [0] * (4 if g2 else 2)
+        else:
+            flat += ([p[0][0], p[0][1], p[1][0], p[1][1]] if g2 else [p[0], p[1]])
+        infs.append(int(p is None))
+    arr = ints_to_u64(flat).reshape(-1) if flat else np.zeros(0, dtype=np.uint64)
+    return arr, (ctypes.c_int * max(len(infs), 1))(*infs)
+
+
 def init(device=None):
     """gs_init on `device` (default: LOCAL_RANK or 0): one process drives one GPU.  `device` may also be a list of HIP
     ordinals -- one logical device (context) per entry, the same ordinal may repeat (see include/gosnark_hip.h)."""
     global _INIT_DEVICE
-    lib = load_library()
     if device is None:
         if _INIT_DEVICE is not None:          # already initialised: keep it
             return
@@ -244,8 +316,7 @@ def init(device=None):
     devices = tuple(int(d) for d in device) if isinstance(device, (list, tuple)) else (int(device),)
     if _INIT_DEVICE == devices:
         return
-    arr = (ctypes.c_int * len(devices))(*devices)
-    check(lib.gs_init(arr, len(devices)))
+    call("gs_init", (ctypes.c_int * len(devices))(*devices), len(devices))
     _INIT_DEVICE = devices
 
 
@@ -255,7 +326,7 @@ def device_count():
 
 def set_device(logical):
     """Objects created by this host thread from now on live on logical device `logical`."""
-    check(load_library().gs_set_device(int(logical)))
+    call("gs_set_device", int(logical))
 
 
 def get_device():
@@ -263,7 +334,7 @@ def get_device():
 
 
 def handle_device(handle):
-    return load_library().gs_handle_device(Handle(handle.h))
+    return load_library().gs_handle_device(raw(handle))
 
 
 def shutdown():
@@ -278,6 +349,9 @@ def version():
 
 
 # ---- integer <-> limb array helpers -------------------------------------------------------------
+R = 21888242871839275222246405745257275088548364400416034343698204186575808495617
+
+
 def ints_to_u64(vals, words=4):
     """list of non-negative Python ints -> np.uint64 array [len, words] (little-endian limbs)."""
     nbytes = 8 * words
@@ -287,9 +361,9 @@ def ints_to_u64(vals, words=4):
 
 def u64_to_ints(arr, words=4):
     a = np.ascontiguousarray(arr, dtype="<u8").reshape(-1, words)
-    raw = a.tobytes()
+    buf = a.tobytes()
     nbytes = 8 * words
-    return [int.from_bytes(raw[i * nbytes:(i + 1) * nbytes], "little") for i in range(a.shape[0])]
+    return [int.from_bytes(buf[i * nbytes:(i + 1) * nbytes], "little") for i in range(a.shape[0])]
 
 
 def ptr64(a):
@@ -316,6 +390,26 @@ def g2_points_to_u64(points):
     return ints_to_u64(flat).reshape(len(points), 24)
 
 
+def g1_tuples(a):
+    """[n, 12] uint64 -> [(X, Y, Z), ...] ints"""
+    v = u64_to_ints(a)
+    return [(v[3 * i], v[3 * i + 1], v[3 * i + 2]) for i in range(len(v) // 3)]
+
+
+def g2_tuples(a):
+    """[n, 24] uint64 -> [((X0,X1),(Y0,Y1),(Z0,Z1)), ...] ints"""
+    v = u64_to_ints(a)
+    return [((v[6 * i], v[6 * i + 1]), (v[6 * i + 2], v[6 * i + 3]), (v[6 * i + 4], v[6 * i + 5])) for i in range(len(v) // 6)]
+
+
+def u64_rows(x):
+    """ints (reduced mod r here) or an [n, 4] uint64 limb array (taken as it is: the device reduces any value < 2^256) -> contiguous
+    [n, 4] uint64"""
+    if isinstance(x, np.ndarray):
+        return np.ascontiguousarray(x, dtype=np.uint64).reshape(-1, 4)
+    return ints_to_u64([v % R for v in x])
+
+
 class DeviceHandle:
     """RAII wrapper of a gs_handle."""
 
@@ -327,7 +421,7 @@ class DeviceHandle:
         fails all the same (foreign handle) the handle is kept so that the failure is not silent."""
         if self.h:
             lib = load_library()
-            rc = lib.gs_free(Handle(self.h))
+            rc = lib.gs_free(self.h)
             if rc == 0 or lib.gs_device_count() == 0:     # after gs_shutdown every handle is already gone
                 self.h = 0
             else:
@@ -340,152 +434,134 @@ class DeviceHandle:
             pass
 
     def __len__(self):
-        n = ctypes.c_size_t(0)
-        check(load_library().gs_len(Handle(self.h), ctypes.byref(n)))
-        return n.value
+        return _count("gs_len", self)
 
 
-def _upload(fname, arr, n):
-    init()
-    h = Handle(0)
-    check(getattr(load_library(), fname)(ptr64(arr), n, ctypes.byref(h)))
-    return DeviceHandle(h.value)
+def _count(name, h):
+    n = ctypes.c_size_t(0)
+    call(name, raw(h), ctypes.byref(n))
+    return int(n.value)
 
 
 def pk_eval_count(pk_handle):
     """gs_pk_eval_count: evaluation-basis points a resident Groth16 / Pinocchio key holds (0 = none)."""
-    n = ctypes.c_size_t(0)
-    check(load_library().gs_pk_eval_count(Handle(_raw(pk_handle)), ctypes.byref(n)))
-    return int(n.value)
+    return _count("gs_pk_eval_count", pk_handle)
 
 
 def pk_quot_count(pk_handle):
     """gs_pk_quot_count: quotient-basis points a resident Groth16 / Pinocchio key holds (0 = none: the h-sum divides px by Z)."""
-    n = ctypes.c_size_t(0)
-    check(load_library().gs_pk_quot_count(Handle(_raw(pk_handle)), ctypes.byref(n)))
-    return int(n.value)
+    return _count("gs_pk_quot_count", pk_handle)
+
+
+def _upload(name, arr, words):
+    init()
+    a = np.ascontiguousarray(arr, dtype=np.uint64).reshape(-1, words)
+    cell = HandleCell()
+    call(name, ptr64(a), a.shape[0], cell.ref)
+    return cell.result()
 
 
 def g1_upload(points_u64):
-    a = np.ascontiguousarray(points_u64, dtype=np.uint64).reshape(-1, 12)
-    return _upload("gs_g1_upload", a, a.shape[0])
+    return _upload("gs_g1_upload", points_u64, 12)
 
 
 def g2_upload(points_u64):
-    a = np.ascontiguousarray(points_u64, dtype=np.uint64).reshape(-1, 24)
-    return _upload("gs_g2_upload", a, a.shape[0])
+    return _upload("gs_g2_upload", points_u64, 24)
 
 
 def scalars_upload(s_u64):
-    a = np.ascontiguousarray(s_u64, dtype=np.uint64).reshape(-1, 4)
-    return _upload("gs_scalars_upload", a, a.shape[0])
+    return _upload("gs_scalars_upload", s_u64, 4)
 
 
 def g1_fixed_base(s_u64):
-    a = np.ascontiguousarray(s_u64, dtype=np.uint64).reshape(-1, 4)
-    return _upload("gs_g1_fixed_base", a, a.shape[0])
+    return _upload("gs_g1_fixed_base", s_u64, 4)
 
 
 def g2_fixed_base(s_u64):
-    a = np.ascontiguousarray(s_u64, dtype=np.uint64).reshape(-1, 4)
-    return _upload("gs_g2_fixed_base", a, a.shape[0])
+    return _upload("gs_g2_fixed_base", s_u64, 4)
+
+
+def _download(name, handle, words):
+    n = len(handle)
+    out = np.zeros((n, words), dtype=np.uint64)
+    call(name, raw(handle), ptr64(out), n)
+    return out
 
 
 def g1_download(handle):
-    n = len(handle)
-    out = np.zeros((n, 12), dtype=np.uint64)
-    check(load_library().gs_g1_download(Handle(handle.h), ptr64(out), n))
-    return out
+    return _download("gs_g1_download", handle, 12)
 
 
 def g2_download(handle):
-    n = len(handle)
-    out = np.zeros((n, 24), dtype=np.uint64)
-    check(load_library().gs_g2_download(Handle(handle.h), ptr64(out), n))
-    return out
+    return _download("gs_g2_download", handle, 24)
 
 
 def scalars_download(handle):
-    n = len(handle)
-    out = np.zeros((n, 4), dtype=np.uint64)
-    check(load_library().gs_scalars_download(Handle(handle.h), ptr64(out), n))
-    return out
+    return _download("gs_scalars_download", handle, 4)
 
 
 def _affine_result(out, inf, g2):
-    if inf.value:
+    if inf[0]:
         return None
     v = u64_to_ints(out)
     return ((v[0], v[1]), (v[2], v[3])) if g2 else (v[0], v[1])
 
 
+def _point_call(name, g2, *args):
+    """One of the g1 / g2 twins `name` ({g} = the group) whose arguments end in one affine point and its infinity flag."""
+    out, inf = result(16 if g2 else 8)
+    call(name.format(g="g2" if g2 else "g1"), *args, ptr64(out), inf)
+    return _affine_result(out, inf, g2)
+
+
 def msm(bases, scalars_u64, off=0, g2=False):
     """sum_i scalars[i] * bases[off+i] -> affine (x, y) / ((x0,x1),(y0,y1)) ints, None = infinity."""
     s = np.ascontiguousarray(scalars_u64, dtype=np.uint64).reshape(-1, 4)
-    out = np.zeros(16 if g2 else 8, dtype=np.uint64)
-    inf = ctypes.c_int(0)
-    fn = load_library().gs_msm_g2 if g2 else load_library().gs_msm_g1
-    check(fn(Handle(bases.h), ptr64(s), off, s.shape[0], ptr64(out), ctypes.byref(inf)))
-    return _affine_result(out, inf, g2)
+    return _point_call("gs_msm_{g}", g2, raw(bases), ptr64(s), off, s.shape[0])
 
 
 def msm_resident(bases, scalars, n, off=0, soff=0, g2=False):
-    out = np.zeros(16 if g2 else 8, dtype=np.uint64)
-    inf = ctypes.c_int(0)
-    fn = load_library().gs_msm_g2_resident if g2 else load_library().gs_msm_g1_resident
-    check(fn(Handle(bases.h), off, Handle(scalars.h), soff, n, ptr64(out), ctypes.byref(inf)))
-    return _affine_result(out, inf, g2)
+    return _point_call("gs_msm_{g}_resident", g2, raw(bases), off, raw(scalars), soff, n)
 
 
 def sum_affine(points, g2=False):
     """points: list of affine tuples or None (infinity) -> affine sum."""
-    n = len(points)
-    words = 4 if g2 else 2
-    flat, infs = [], []
-    for p in points:
-        if p is None:
-            flat += [0] * words
-            infs.append(1)
-        else:
-            flat += ([p[0][0], p[0][1], p[1][0], p[1][1]] if g2 else [p[0], p[1]])
-            infs.append(0)
-    arr = ints_to_u64(flat).reshape(n, 4 * words) if n else np.zeros((0, 4 * words), dtype=np.uint64)
-    ia = (ctypes.c_int * max(n, 1))(*infs)
-    out = np.zeros(16 if g2 else 8, dtype=np.uint64)
-    inf = ctypes.c_int(0)
-    fn = load_library().gs_g2_sum_affine if g2 else load_library().gs_g1_sum_affine
-    check(fn(ptr64(arr), ia, n, ptr64(out), ctypes.byref(inf)))
-    return _affine_result(out, inf, g2)
+    arr, ia = affine_words(points, [g2] * len(points))
+    return _point_call("gs_{g}_sum_affine", g2, ptr64(arr), ia, len(points))
 
 
-def last_timing():
+def _timing(name, *args):
     t = Timing()
-    check(load_library().gs_last_timing(ctypes.byref(t)))
+    call(name, *args, ctypes.byref(t))
     return {n: getattr(t, n) for n, _ in Timing._fields_}
 
 
-def _raw(h):
-    return int(h.h) if hasattr(h, "h") else int(h)
+def last_timing():
+    return _timing("gs_last_timing")
 
 
 def memory_query():
     """gs_memory_query: what the current logical device's GPU and this library hold (bytes)."""
     init()
     m = Memory()
-    check(load_library().gs_memory_query(ctypes.byref(m)))
+    call("gs_memory_query", ctypes.byref(m))
     return {n: int(getattr(m, n)) for n, _ in Memory._fields_ if n != "reserved"}
+
+
+def _u64_pair(name, *args):
+    a, b = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    call(name, *args, ctypes.byref(a), ctypes.byref(b))
+    return int(a.value), int(b.value)
 
 
 def handle_bytes(h):
     """gs_handle_bytes -> (object bytes, window-table bytes) of one handle."""
-    a, b = ctypes.c_uint64(0), ctypes.c_uint64(0)
-    check(load_library().gs_handle_bytes(Handle(_raw(h)), ctypes.cast(ctypes.byref(a), u64p), ctypes.cast(ctypes.byref(b), u64p)))
-    return int(a.value), int(b.value)
+    return _u64_pair("gs_handle_bytes", raw(h))
 
 
 def release_tables(h):
     """gs_release_tables: drop the window tables of a key / base array (rebuilt on its next use)."""
-    check(load_library().gs_release_tables(Handle(_raw(h))))
+    call("gs_release_tables", raw(h))
 
 
 TABLE_POLICY = {"auto": 0, "always": 1, "never": 2}
@@ -495,117 +571,109 @@ def set_table_policy(policy):
     """gs_set_table_policy: "auto" (table-free until a base array's second use, then a build in instalments paid by the calls
     that follow), "always" (build inside the first call), "never" (table-free only).  Results never depend on it."""
     init()
-    check(load_library().gs_set_table_policy(TABLE_POLICY[policy] if isinstance(policy, str) else int(policy)))
+    call("gs_set_table_policy", TABLE_POLICY[policy] if isinstance(policy, str) else int(policy))
 
 
 def build_tables(h, route=0):
     """gs_build_tables: build the window tables of a key / base array now (blocking).  route: 0 all, 1 px routes only, 2 witness
     routes only."""
-    check(load_library().gs_build_tables(Handle(_raw(h)), int(route)))
+    call("gs_build_tables", raw(h), int(route))
 
 
 def set_memory_limit(nbytes):
     """gs_set_memory_limit (development / test hook): cap on the device bytes the library may hold, 0 = none."""
-    check(load_library().gs_set_memory_limit(ctypes.c_uint64(int(nbytes))))
+    call("gs_set_memory_limit", int(nbytes))
 
 
 def alloc_counters():
     """gs_alloc_counters -> (hipMalloc calls, hipFree calls) the library has made so far."""
-    a, b = ctypes.c_uint64(0), ctypes.c_uint64(0)
-    check(load_library().gs_alloc_counters(ctypes.cast(ctypes.byref(a), u64p), ctypes.cast(ctypes.byref(b), u64p)))
-    return int(a.value), int(b.value)
+    return _u64_pair("gs_alloc_counters")
 
 
 def scalars_update(handle, s_u64):
     """gs_scalars_update: overwrite a resident scalar vector in place (same length) -- no allocation, no device-wide sync."""
     a = np.ascontiguousarray(s_u64, dtype=np.uint64).reshape(-1, 4)
-    check(load_library().gs_scalars_update(Handle(_raw(handle)), ptr64(a), a.shape[0]))
+    call("gs_scalars_update", raw(handle), ptr64(a), a.shape[0])
 
 
 def trim():
     """gs_trim: drop the cached workspaces of the current logical device."""
-    check(load_library().gs_trim())
+    call("gs_trim")
 
 
 def set_eval_basis(on):
     init()
-    check(load_library().gs_set_eval_basis(1 if on else 0))
+    call("gs_set_eval_basis", 1 if on else 0)
 
 
 def set_window_bits(c):
     init()
-    check(load_library().gs_set_window_bits(int(c)))
+    call("gs_set_window_bits", int(c))
 
 
 def zpoly(deg):
     """Z(x) = prod_{i=1}^{deg} (x - i) as a [deg+1, 4] uint64 array (gs_zpoly)."""
     init()
     out = np.zeros((deg + 1, 4), dtype=np.uint64)
-    check(load_library().gs_zpoly(deg, ptr64(out)))
+    call("gs_zpoly", deg, ptr64(out))
     return out
 
 
 def msm_begin(bases, scalars, n, off=0, soff=0, g2=False):
     """Enqueue one resident MSM (gs_msm_g1_begin / gs_msm_g2_begin) -> ticket; at most three operations outstanding per logical device."""
-    t = ctypes.c_uint64(0)
-    fn = load_library().gs_msm_g2_begin if g2 else load_library().gs_msm_g1_begin
-    check(fn(Handle(bases.h), off, Handle(scalars.h), soff, n, ctypes.cast(ctypes.byref(t), u64p)))
+    t = ticket_cell()
+    call("gs_msm_g2_begin" if g2 else "gs_msm_g1_begin", raw(bases), off, raw(scalars), soff, n, ctypes.byref(t))
     return (t.value, g2)
 
 
 def ticket_cancel(ticket):
     """gs_ticket_cancel: abandon a pipelined operation (proof ticket, or the integer of an MSM ticket) without its result."""
-    check(load_library().gs_ticket_cancel(ctypes.c_uint64(ticket[0] if isinstance(ticket, tuple) else ticket)))
+    call("gs_ticket_cancel", ticket[0] if isinstance(ticket, tuple) else ticket)
 
 
 def msm_end(ticket):
-    t, g2 = ticket
-    out = np.zeros(16 if g2 else 8, dtype=np.uint64)
-    inf = ctypes.c_int(0)
-    check(load_library().gs_msm_end(ctypes.c_uint64(t), ptr64(out), ctypes.byref(inf)))
-    return _affine_result(out, inf, g2)
+    return _point_call("gs_msm_end", ticket[1], ticket[0])
 
 
 # ---- several logical devices / communicator (multi.hip) -------------------------------------------------
-def _clone(fname, handle, off, n, target):
-    h = Handle(0)
-    check(getattr(load_library(), fname)(Handle(handle.h), off, n, int(target), ctypes.byref(h)))
-    return DeviceHandle(h.value)
+def _clone(name, handle, target, off, n):
+    cell = HandleCell()
+    call(name, raw(handle), off, len(handle) - off if n is None else n, int(target), cell.ref)
+    return cell.result()
 
 
 def scalars_clone(handle, target, off=0, n=None):
-    return _clone("gs_scalars_clone", handle, off, len(handle) - off if n is None else n, target)
+    return _clone("gs_scalars_clone", handle, target, off, n)
 
 
 def g1_clone(handle, target, off=0, n=None):
-    return _clone("gs_g1_clone", handle, off, len(handle) - off if n is None else n, target)
+    return _clone("gs_g1_clone", handle, target, off, n)
 
 
 def g2_clone(handle, target, off=0, n=None):
-    return _clone("gs_g2_clone", handle, off, len(handle) - off if n is None else n, target)
+    return _clone("gs_g2_clone", handle, target, off, n)
 
 
 def scalars_scatter(full_handle, total, root, slice_handle=None):
     """gs_scalars_scatter (one process per GPU, communicator of comm_init_rank): the root's `total` scalars -> every rank's slice of
     the contiguous split.  full_handle is ignored on the other ranks (pass None)."""
-    h = Handle(slice_handle.h if slice_handle is not None else 0)
-    check(load_library().gs_scalars_scatter(Handle(full_handle.h if full_handle is not None else 0), int(total), int(root), ctypes.byref(h)))
-    return slice_handle if slice_handle is not None else DeviceHandle(h.value)
+    cell = HandleCell(slice_handle)
+    call("gs_scalars_scatter", raw(full_handle), int(total), int(root), cell.ref)
+    return cell.result()
 
 
 def comm_unique_id():
     buf = (ctypes.c_uint8 * 128)()
-    check(load_library().gs_comm_unique_id(buf))
+    call("gs_comm_unique_id", buf)
     return bytes(buf)
 
 
 def comm_init_rank(uid, nranks, rank):
-    buf = (ctypes.c_uint8 * 128).from_buffer_copy(uid)
-    check(load_library().gs_comm_init_rank(buf, int(nranks), int(rank)))
+    call("gs_comm_init_rank", (ctypes.c_uint8 * 128).from_buffer_copy(uid), int(nranks), int(rank))
 
 
 def comm_init_local():
-    check(load_library().gs_comm_init_local())
+    call("gs_comm_init_local")
 
 
 def comm_destroy():
@@ -614,7 +682,7 @@ def comm_destroy():
 
 def comm_info():
     nr, rk, loc, cnt = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0), ctypes.c_uint64(0)
-    check(load_library().gs_comm_info(ctypes.byref(nr), ctypes.byref(rk), ctypes.byref(loc), ctypes.cast(ctypes.byref(cnt), u64p)))
+    call("gs_comm_info", ctypes.byref(nr), ctypes.byref(rk), ctypes.byref(loc), ctypes.byref(cnt))
     return {"nranks": nr.value, "rank": rk.value, "local": bool(loc.value), "collectives": cnt.value}
 
 
@@ -623,32 +691,21 @@ def comm_allgather(block, nblocks_out, local_blocks=1):
     per = len(block) // local_blocks
     send = (ctypes.c_uint8 * len(block)).from_buffer_copy(block)
     recv = (ctypes.c_uint8 * (per * nblocks_out))()
-    check(load_library().gs_comm_allgather(send, per, recv))
+    call("gs_comm_allgather", send, per, recv)
     return bytes(recv)
-
-
-def _harr(handles):
-    return (Handle * len(handles))(*[Handle(h.h if isinstance(h, DeviceHandle) else int(h)) for h in handles])
 
 
 def msm_multi(bases, scalars, g2=False):
     """One MSM over len(bases) logical devices (gs_msm_g1_multi / gs_msm_g2_multi) -> (affine point, used_rccl)."""
-    out = np.zeros(16 if g2 else 8, dtype=np.uint64)
-    inf, used = ctypes.c_int(0), ctypes.c_int(0)
-    fn = load_library().gs_msm_g2_multi if g2 else load_library().gs_msm_g1_multi
-    check(fn(_harr(bases), _harr(scalars), len(bases), ptr64(out), ctypes.byref(inf), ctypes.byref(used)))
+    out, inf = result(16 if g2 else 8)
+    used = ctypes.c_int(0)
+    call("gs_msm_g2_multi" if g2 else "gs_msm_g1_multi", harr(bases), harr(scalars), len(bases), ptr64(out), inf, ctypes.byref(used))
     return _affine_result(out, inf, g2), bool(used.value)
 
 
 def msm_sharded(bases, scalars, g2=False):
-    out = np.zeros(16 if g2 else 8, dtype=np.uint64)
-    inf = ctypes.c_int(0)
-    fn = load_library().gs_msm_g2_sharded if g2 else load_library().gs_msm_g1_sharded
-    check(fn(Handle(bases.h), Handle(scalars.h), ptr64(out), ctypes.byref(inf)))
-    return _affine_result(out, inf, g2)
+    return _point_call("gs_msm_{g}_sharded", g2, raw(bases), raw(scalars))
 
 
 def device_timing(logical):
-    t = Timing()
-    check(load_library().gs_device_timing(int(logical), ctypes.byref(t)))
-    return {n: getattr(t, n) for n, _ in Timing._fields_}
+    return _timing("gs_device_timing", int(logical))

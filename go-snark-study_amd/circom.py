@@ -16,11 +16,9 @@ above that).  It maps onto the engine's Groth16 key one to one:
 
 polsA/B/C[s] = {row c: coefficient of signal s in row c} are transposed into the CSR rows the device multiplies the witness with.
 Values are decimal strings; ["0", "1", "0"] (Z = 0) is the point at infinity.  The newer .zkey / .wtns binaries are not read here."""
-import ctypes
-
 import numpy as np
 
-from . import capi, groth16, r1csqap, utils
+from . import _scheme, capi, groth16, r1csqap, utils
 
 R = groth16.R
 G1_INF = (0, 1, 0)
@@ -120,14 +118,8 @@ class DeviceDomainR1CS(r1csqap.DeviceR1CS):
     """A sparse R1CS resident on the device as a QAP over the domain 2^log2_domain (gs_r1cs_upload_domain)."""
 
     def __init__(self, log2_domain, a_csr, b_csr, c_csr, nvars):
-        capi.init()
-        self.n, self.nvars, self.log2_domain = a_csr[0].shape[0] - 1, nvars, int(log2_domain)
-        a = r1csqap._csr_args((a_csr, b_csr, c_csr))
-        h = capi.Handle(0)
-        capi.check(capi.load_library().gs_r1cs_upload_domain(self.log2_domain, self.n, nvars, capi.ptr32(a[0]), capi.ptr32(a[1]), capi.ptr64(a[2]),
-                                                             capi.ptr32(a[3]), capi.ptr32(a[4]), capi.ptr64(a[5]), capi.ptr32(a[6]), capi.ptr32(a[7]),
-                                                             capi.ptr64(a[8]), ctypes.byref(h)))
-        self.handle = capi.DeviceHandle(h.value)
+        self.log2_domain = int(log2_domain)
+        self._upload("gs_r1cs_upload_domain", (self.log2_domain,), (a_csr, b_csr, c_csr), nvars)
 
 
 def UploadProvingKey(pkj):
@@ -146,14 +138,13 @@ def UploadProvingKey(pkj):
 def DeriveEvalBasis(dev_pk, log2_domain):
     """Compute the coset evaluation-basis array of a resident domain key from its hExps alone and attach it
     (gs_groth16_pk_derive_eval_domain: one transform of size 2^log2_domain in the group, once per key)."""
-    capi.check(capi.load_library().gs_groth16_pk_derive_eval_domain(capi.Handle(dev_pk.handle.h), int(log2_domain)))
+    _scheme.derive_basis(groth16._S, "eval_domain", dev_pk, int(log2_domain))
 
 
 def SetEvalBasis(dev_pk, points, log2_domain):
     """Attach a coset evaluation-basis array (2^log2_domain Jacobian int triples, natural order) read from a file
     (gs_groth16_pk_set_eval_domain)."""
-    b = capi.g1_upload(capi.ints_to_u64([c for p in points for c in p]).reshape(-1, 12))
-    capi.check(capi.load_library().gs_groth16_pk_set_eval_domain(capi.Handle(dev_pk.handle.h), capi.Handle(b.h), int(log2_domain)))
+    _scheme.set_basis(groth16._S, "eval_domain", dev_pk, capi.g1_points_to_u64(points), int(log2_domain))
 
 
 def GenerateProofsWithRS(dev_pk, dev_r1cs, w, r, s):
@@ -214,7 +205,5 @@ def UploadProvingKeyBinary(path):
             np.ascontiguousarray(sec["R1CS.%s.col" % n]).reshape(-1).astype(np.uint32),
             np.ascontiguousarray(sec["R1CS.%s.val" % n], dtype=np.uint64).reshape(-1, 4)) for n in "ABC"]
     if EVAL_SECTION in sec:
-        e = capi.g1_upload(np.ascontiguousarray(sec[EVAL_SECTION], dtype=np.uint64))
-        capi.check(capi.load_library().gs_groth16_pk_set_eval_domain(capi.Handle(dev.handle.h), capi.Handle(e.h), k))
-        e.free()
+        _scheme.set_basis(groth16._S, "eval_domain", dev, sec[EVAL_SECTION], k)
     return dev, DeviceDomainR1CS(k, csr[0], csr[1], csr[2], nvars)

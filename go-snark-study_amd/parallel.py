@@ -26,11 +26,8 @@ def shard_range(n, world, rank):
 def _encode(point, g2):
     words = 16 if g2 else 8
     buf = np.zeros(words + 1, dtype=np.uint64)
-    if point is None:
-        buf[words] = 1
-    else:
-        flat = [point[0][0], point[0][1], point[1][0], point[1][1]] if g2 else [point[0], point[1]]
-        buf[:words] = capi.ints_to_u64(flat).reshape(-1)
+    buf[:words], inf = capi.affine_words([point], [g2])
+    buf[words] = inf[0]
     return buf
 
 

@@ -1,12 +1,9 @@
 """Mirror of the reference's r1csqap.PolynomialField (r1csqap/r1csqap.go:45-216) on the HIP kernels.
 Polynomials are lists of Python ints (coefficients mod r, lowest degree first), like []*big.Int."""
-import ctypes
-
 import numpy as np
 
 from . import capi
-
-R = 21888242871839275222246405745257275088548364400416034343698204186575808495617
+from .capi import R
 
 
 def _arr(v):
@@ -22,7 +19,7 @@ class PolynomialField:
     def Mul(self, a, b):                     # r1csqap.go:57-67
         capi.init()
         out = np.zeros((len(a) + len(b) - 1, 4), dtype=np.uint64)
-        capi.check(capi.load_library().gs_poly_mul(capi.ptr64(_arr(a)), len(a), capi.ptr64(_arr(b)), len(b), capi.ptr64(out)))
+        capi.call("gs_poly_mul", capi.ptr64(_arr(a)), len(a), capi.ptr64(_arr(b)), len(b), capi.ptr64(out))
         return capi.u64_to_ints(out)
 
     def Div(self, a, b):                     # r1csqap.go:70-84 -> (quotient, remainder)
@@ -30,14 +27,14 @@ class PolynomialField:
         nq, nr = len(a) - len(b) + 1, len(b) - 1
         q = np.zeros((nq, 4), dtype=np.uint64)
         r = np.zeros((max(nr, 1), 4), dtype=np.uint64)
-        capi.check(capi.load_library().gs_poly_div(capi.ptr64(_arr(a)), len(a), capi.ptr64(_arr(b)), len(b), capi.ptr64(q), capi.ptr64(r)))
+        capi.call("gs_poly_div", capi.ptr64(_arr(a)), len(a), capi.ptr64(_arr(b)), len(b), capi.ptr64(q), capi.ptr64(r))
         return capi.u64_to_ints(q), capi.u64_to_ints(r)[:nr]
 
     def _addsub(self, a, b, name):
         capi.init()
         n = max(len(a), len(b))
         out = np.zeros((n, 4), dtype=np.uint64)
-        capi.check(getattr(capi.load_library(), name)(capi.ptr64(_arr(a)), len(a), capi.ptr64(_arr(b)), len(b), capi.ptr64(out)))
+        capi.call(name, capi.ptr64(_arr(a)), len(a), capi.ptr64(_arr(b)), len(b), capi.ptr64(out))
         return capi.u64_to_ints(out)
 
     def Add(self, a, b):                     # r1csqap.go:94-103
@@ -49,13 +46,13 @@ class PolynomialField:
     def Eval(self, v, x):                    # r1csqap.go:118-126
         capi.init()
         out = np.zeros(4, dtype=np.uint64)
-        capi.check(capi.load_library().gs_poly_eval(capi.ptr64(_arr(v)), len(v), capi.ptr64(_arr([x])), capi.ptr64(out)))
+        capi.call("gs_poly_eval", capi.ptr64(_arr(v)), len(v), capi.ptr64(_arr([x])), capi.ptr64(out))
         return capi.u64_to_ints(out)[0]
 
     def LagrangeInterpolation(self, v):      # r1csqap.go:150-158 (nodes 1..len(v))
         capi.init()
         out = np.zeros((len(v), 4), dtype=np.uint64)
-        capi.check(capi.load_library().gs_lagrange_interpolation(capi.ptr64(_arr(v)), len(v), capi.ptr64(out)))
+        capi.call("gs_lagrange_interpolation", capi.ptr64(_arr(v)), len(v), capi.ptr64(out))
         return capi.u64_to_ints(out)
 
     def DivisorPolynomial(self, px, z):      # r1csqap.go:213-216
@@ -137,18 +134,7 @@ def ComputePx(a_csr, b_csr, c_csr, w_u64, nvars):
     w = np.ascontiguousarray(w_u64, dtype=np.uint64).reshape(-1, 4)
     assert w.shape[0] == nvars
     out = [np.zeros((n, 4), dtype=np.uint64) for _ in range(3)] + [np.zeros((2 * n - 1, 4), dtype=np.uint64)]
-    args = []
-    for rp, cl, vl in (a_csr, b_csr, c_csr):
-        rp = np.ascontiguousarray(rp, dtype=np.uint32)
-        cl = np.ascontiguousarray(cl, dtype=np.uint32)
-        vl = np.ascontiguousarray(vl, dtype=np.uint64).reshape(-1, 4)
-        if cl.size == 0:
-            cl, vl = np.zeros(1, dtype=np.uint32), np.zeros((1, 4), dtype=np.uint64)
-        args += [rp, cl, vl]
-    capi.check(capi.load_library().gs_r1cs_to_px(
-        n, nvars, capi.ptr32(args[0]), capi.ptr32(args[1]), capi.ptr64(args[2]), capi.ptr32(args[3]), capi.ptr32(args[4]), capi.ptr64(args[5]),
-        capi.ptr32(args[6]), capi.ptr32(args[7]), capi.ptr64(args[8]), capi.ptr64(w),
-        capi.ptr64(out[0]), capi.ptr64(out[1]), capi.ptr64(out[2]), capi.ptr64(out[3])))
+    capi.call("gs_r1cs_to_px", n, nvars, *capi.csr_args((a_csr, b_csr, c_csr)), capi.ptr64(w), *map(capi.ptr64, out))
     return tuple(out)
 
 
@@ -157,33 +143,22 @@ def ZPoly(deg):
     return capi.u64_to_ints(capi.zpoly(deg))
 
 
-def _csr_args(csrs):
-    args = []
-    for rp, cl, vl in csrs:
-        rp = np.ascontiguousarray(rp, dtype=np.uint32)
-        cl = np.ascontiguousarray(cl, dtype=np.uint32)
-        vl = np.ascontiguousarray(vl, dtype=np.uint64).reshape(-1, 4)
-        if cl.size == 0:
-            cl, vl = np.zeros(1, dtype=np.uint32), np.zeros((1, 4), dtype=np.uint64)
-        args += [rp, cl, vl]
-    return args
-
-
 class DeviceR1CS:
     """A sparse R1CS resident on the device (gs_r1cs_upload): upload once per circuit, then ComputePxResident per proof."""
 
     def __init__(self, a_csr, b_csr, c_csr, nvars):
+        self._upload("gs_r1cs_upload", (), (a_csr, b_csr, c_csr), nvars)
+
+    def _upload(self, name, domain, csrs, nvars):
+        """gs_r1cs_upload / gs_r1cs_upload_domain (whose arguments begin with the domain's log2)."""
         capi.init()
-        self.n, self.nvars = a_csr[0].shape[0] - 1, nvars
-        a = _csr_args((a_csr, b_csr, c_csr))
-        h = capi.Handle(0)
-        capi.check(capi.load_library().gs_r1cs_upload(self.n, nvars, capi.ptr32(a[0]), capi.ptr32(a[1]), capi.ptr64(a[2]), capi.ptr32(a[3]),
-                                                      capi.ptr32(a[4]), capi.ptr64(a[5]), capi.ptr32(a[6]), capi.ptr32(a[7]), capi.ptr64(a[8]),
-                                                      ctypes.byref(h)))
-        self.handle = capi.DeviceHandle(h.value)
+        self.n, self.nvars = csrs[0][0].shape[0] - 1, nvars
+        cell = capi.HandleCell()
+        capi.call(name, *domain, self.n, nvars, *capi.csr_args(csrs), cell.ref)
+        self.handle = cell.result()
 
     def ComputePxResident(self, w_handle, px_handle=None):
         """resident w (capi.scalars_upload) -> resident px (a capi.DeviceHandle; pass the previous one to overwrite it)."""
-        h = capi.Handle(px_handle.h if px_handle is not None else 0)
-        capi.check(capi.load_library().gs_r1cs_px(capi.Handle(self.handle.h), capi.Handle(w_handle.h), ctypes.byref(h)))
-        return px_handle if px_handle is not None else capi.DeviceHandle(h.value)
+        cell = capi.HandleCell(px_handle)
+        capi.call("gs_r1cs_px", capi.raw(self), capi.raw(w_handle), cell.ref)
+        return cell.result()

@@ -98,17 +98,20 @@ class QuotientInstance(RandomInstance):
     def __init__(self, n, seed):
         import hashlib
         super().__init__(n, seed)
-        lib = capi.load_library()
         self.hx_host = scalars_u64(n, seed + 11)
-        rem = scalars_u64(n - 2, seed + 12)
-        prod = np.zeros((2 * n - 1, 4), dtype=np.uint64)
-        capi.check(lib.gs_poly_mul(capi.ptr64(self.hx_host), n, capi.ptr64(self.z_host), self.z_host.shape[0], capi.ptr64(prod)))
-        px = np.zeros((2 * n - 1, 4), dtype=np.uint64)
-        capi.check(lib.gs_poly_add(capi.ptr64(prod), 2 * n - 1, capi.ptr64(rem), n - 2, capi.ptr64(px)))
-        self.px_host = px
+        self.px_host = px = _quotient_px(self.hx_host, self.z_host, scalars_u64(n - 2, seed + 12))
         self.px_sha256 = hashlib.sha256(np.ascontiguousarray(px, dtype="<u8").tobytes()).hexdigest()
         self.px.free()
         self.px = capi.scalars_upload(px)
+
+
+def _quotient_px(hx, z, rem):
+    """hx * z + rem as [2 n - 1, 4] uint64 for n = len(hx), len(z) = n: the library's own gs_poly_mul / gs_poly_add."""
+    n = hx.shape[0]
+    prod, px = np.zeros((2 * n - 1, 4), dtype=np.uint64), np.zeros((2 * n - 1, 4), dtype=np.uint64)
+    capi.call("gs_poly_mul", capi.ptr64(hx), n, capi.ptr64(z), z.shape[0], capi.ptr64(prod))
+    capi.call("gs_poly_add", capi.ptr64(prod), 2 * n - 1, capi.ptr64(rem), rem.shape[0], capi.ptr64(px))
+    return px
 
 
 def quotient_instance(n, seed):
@@ -508,7 +511,6 @@ class RandomPinocchioInstance:
     G1_ARRAYS = ("A", "Ap", "Bp", "C", "Cp", "Kp")
 
     def __init__(self, n, seed):
-        import ctypes
         from . import snark
         self.n, self.m, self.seed = n, n + 1, seed
         m = self.m
@@ -518,15 +520,9 @@ class RandomPinocchioInstance:
         self.w_host = scalars_u64(m, seed + 9)
         self.w_host[0] = (1, 0, 0, 0)
         self.px_host = scalars_u64(2 * n - 1, seed + 10)
-        z = capi.zpoly(m - 2)
-        h = capi.Handle(0)
-        H = lambda x: capi.Handle(x.h)   # noqa: E731
-        capi.check(capi.load_library().gs_pinocchio_pk_create(
-            H(g1["A"]), H(g1["Ap"]), H(b2), H(g1["Bp"]), H(g1["C"]), H(g1["Cp"]), H(g1["Kp"]), H(g1t),
-            capi.ptr64(z), z.shape[0], m, 1, ctypes.byref(h)))
+        self._pk = snark.device_pk_from_handles(B=b2, G1T=g1t, z_u64=capi.zpoly(m - 2), nvars=m, npublic=1, **g1)
         for x in list(g1.values()) + [g1t, b2]:
             x.free()
-        self._pk = snark.DevicePk(capi.DeviceHandle(h.value), m, 1)
         self.w = capi.scalars_upload(self.w_host)
         self.px = capi.scalars_upload(self.px_host)
 
@@ -545,15 +541,8 @@ class QuotientPinocchioInstance(RandomPinocchioInstance):
     def __init__(self, n, seed):
         import hashlib
         super().__init__(n, seed)
-        lib = capi.load_library()
         self.hx_host = scalars_u64(n, seed + 11)
-        rem = scalars_u64(n - 2, seed + 12)
-        z = capi.zpoly(self.m - 2)
-        prod = np.zeros((2 * n - 1, 4), dtype=np.uint64)
-        capi.check(lib.gs_poly_mul(capi.ptr64(self.hx_host), n, capi.ptr64(z), z.shape[0], capi.ptr64(prod)))
-        px = np.zeros((2 * n - 1, 4), dtype=np.uint64)
-        capi.check(lib.gs_poly_add(capi.ptr64(prod), 2 * n - 1, capi.ptr64(rem), n - 2, capi.ptr64(px)))
-        self.px_host = px
+        self.px_host = px = _quotient_px(self.hx_host, capi.zpoly(self.m - 2), scalars_u64(n - 2, seed + 12))
         self.px_sha256 = hashlib.sha256(np.ascontiguousarray(px, dtype="<u8").tobytes()).hexdigest()
         self.px.free()
         self.px = capi.scalars_upload(px)

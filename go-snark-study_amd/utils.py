@@ -21,7 +21,7 @@ import struct
 
 import numpy as np
 
-from . import capi, groth16, snark
+from . import _scheme, capi, groth16, snark
 
 
 # ---------------------------------------------------------------------------------------------
@@ -297,29 +297,16 @@ def GrothSetupToBinary(path, circuit, pk, vk):
     """pk: groth16.Pk (host integers) or groth16.DevicePk (resident; read back through gs_groth16_pk_export)."""
     sec = {}
     if isinstance(pk, groth16.DevicePk):
-        lib = capi.load_library()
-        for name, which, words in _GROTH_ARRAYS:
-            count = pk.nvars - 1 if which == 4 else pk.nvars
-            a = np.zeros((count, words), dtype=np.uint64)
-            capi.check(lib.gs_groth16_pk_export(capi.Handle(pk.handle.h), which, capi.ptr64(a), count))
-            sec[name] = a
-        singles = np.zeros(84, dtype=np.uint64)
-        capi.check(lib.gs_groth16_pk_export(capi.Handle(pk.handle.h), 5, capi.ptr64(singles), 5))
+        S = groth16._S
+        for name, which, _ in _GROTH_ARRAYS:
+            sec[name] = _scheme.export_array(S, pk, which)
+        singles = _scheme.export_words(S, pk, 5, 5, 84)
         sec["G1.ABD"] = singles[:36].reshape(3, 12)
         sec["G2.BD"] = singles[36:].reshape(2, 24)
-        z = np.zeros((pk.nvars - 1, 4), dtype=np.uint64)
-        capi.check(lib.gs_groth16_pk_export(capi.Handle(pk.handle.h), 6, capi.ptr64(z), z.shape[0]))
-        sec["Z"] = z
-        ne = capi.pk_eval_count(pk.handle)
-        if ne:           # optional section: the evaluation-basis copy of PowersTauDelta (only whoever knew tau can produce it)
-            e = np.zeros((ne, 12), dtype=np.uint64)
-            capi.check(lib.gs_groth16_pk_export(capi.Handle(pk.handle.h), 7, capi.ptr64(e), ne))
-            sec["PowersTauDeltaEval"] = e
-        nq = capi.pk_quot_count(pk.handle)
-        if nq:           # optional section: the quotient-basis array (h-sum over px's top coefficients, no division by Z)
-            q = np.zeros((nq, 12), dtype=np.uint64)
-            capi.check(lib.gs_groth16_pk_export(capi.Handle(pk.handle.h), 10, capi.ptr64(q), nq))
-            sec["PowersTauDeltaQuot"] = q
+        sec["Z"] = _scheme.export_words(S, pk, 6, pk.nvars - 1, (pk.nvars - 1, 4))
+        # optional sections: the evaluation-basis copy of PowersTauDelta (only whoever knew tau can produce it) and the
+        # quotient-basis array (h-sum over px's top coefficients, no division by Z)
+        _optional_sections(S, pk, sec, ("PowersTauDeltaEval", "PowersTauDeltaQuot"))
     else:
         sec["G1.At"] = capi.g1_points_to_u64(pk.G1_At)
         sec["G1.BACGamma"] = capi.g1_points_to_u64(pk.G1_BACGamma)
@@ -334,14 +321,15 @@ def GrothSetupToBinary(path, circuit, pk, vk):
     WriteBinary(path, PROTO_GROTH16, circuit.NVars, circuit.NPublic, sec)
 
 
-def _g1_tuples(a):
-    v = capi.u64_to_ints(a)
-    return [(v[3 * i], v[3 * i + 1], v[3 * i + 2]) for i in range(len(v) // 3)]
+def _optional_sections(S, pk, sec, names):
+    """The arrays of a resident key that it may or may not hold."""
+    for name in names:
+        a = _scheme.export_array(S, pk, S.arrays[name])
+        if len(a):
+            sec[name] = a
 
 
-def _g2_tuples(a):
-    v = capi.u64_to_ints(a)
-    return [((v[6 * i], v[6 * i + 1]), (v[6 * i + 2], v[6 * i + 3]), (v[6 * i + 4], v[6 * i + 5])) for i in range(len(v) // 6)]
+_g1_tuples, _g2_tuples = capi.g1_tuples, capi.g2_tuples
 
 
 def GrothVkFromBinary(path):
@@ -389,13 +377,9 @@ def UploadGrothPkBinary(path, shard=None):
     if shard is None:
         dev = groth16.device_pk_from_handles(at, b1, b2, cd, pt, abd[0], abd[1], abd[2], bd[0], bd[1], z, nvars, npublic)
         if "PowersTauDeltaEval" in sec:          # the witness route then runs its h-MSM over H's values (gs_groth16_pk_set_eval)
-            e = capi.g1_upload(np.ascontiguousarray(sec["PowersTauDeltaEval"], dtype=np.uint64))
-            capi.check(capi.load_library().gs_groth16_pk_set_eval(capi.Handle(dev.handle.h), capi.Handle(e.h)))
-            e.free()
+            _scheme.set_basis(groth16._S, "eval", dev, sec["PowersTauDeltaEval"])
         if "PowersTauDeltaQuot" in sec:          # the px routes then sum h over px's top coefficients (gs_groth16_pk_set_quot)
-            q = capi.g1_upload(np.ascontiguousarray(sec["PowersTauDeltaQuot"], dtype=np.uint64))
-            capi.check(capi.load_library().gs_groth16_pk_set_quot(capi.Handle(dev.handle.h), capi.Handle(q.h)))
-            q.free()
+            _scheme.set_basis(groth16._S, "quot", dev, sec["PowersTauDeltaQuot"])
     else:
         dev = groth16.device_pk_shard_from_handles(at, b1, b2, cd, pt, abd[0], abd[1], abd[2], bd[0], bd[1], z, nvars, npublic, nptd,
                                                    shard[0], shard[1])
@@ -411,25 +395,11 @@ def SetupToBinary(path, circuit, pk, vk=None):
     Note: a resident key's A / Ap hold infinity for i <= NPublic (what the prover sums, snark.go:265)."""
     sec = {}
     if isinstance(pk, snark.DevicePk):
-        lib = capi.load_library()
-        for name, which, words in _PIN_ARRAYS:
-            count = pk.nvars - 1 if which == 7 else pk.nvars
-            a = np.zeros((count, words), dtype=np.uint64)
-            capi.check(lib.gs_pinocchio_pk_export(capi.Handle(pk.h), which, capi.ptr64(a), count))
-            sec[name] = a
-        z = np.zeros((pk.nvars - 1, 4), dtype=np.uint64)
-        capi.check(lib.gs_pinocchio_pk_export(capi.Handle(pk.h), 8, capi.ptr64(z), z.shape[0]))
-        sec["Z"] = z
-        ne = capi.pk_eval_count(pk.handle)
-        if ne:           # optional section: the evaluation-basis copy of G1T
-            e = np.zeros((ne, 12), dtype=np.uint64)
-            capi.check(lib.gs_pinocchio_pk_export(capi.Handle(pk.h), 9, capi.ptr64(e), ne))
-            sec["G1TEval"] = e
-        nq = capi.pk_quot_count(pk.handle)
-        if nq:           # optional section: the quotient-basis array of G1T
-            q = np.zeros((nq, 12), dtype=np.uint64)
-            capi.check(lib.gs_pinocchio_pk_export(capi.Handle(pk.h), 10, capi.ptr64(q), nq))
-            sec["G1TQuot"] = q
+        S = snark._S
+        for name, which, _ in _PIN_ARRAYS:
+            sec[name] = _scheme.export_array(S, pk, which)
+        sec["Z"] = _scheme.export_words(S, pk, 8, pk.nvars - 1, (pk.nvars - 1, 4))
+        _optional_sections(S, pk, sec, ("G1TEval", "G1TQuot"))     # the evaluation-basis copy and the quotient-basis array of G1T
     else:
         for name, _, words in _PIN_ARRAYS:
             pts = getattr(pk, name)
@@ -457,25 +427,12 @@ def SetupFromBinary(path):
 
 def UploadPkBinary(path):
     """Pinocchio key: file -> memmap -> HBM (gs_g1_upload / gs_g2_upload on the mapped sections).  -> (Circuit, DevicePk)."""
-    import ctypes
     protocol, nvars, npublic, sec = ReadBinary(path)
     if protocol != PROTO_PINOCCHIO:
         raise ValueError("error parsing key file: not a Pinocchio key")
-    g1 = {k: capi.g1_upload(np.ascontiguousarray(sec[k], dtype=np.uint64)) for k in ("A", "Ap", "Bp", "C", "Cp", "Kp", "G1T")}
-    b2 = capi.g2_upload(np.ascontiguousarray(sec["B"], dtype=np.uint64))
-    z = np.ascontiguousarray(sec["Z"], dtype=np.uint64)
-    h = capi.Handle(0)
-    H = lambda x: capi.Handle(x.h)   # noqa: E731
-    capi.check(capi.load_library().gs_pinocchio_pk_create(
-        H(g1["A"]), H(g1["Ap"]), H(b2), H(g1["Bp"]), H(g1["C"]), H(g1["Cp"]), H(g1["Kp"]), H(g1["G1T"]),
-        capi.ptr64(z), z.shape[0], nvars, npublic, ctypes.byref(h)))
-    dev = snark.DevicePk(capi.DeviceHandle(h.value), nvars, npublic)
-    if "G1TEval" in sec:
-        e = capi.g1_upload(np.ascontiguousarray(sec["G1TEval"], dtype=np.uint64))
-        capi.check(capi.load_library().gs_pinocchio_pk_set_eval(capi.Handle(dev.h), capi.Handle(e.h)))
-        e.free()
-    if "G1TQuot" in sec:
-        q = capi.g1_upload(np.ascontiguousarray(sec["G1TQuot"], dtype=np.uint64))
-        capi.check(capi.load_library().gs_pinocchio_pk_set_quot(capi.Handle(dev.h), capi.Handle(q.h)))
-        q.free()
+    g1 = {k: capi.g1_upload(sec[k]) for k in ("A", "Ap", "Bp", "C", "Cp", "Kp", "G1T")}
+    dev = snark.device_pk_from_handles(B=capi.g2_upload(sec["B"]), z_u64=sec["Z"], nvars=nvars, npublic=npublic, **g1)
+    for which, name in (("eval", "G1TEval"), ("quot", "G1TQuot")):
+        if name in sec:
+            _scheme.set_basis(snark._S, which, dev, sec[name])
     return snark.Circuit(nvars, npublic), dev

@@ -196,3 +196,144 @@ def test_memory_and_witness_entry_points_without_a_device():
     assert lib.gs_pinocchio_prove_witness(capi.Handle(1), capi.Handle(2), capi.Handle(3), capi.ptr64(out), inf) == -5
     assert lib.gs_groth16_prove_witness(capi.Handle(1), capi.Handle(2), capi.Handle(3), capi.ptr64(rs[0]), capi.ptr64(rs[1]), capi.ptr64(out), inf) == -5
     assert not out.any()
+
+
+@pytest.mark.skipif(_has_gpu(), reason="checks the no-device behaviour")
+def test_every_wrapper_marshals_its_arguments_without_a_device(monkeypatch, tmp_path):
+    """With no device every guarded entry point answers GS_ERR_NOT_INIT before it touches an argument, so calling a wrapper runs
+    exactly its marshalling: each proving, key and MSM wrapper of groth16, snark, circom and capi must end in GosnarkHipError (or
+    return, if it is host side) -- never in ctypes.ArgumentError, TypeError or AttributeError.  capi.init is stubbed out, otherwise
+    the wrappers that begin with it would stop there.  Left out: the communicator wrappers capi.comm_unique_id / comm_init_rank /
+    comm_init_local / comm_destroy / comm_info / comm_allgather and capi.scalars_scatter -- they reach RCCL, which probes the
+    machine's devices and network on its own."""
+    from gosnark_amd import circom, groth16, r1csqap, snark
+    monkeypatch.setattr(capi, "init", lambda device=None: None)
+    ran = []
+
+    def loud(f, *a, **k):
+        ran.append(getattr(f, "__qualname__", repr(f)))
+        try:
+            return f(*a, **k)
+        except capi.GosnarkHipError:
+            return None
+
+    H = capi.DeviceHandle
+    G1, G2, A1, A2 = (1, 2, 1), ((1, 0), (2, 0), (1, 0)), (1, 2), ((1, 0), (2, 0))
+    w, px, r, s = [1, 3], [2, 4, 6], 5, 7
+    w_arr = capi.ints_to_u64(w)
+    csr = r1csqap.csr_from_rows([{0: 1, 1: 2}, {}])
+    wh, pxh, hv = H(31), H(32), H(33)
+    r1 = r1csqap.DeviceR1CS.__new__(r1csqap.DeviceR1CS)
+    r1.handle, r1.n, r1.nvars = H(34), 2, 2
+    circ = groth16.Circuit(2, 1)
+
+    # ---- capi: uploads, downloads, MSMs in both groups, tables, clones
+    for f in (capi.g1_upload, capi.g2_upload, capi.scalars_upload, capi.g1_fixed_base, capi.g2_fixed_base):
+        loud(f, np.zeros((2, {capi.g1_upload: 12, capi.g2_upload: 24}.get(f, 4)), dtype=np.uint64))
+    for f in (capi.g1_download, capi.g2_download, capi.scalars_download, len, capi.pk_eval_count, capi.pk_quot_count, capi.handle_bytes,
+              capi.release_tables, capi.build_tables, capi.handle_device):
+        loud(f, H(9))
+    for g2 in (False, True):
+        loud(capi.msm, H(9), w_arr, 0, g2)
+        loud(capi.msm_resident, H(9), wh, 2, 0, 0, g2)
+        loud(capi.msm_begin, H(9), wh, 2, 0, 0, g2)
+        loud(capi.msm_end, (1, g2))
+        loud(capi.msm_multi, [H(9), 8], [wh, 7], g2)
+        loud(capi.msm_sharded, H(9), wh, g2)
+    assert loud(capi.sum_affine, [A1, None]) == A1 and loud(capi.sum_affine, [A2, None], True) == A2      # host side
+    for f in (capi.scalars_clone, capi.g1_clone, capi.g2_clone):
+        loud(f, H(9), 0, 0, 2)
+    loud(capi.scalars_update, wh, w_arr)
+    loud(capi.ticket_cancel, 1)
+    for f in (capi.last_timing, capi.memory_query, capi.alloc_counters, capi.trim):
+        loud(f)
+    loud(capi.device_timing, 0)
+    loud(capi.set_device, 0)
+    loud(capi.set_table_policy, "auto")
+    loud(capi.set_window_bits, 13)
+    loud(capi.set_eval_basis, True)
+    loud(capi.zpoly, 2)
+
+    # ---- both schemes: the same operations, Groth16's carry r, s
+    gpk, spk = groth16.DevicePk(H(21), 2, 1, None), snark.DevicePk(H(22), 2, 1)
+    ghost = groth16.Pk(BACDelta=[G1] * 2, Z=[1, 2], G1_Alpha=G1, G1_Beta=G1, G1_Delta=G1, G1_At=[G1] * 2, G1_BACGamma=[G1] * 2, G2_Beta=G2,
+                       G2_Delta=G2, G2_BACGamma=[G2] * 2, PowersTauDelta=[G1])
+    shost = snark.Pk(G1T=[G1], A=[G1] * 2, B=[G2] * 2, C=[G1] * 2, Kp=[G1] * 2, Ap=[G1] * 2, Bp=[G1] * 2, Cp=[G1] * 2, Z=[1, 2])
+    for mod, pk, host, rs, ntoxic in ((groth16, gpk, ghost, (r, s), 5), (snark, spk, shost, (), 8)):
+        loud(mod.GenerateTrustedSetupSparse, 2, 2, 1, csr, csr, csr, list(range(1, ntoxic + 1)))
+        loud(mod.UploadPk, host, circ)
+        for name in mod.PK_ARRAYS:
+            loud(mod.ExportPkArray, pk, name)
+        for f in (mod.prove_resident, mod.prove_begin, mod.prove_sharded_rccl):
+            loud(f, pk, wh, pxh, *rs)
+        for f in (mod.prove_from_witness, mod.prove_witness_begin):
+            loud(f, pk, r1, wh, *rs)
+        for f in (mod.prove_witness_host_begin, mod.prove_from_witness_host):
+            loud(f, pk, r1, w, *rs)
+            loud(f, pk, r1, w_arr, *rs)
+        loud(mod.prove_host_begin, pk, w, px, *rs)
+        loud(mod.prove_end, 1)
+        loud(mod.SetEvalBasis, pk, [G1, G1])
+        loud(mod.SetQuotBasis, pk, [G1])
+        loud(mod.SetQuotBasis, pk, None)
+        loud(mod.DeriveQuotBasis, pk)
+        loud(mod.DeriveEvalBasis, pk, 2)
+        for f in (mod.prove_partials, mod.prove_partials_values):
+            loud(f, pk, wh, hv, 0, 2)
+        loud(mod.witness_values, pk, r1, wh)
+        loud(mod.witness_values, pk, r1, wh, hv)
+        for prover in (mod.NewProver(circ, pk, r1), mod.NewProver(circ, pk)):
+            loud(prover.Submit, w, px)
+            prover.Close()
+    loud(groth16.GenerateProofsWithRS, circ, gpk, w, px, r, s)
+    loud(groth16.GenerateProofs, circ, ghost, w, px)
+    loud(groth16.GenerateProofsFromWitnessWithRS, circ, gpk, r1, w, r, s)
+    loud(snark.GenerateProofs, circ, spk, w, px)
+    loud(snark.GenerateProofs, circ, shost, w, px)
+    loud(snark.GenerateProofsFromWitness, circ, spk, r1, w)
+    loud(groth16.NewProver(circ, gpk, r1).SubmitWithRS, w, None, r, s)
+    loud(groth16.prove_from_r1cs, gpk, r1, wh, r, s)
+    loud(groth16.prove_from_r1cs, gpk, r1, wh, r, s, pxh)
+    loud(groth16.ShardPk, gpk, 0, 2)
+    loud(groth16.ShardPkTo, gpk, 0, 2, 0)
+    loud(snark.ShardPk, spk, 0, 2)
+    loud(snark.ShardPk, spk, 0, 2, 0)
+    loud(groth16.UploadPkShard, ghost, circ, 0, 2)
+    loud(groth16.device_pk_from_handles, H(1), H(2), H(3), H(4), H(5), G1, G1, G1, G2, G2, w_arr, 2, 1)
+    loud(groth16.device_pk_shard_from_handles, H(1), H(2), H(3), H(4), H(5), G1, G1, G1, G2, G2, w_arr, 2, 1, 1, 0, 2)
+    loud(snark.device_pk_from_handles, H(1), H(2), H(3), H(4), H(5), H(6), H(7), H(8), w_arr, 2, 1)
+    loud(groth16.finish, gpk, [A1, None, A2, A1, None], r, s)
+    loud(groth16.prove_sharded, gpk, wh, pxh, r, s)
+    loud(groth16.prove_multi, [gpk, gpk], [wh, wh], [pxh, pxh], r, s)
+    loud(groth16.prove_multi_values, [gpk], [wh], [hv], r, s)
+    loud(groth16.prove_sharded_values_rccl, gpk, wh, hv, r, s)
+    loud(groth16.partials_values_begin, gpk, wh, hv, 0, 2)
+    loud(groth16.partials_end, 1)
+    loud(groth16.scatter_values, hv, 2)
+    loud(groth16.prove_batch, [gpk, None], [wh, wh], [pxh, pxh], [(1, 2), (3, 4)])
+    loud(groth16.prove_batch, [gpk], [], [], [])
+    for values in (False, True):
+        loud(snark.prove_multi, [spk, spk], [wh, wh], [pxh, pxh], values)
+        loud(snark.prove_sharded_rccl, spk, wh, pxh, values)
+    loud(snark.prove_batch, [spk, None], [wh, wh], [pxh, pxh])
+    loud(snark.prove_batch, [spk], [], [])
+    rec = (np.zeros(72, dtype=np.uint64), [1] * 8)
+    assert loud(snark.combine, [rec, rec]).PiA == (0, 0, 0)                                                # host side: infinity + infinity
+
+    # ---- circom
+    key, dr1 = groth16.DevicePk(H(41), 2, 1), circom.DeviceDomainR1CS.__new__(circom.DeviceDomainR1CS)
+    dr1.handle, dr1.n, dr1.nvars, dr1.log2_domain = H(42), 2, 2, 1
+    loud(circom.DeviceDomainR1CS, 1, csr, csr, csr, 2)
+    loud(r1csqap.DeviceR1CS, csr, csr, csr, 2)
+    loud(r1.ComputePxResident, wh)
+    loud(r1.ComputePxResident, wh, pxh)
+    loud(circom.DeriveEvalBasis, key, 1)
+    loud(circom.SetEvalBasis, key, [G1, G1], 1)
+    loud(circom.GenerateProofsWithRS, key, dr1, w, r, s)
+    loud(circom.GenerateProofs, key, dr1, w)
+    pkj = circom.ProvingKey(2, 1, 1, [{0: 1}, {}], [{1: 1}, {}], [{}, {}], [G1] * 2, [G1] * 2, [G2] * 2, [G1] * 2, [G1] * 2, G1, G1, G1, G2, G2)
+    loud(circom.UploadProvingKey, pkj)
+    path = str(tmp_path / "key.bin")
+    circom.ProvingKeyToBinary(path, pkj, [G1, G1])
+    loud(circom.UploadProvingKeyBinary, path)
+    assert len(ran) > 150

@@ -410,3 +410,29 @@ def test_pinocchio_derived_array_is_the_definition_equals_the_setups_and_proves_
     assert proof[6] == g1_multiple((At * Bt - Ct) * pow(zt, R - 2, R) % R)
     capi.set_eval_basis(False)
     assert pin_points(snark.prove_from_witness(foreign, dev, inst.w)) == proof
+
+
+def test_pinocchio_uploaded_key_takes_the_setups_array_through_set_eval_basis():
+    """snark.SetEvalBasis (gs_pinocchio_pk_set_eval): a foreign key uploaded with snark.UploadPk from the setup key's exported arrays,
+    G1TEval attached as exported, proves field for field what the setup key proves -- on the witness route, the resident route and,
+    as the DevicePk that UploadPk returns, through snark.prove_multi on one logical device."""
+    n = 16
+    inst = synth.sqchain_pinocchio_instance(n, 0xE700)
+    pk = inst.device_pk()
+    arrays = {k: snark.ExportPkArray(pk, k) for k in snark.PK_ARRAYS}
+    assert len(arrays["G1TEval"]) == n == capi.pk_eval_count(pk)
+    z = np.zeros((inst.m - 1, 4), dtype=np.uint64)
+    capi.call("gs_pinocchio_pk_export", capi.raw(pk), 8, capi.ptr64(z), inst.m - 1)
+    host = snark.Pk(Z=capi.u64_to_ints(z), **{k: arrays[k] for k in ("G1T", "A", "B", "C", "Kp", "Ap", "Bp", "Cp")})
+    foreign = snark.UploadPk(host, snark.Circuit(inst.m, 1))
+    assert isinstance(foreign, snark.DevicePk) and capi.pk_eval_count(foreign) == 0
+    snark.SetEvalBasis(foreign, arrays["G1TEval"])
+    assert capi.pk_eval_count(foreign) == capi.pk_eval_count(pk)
+    assert snark.ExportPkArray(foreign, "G1TEval") == arrays["G1TEval"]
+    dev = r1csqap.DeviceR1CS(*inst.r1cs, inst.m)
+    want = pin_points(snark.prove_from_witness(pk, dev, inst.w))
+    assert pin_points(snark.prove_from_witness(foreign, dev, inst.w)) == want
+    assert pin_points(snark.prove_resident(foreign, inst.w, inst.px)) == want
+    capi.comm_destroy()
+    got, _ = snark.prove_multi([foreign], [inst.w], [inst.px])
+    assert pin_points(got) == want
