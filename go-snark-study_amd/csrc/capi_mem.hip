@@ -19,7 +19,7 @@ void for_each_table(Object* o, F f) {
   switch (o->kind) {
     case Kind::G1Bases: case Kind::G2Bases: {
       auto* b = static_cast<Bases*>(o);
-      if (b->table) f(*static_cast<BaseTable*>(b->table.get()));
+      if (b->table) f(*b->table);
       break;
     }
     default:
@@ -50,7 +50,7 @@ uint64_t object_bytes(Object* o) {
 
 uint64_t table_bytes(Object* o) {
   uint64_t t = 0;
-  for_each_table(o, [&](BaseTable& b) { t += b.rows.bytes + b.pending.bytes; });
+  for_each_table(o, [&](BaseTable& b) { t += b.bytes(); });
   return t;
 }
 
@@ -73,7 +73,7 @@ bool gs::evict_tables_for(size_t need) {
       if (f) for (auto& k : f->keep) held = held || k.get() == o;
     if (held) continue;
     for_each_table(o, [&](BaseTable& b) {
-      if (b.rows.p && !b.pending.p && b.last_use != c->call_clock) cands.push_back(Cand{&b, b.last_use});
+      if (b.evictable(c->call_clock)) cands.push_back(Cand{&b, b.last_use});
     });
   }
   std::sort(cands.begin(), cands.end(), [](const Cand& a, const Cand& b) { return a.stamp < b.stamp; });
@@ -81,8 +81,7 @@ bool gs::evict_tables_for(size_t need) {
   for (auto& cd : cands) {
     if (freed >= need) break;
     freed += cd.t->rows.bytes;
-    cd.t->drop();
-    cd.t->uses = 0;
+    cd.t->evict();
     c->evictions += 1;
   }
   return freed > 0;
@@ -128,13 +127,13 @@ int gs_release_tables(gs_handle h) {
     auto it = c.objs.find(h);
     if (it == c.objs.end()) return fail(GS_ERR_ARG, "gs_release_tables: bad handle");
     c.drain();
-    for_each_table(it->second.get(), [&](BaseTable& b) { table_settle(c, b, false); b.drop(); b.uses = 0; });
+    for_each_table(it->second.get(), [](BaseTable& b) { b.release(); });
     return GS_OK;
   }, true, false, h);
 }
 
-// When base arrays get their window tables: 0 = auto (default: table-free until an array's second use, then a build in the
-// background), 1 = always (inside the first call that needs them: ~140 ms per 2^20 Groth16 key), 2 = never.  Every logical device.
+// When base arrays get their window tables: 0 = auto (default: table-free until an array's second use, then a build in
+// instalments, a few slabs in front of every call's own work), 1 = always (inside the first call that needs them: ~140 ms per 2^20 Groth16 key), 2 = never.  Every logical device.
 int gs_set_table_policy(int policy) {
   if (policy < 0 || policy > 2) return fail(GS_ERR_ARG, "gs_set_table_policy: 0 (auto), 1 (always) or 2 (never)");
   Registry& r = registry();
@@ -162,15 +161,12 @@ int gs_build_tables(gs_handle h, int route) {
     auto build = [&](BaseTable& t, const DevBuf& pts, size_t n, bool g2) {
       if (!n) return;
       t.last_use = c.call_clock;
-      const int cb = choose_window_bits((uint32_t)n, c.window_bits);
-      if (t.pending.p) table_settle(c, t, t.pending_c == cb && t.pending_n == n);
-      if (g2) ensure_table_g2(c, t, pts.as<uint32_t>(), n, cb); else ensure_table_g1(c, t, pts.as<uint32_t>(), n, cb);
+      t.build_now(c, pts.as<uint32_t>(), n, choose_window_bits((uint32_t)n, c.window_bits), g2);
     };
     switch (o->kind) {
       case Kind::G1Bases: case Kind::G2Bases: {
         auto* b = static_cast<Bases*>(o);
-        if (!b->table) b->table = std::make_shared<BaseTable>();
-        build(*static_cast<BaseTable*>(b->table.get()), b->buf, b->n, o->kind == Kind::G2Bases);
+        build(table_of(*b), b->buf, b->n, o->kind == Kind::G2Bases);
         return GS_OK;
       }
       default: {
@@ -208,11 +204,10 @@ int gs_abi_sizes(size_t* timing_bytes, size_t* memory_bytes) {
 // tables, fixed-base tables): all of it is rebuilt on demand.  Keys, base arrays, scalars and their tables stay.
 int gs_trim(void) {
   return guarded([&](Ctx& c) -> int {
-    c.drain();
-    if (c.table_stream) GS_HIP(hipStreamSynchronize(c.table_stream));      // a background table build uses the engine's scratch slab
+    c.drain();                             // (the instalments of a pending table build use the table unit's scratch slab)
     for (int i = 0; i < Ctx::kWsSets; ++i) { c.ws_buckets[i].release(); c.ws_chunks[i].release(); c.ws_partials[i].release(); c.ws_out[i].release(); }
     c.ws_misc.release(); c.g1_pow2.release(); c.g2_pow2.release();
-    c.msm_state.reset(); c.poly_state.reset(); c.prove_state.reset();
+    c.msm_state.reset(); c.poly_state.reset(); c.prove_state.reset(); c.table_state.reset();
     return GS_OK;
   }, true, false);
 }

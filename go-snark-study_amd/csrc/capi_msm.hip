@@ -79,11 +79,10 @@ int msm_resident(Ctx& c, Kind kind, gs_handle hb, size_t off, const uint32_t* sc
   if (n > (size_t)kIndexMask) return fail(GS_ERR_ARG, "at most 2^26 - 1 terms per MSM call (shard larger sums)");
   if (off > b->n || n > b->n - off) return fail(GS_ERR_ARG, "term range [%zu, %zu) exceeds the %zu resident points", off, off + n, b->n);
   // window table of this base array for the width the plan will use (built on first use, kept resident)
-  if (!b->table) b->table = std::make_shared<BaseTable>();
-  BaseTable* tab = static_cast<BaseTable*>(b->table.get());
+  BaseTable* tab = &table_of(*b);
   int cbits = 0;
   double credit = build_credit(T::kWords == 16 ? 2.76 : 1.0, n);      // policy auto: this call's instalment of the array's table
-  const bool tabled = prepare_tables(c, {TableRef{tab, b->buf.as<uint32_t>(), b->n, T::kWords == 16}}, (uint32_t)n, &cbits, &credit);
+  const bool tabled = prepare_tables(c, {table_ref(*b)}, (uint32_t)n, &cbits, &credit);
   PhaseTimer total(c.stream);
   MsmPlan plan;
   {
@@ -133,11 +132,10 @@ int msm_begin(Ctx& c, Kind kind, gs_handle hb, size_t off, gs_handle hs, size_t 
   if (off > b->n || n > b->n - off || soff > sc->n || n > sc->n - soff) return fail(GS_ERR_ARG, "gs_msm_begin: range exceeds the resident arrays");
   const int parity = c.free_parity();
   if (parity < 0) return fail(GS_ERR_BUSY, "gs_msm_begin: three operations are already outstanding");
-  if (!b->table) b->table = std::make_shared<BaseTable>();
-  BaseTable* tab = static_cast<BaseTable*>(b->table.get());
+  BaseTable* tab = &table_of(*b);
   int cbits = 0;
   double credit = build_credit(T::kWords == 16 ? 2.76 : 1.0, n);      // policy auto: this call's instalment of the array's table
-  const bool tabled = prepare_tables(c, {TableRef{tab, b->buf.as<uint32_t>(), b->n, T::kWords == 16}}, (uint32_t)n, &cbits, &credit);
+  const bool tabled = prepare_tables(c, {table_ref(*b)}, (uint32_t)n, &cbits, &credit);
   auto st = std::make_unique<MsmInFlight>();
   st->g2 = T::kWords == 16;
   st->keep = {c.share<Object>(hb, kind), c.share<Object>(hs, Kind::Scalars)};
@@ -285,7 +283,7 @@ static void ctx_destroy(Ctx& c) {
   (void)hipDeviceSynchronize();
   for (auto& f : c.inflight) f.reset();
   c.objs.clear();
-  c.msm_state.reset(); c.poly_state.reset(); c.prove_state.reset();
+  c.msm_state.reset(); c.poly_state.reset(); c.prove_state.reset(); c.table_state.reset();
   for (auto& a : c.aux_stream) {
     if (a && a != c.main_stream) (void)hipStreamDestroy(a);
     a = nullptr;
@@ -302,8 +300,6 @@ static void ctx_destroy(Ctx& c) {
   c.bad_dev.release();
   if (c.copy_stream) (void)hipStreamDestroy(c.copy_stream);
   c.copy_stream = nullptr;
-  if (c.table_stream) (void)hipStreamDestroy(c.table_stream);
-  c.table_stream = nullptr;
   for (int b = 0; b < Ctx::kStageBuffers; ++b) {
     if (c.stage[b]) (void)hipHostFree(c.stage[b]);
     if (c.stage_ev[b]) (void)hipEventDestroy(c.stage_ev[b]);

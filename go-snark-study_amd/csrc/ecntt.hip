@@ -23,8 +23,6 @@ namespace {
 
 constexpr int kPw = PointIO<FqTag>::kXyzzWords;
 
-static inline dim3 grid1(size_t n, int block = 256) { return dim3((unsigned)((n + block - 1) / block)); }
-
 GS_HD void load_words(const uint32_t* __restrict__ p, uint32_t (&k)[8]) {
 #pragma unroll
   for (int i = 0; i < 8; ++i) k[i] = p[i];
@@ -199,8 +197,7 @@ int pk_derive_quot_impl(Ctx& c, const char* fn, Kind kind, gs_handle hpk) {
   for (int s = logn - 1; s >= 0; --s)                  // spans 1, 2, .., N/2
     hipLaunchKernelGGL((k_ec_stage<true>), grid1(nbf, 64), dim3(64), 0, c.stream, pts.as<uint32_t>(), nbf, (uint32_t)(N >> (s + 1)), 1u << s, twi.as<uint32_t>());
   GS_HIP(hipGetLastError());
-  table_settle(c, pk->h_quot.table, false);
-  pk->h_quot.table.drop();
+  pk->h_quot.table.invalidate();
   pk->n_q = 0;
   pk->h_quot.pts.alloc(n * 64);
   hipLaunchKernelGGL(k_ec_to_affine, grid1(n), dim3(256), 0, c.stream, pts.as<uint32_t>(), (uint32_t)n, pk->h_quot.pts.as<uint32_t>());
@@ -257,8 +254,7 @@ int pk_derive_eval_impl(Ctx& c, const char* fn, Kind kind, gs_handle hpk, size_t
     hipLaunchKernelGGL(k_ec_window, grid1(total), dim3(256), 0, c.stream, prod.as<uint32_t>(), cur.as<uint32_t>(), (uint32_t)n, level, (uint32_t)total);
   }
   GS_HIP(hipGetLastError());
-  table_settle(c, pk->h_eval.table, false);
-  pk->h_eval.table.drop();
+  pk->h_eval.table.invalidate();
   pk->n_eval = 0; pk->e_lo = 0; pk->n_e = 0;
   pk->h_eval.pts.alloc(n * 64);
   hipLaunchKernelGGL(k_ec_leaves, grid1(n, 64), dim3(64), 0, c.stream, cur.as<uint32_t>(), weights.as<uint32_t>(), (uint32_t)n, pk->h_eval.pts.as<uint32_t>());
@@ -306,8 +302,7 @@ int pk_derive_eval_domain_impl(Ctx& c, gs_handle hpk, size_t log2_domain) {
   for (int s = k - 1; s >= 0; --s)                     // spans 1, 2, .., m/2
     hipLaunchKernelGGL((k_ec_stage<true>), grid1(nbf, 64), dim3(64), 0, c.stream, pts.as<uint32_t>(), nbf, (uint32_t)(m >> (s + 1)), 1u << s, twi.as<uint32_t>());
   GS_HIP(hipGetLastError());
-  table_settle(c, pk->h_eval.table, false);
-  pk->h_eval.table.drop();
+  pk->h_eval.table.invalidate();
   pk->n_eval = 0; pk->e_lo = 0; pk->n_e = 0;
   pk->h_eval.pts.alloc(m * 64);
   hipLaunchKernelGGL(k_ec_to_affine, grid1(m), dim3(256), 0, c.stream, pts.as<uint32_t>(), (uint32_t)m, pk->h_eval.pts.as<uint32_t>());

@@ -5,6 +5,7 @@
 
 #include "ec.h"
 #include "runtime.h"
+#include "tables.h"
 
 namespace gs {
 
@@ -38,59 +39,6 @@ int choose_window_bits(uint32_t n, int forced);
 // a reduce workgroup never straddles two windows)
 constexpr int kMinFreeWindowBits = 9, kMaxFreeWindowBits = 16;
 int choose_window_bits_free(uint32_t n, int forced);
-
-// Window table of a base array: rows[j][i] = 2^(c j) * P_i (packed affine), j < W = 254 / c + 1.
-struct BaseTable {
-  DevBuf rows;
-  size_t n = 0;
-  int c = 0, W = 0;
-  uint64_t last_use = 0;           // Ctx::call_clock of the last call that used the array (LRU order of evict_tables_for)
-  uint64_t last_table_use = 0;     // ... of the last call that summed it over its TABLE: under policy auto a table that serves is not
-                                   //     replaced by one of another width just because one call wanted that width
-  uint32_t uses = 0;               // proofs / MSMs that found no table since it last had one (table policy auto)
-  // A build under policy auto (round 6: in instalments).  `pending` holds the rows of the table to be; every call that finds the
-  // array without its table enqueues the next slabs of points [pending_next, ...) on the accumulation stream, as many as its build
-  // credit pays for (msm.hip, prepare_tables), and the call that enqueues the last slab installs the table: its accumulation kernel
-  // runs behind the slabs on the same stream.
-  DevBuf pending;
-  int pending_c = 0;
-  size_t pending_n = 0, pending_next = 0;
-  const uint32_t* pending_src = nullptr;      // row 0 (the base array: lives as long as the object that owns this table)
-  bool pending_g2 = false;
-  hipEvent_t pending_done = nullptr;          // recorded behind the last slab
-  bool pending_complete() const { return pending.p != nullptr && pending_next >= pending_n; }
-  bool ready(size_t n_, int c_) const { return rows.p != nullptr && n == n_ && c == c_; }
-  void drop() { rows.release(); n = 0; c = 0; W = 0; }
-  BaseTable() = default;
-  BaseTable(const BaseTable&) = delete;
-  BaseTable& operator=(const BaseTable&) = delete;
-  ~BaseTable() { if (pending_done && !process_exiting()) (void)hipEventDestroy(pending_done); }
-};
-// (Re)build `t` for window width c from row 0 (`row0` = packed affine points; pass nullptr to rebuild from the
-// table's own row 0).  No-op when the table already matches.
-void ensure_table_g1(Ctx& c, BaseTable& t, const uint32_t* row0, size_t n, int cbits);
-void ensure_table_g2(Ctx& c, BaseTable& t, const uint32_t* row0, size_t n, int cbits);
-
-// The base arrays one plan will be multiplied with (a proof's At / BACGamma / BACDelta / BACGamma2 over w; one array for an MSM).
-struct TableRef { BaseTable* t; const uint32_t* row0; size_t n; bool g2; };
-// Decides how the group is summed THIS time and prepares it: true = window tables, all of width *cbits and resident (built now
-// under policy `always`, or found); false = table-free with *cbits from choose_window_bits_free.  Under policy `auto` an array that
-// has been used twice gets its table IN INSTALMENTS: every call enqueues, in front of its own accumulations, as many slabs of the
-// pending table as `*credit` pays for (in G1-point builds; a G2 point costs kG2BuildCost of them; the caller grants ~0.055 points per
-// (job-unit x term) of its own work, i.e. a proof pays ~60 % of its own table-free time on top) and takes what it spent off
-// *credit.  Stamps the tables for the LRU.
-constexpr double kG2BuildCost = 2.3;              // a G2 row costs 2.3 G1 rows (40 vs 17.5 ms per 2^20 points)
-constexpr double kBuildCreditPerUnitTerm = 0.055; // 17.5 ms per 2^20 G1 points built (Jacobian doublings) / 1.5 ms per 2^20 (job-unit x term) summed table-free: 0.055 -> +60 % (6.5 ms per 2^20 proof)
-// The credit a call of `units` job-units (a G1 sum = 1, a G2 sum = 2.76) over n terms grants itself; never less than 2^18 G1 points
-// (~5 ms of building): the tables of a 2^16 key cost 9 ms in all while its table-free proofs take 5.5 ms instead of 2, so small keys are
-// warm after two or three calls instead of sixteen.
-inline double build_credit(double units, size_t n) { return std::max(kBuildCreditPerUnitTerm * units * (double)n, (double)((size_t)1 << 18)); }
-bool prepare_tables(Ctx& c, const std::vector<TableRef>& group, uint32_t nterms, int* cbits, double* credit = nullptr);
-// the tables one call will use, stamped for the LRU BEFORE any of them is built: an allocation made while the first group's tables are
-// built must not evict the second group's (prepare_tables only stamped the group it was called for)
-void stamp_tables(Ctx& c, const std::vector<BaseTable*>& tables);
-// wait for a pending build and install it (finishing it first if instalments are missing) or drop it (gs_release_tables, gs_build_tables)
-void table_settle(Ctx& c, BaseTable& t, bool install);
 
 struct MsmBase {                 // one job of an MSM launch
   const BaseTable* table;        // window-table route: the table ...

@@ -15,8 +15,6 @@ namespace gs {
 static_assert(sizeof(G1Xyzz) == PointIO<FqTag>::kXyzzWords * 4, "G1 XYZZ must be raw limbs");
 static_assert(sizeof(G2Xyzz) == PointIO<Fq2Tag>::kXyzzWords * 4, "G2 XYZZ must be raw limbs");
 
-static inline dim3 grid1(size_t n, int block = 256) { return dim3((unsigned)((n + block - 1) / block)); }
-
 // Window width.  With window tables an MSM costs n * W(c) mixed additions (W = floor(254 / c) + 1 digit positions, all feeding
 // ONE bucket set) plus two complete additions per bucket for the reduction (a complete XYZZ addition is ~1.4 mixed ones) plus
 // the chunk partials, so wide windows pay as soon as n is large against the 2^(c-1) buckets: c = 20 at n = 2^20 is 13
@@ -64,8 +62,6 @@ static void exclusive_scan(Ctx& c, PlanBuffers& pb, const uint32_t* in, uint32_t
 
 struct MsmState {                                  // per context (device memory belongs to one device)
   PlanBuffers plan_slots[3 * Ctx::kSlots];         // (w, h) x slots, then one more per slot: the masked plan over w of keys with sparse B arrays
-  DevBuf table_scratch;                            // slab of the batched window-table builder
-  DevBuf table_scratch_bg;                         // ... and of the builds that run in the background on the table stream
   DevBuf upload_scratch;                           // Jacobian triples of a base array on their way in (upload_jacobian), kept up to kUploadScratchKeep
   DevBuf upload_flag;                              // {points off the curve, first such index} of the conversion kernel
   bool lds_attr_set = false;
@@ -212,236 +208,6 @@ void build_plan(Ctx& c, int slot, const uint32_t* scalars_dev, uint32_t n, MsmPl
   plan.chunk_bucket = pb.chunk_bucket.as<uint32_t>();
   plan.heavy_list = pb.heavy_list.as<uint32_t>();
   plan.heavy_count = pb.counters.as<uint32_t>();
-}
-
-// Enqueue the kernels that fill rows [first, last) of every row of `rows` (W rows of n points, allocated) from row 0 on `stream`.
-// slab: points per launch (2^18 = 1024 workgroups).
-template <class T>
-static void enqueue_table_slabs(hipStream_t stream, DevBuf& scratch, const uint32_t* src, size_t n, int cbits, DevBuf& rows, size_t first, size_t last,
-                                size_t slab) {
-  const int W = 254 / cbits + 1;
-  if (first >= last) return;
-  static const bool per_row = dev_flag("GS_TABLE_PER_ROW");               // the one-inversion-per-row builder, for comparison
-  if (per_row || W <= 2) {
-    // (whole table at once: this builder has no range form; only reached with W <= 2, i.e. never for BN254 widths <= 20)
-    if (first == 0) hipLaunchKernelGGL(k_build_table<T>, grid1(n), dim3(256), 0, stream, src, (uint32_t)n, cbits, W, rows.as<uint32_t>());
-  } else {
-    // slabs: (W - 1) rows of [XYZZ | running product] raw limbs per point (<= 1.4 GiB for G2 at 2^18 points), reused per slab
-    constexpr size_t sw = PointIO<T>::kXyzzWords + PointIO<T>::kXyzzWords / 4;
-    slab = std::min<size_t>(std::max<size_t>(slab, 1), n);
-    scratch.ensure(slab * (size_t)(W - 1) * sw * 4);
-    for (size_t at = first; at < last; at += slab) {
-      const size_t count = std::min(slab, last - at);
-      hipLaunchKernelGGL(k_build_table_batched<T>, grid1(count), dim3(256), 0, stream, src, (uint32_t)n, (uint32_t)at, (uint32_t)count, cbits, W,
-                         rows.as<uint32_t>(), scratch.as<uint32_t>());
-    }
-  }
-  GS_HIP(hipGetLastError());
-}
-template <class T>
-static void enqueue_table_build(Ctx& c, hipStream_t stream, DevBuf& scratch, const uint32_t* src, size_t n, int cbits, DevBuf& fresh,
-                                size_t slab_max = (size_t)1 << 18) {
-  constexpr size_t aw = PointIO<T>::kAffineWords;
-  const int W = 254 / cbits + 1;
-  fresh.alloc(std::max<size_t>(n, 1) * W * aw * 4);
-  enqueue_table_slabs<T>(stream, scratch, src, n, cbits, fresh, 0, n, slab_max);
-}
-
-template <class T>
-static void ensure_table(Ctx& c, BaseTable& t, const uint32_t* row0, size_t n, int cbits) {
-  if (t.c == cbits && t.n == n && t.rows.p) return;
-  table_settle(c, t, false);                    // a pending build of another width: superseded
-  const uint32_t* src = row0 ? row0 : t.rows.as<uint32_t>();
-  if (!src || (!row0 && t.n != n)) throw HipError{hipErrorInvalidValue, "window table rebuild without its points", __LINE__};
-  DevBuf fresh;
-  enqueue_table_build<T>(c, c.stream, msm_state(c).table_scratch, src, n, cbits, fresh);
-  GS_HIP(hipStreamSynchronize(c.stream));       // the old rows (possibly the source) are released below
-  t.rows = std::move(fresh);
-  t.n = n; t.c = cbits; t.W = 254 / cbits + 1;
-  t.uses = 0;
-}
-void ensure_table_g1(Ctx& c, BaseTable& t, const uint32_t* row0, size_t n, int cbits) { ensure_table<FqTag>(c, t, row0, n, cbits); }
-void ensure_table_g2(Ctx& c, BaseTable& t, const uint32_t* row0, size_t n, int cbits) { ensure_table<Fq2Tag>(c, t, row0, n, cbits); }
-
-// ---- when a base array gets its table (gs_set_table_policy) ---------------------------------------------------------------------
-// The reference proves ONCE per key load (cli/main.go:330-349); 15-row tables cost ~140 ms and 15x the key's memory at 2^20 -- fifteen
-// proofs' worth of work before the first one.  Under `auto` a base array is summed table-free until it has been used
-// kTableAfterUses times; from then on every call that finds it without a table builds a few more slabs of it.
-//
-// Round 6: IN INSTALMENTS, in front of the call's own accumulations, on the accumulation stream.  Round 5 enqueued
-// all five builds of a key at once on a lowest-priority stream and let the hardware share the chip: proofs 2-10 of a fresh 2^20 key took
-// 19-35 ms each, unpredictably, and a proof could not use a table the moment it was complete.  The work is what it is -- ~125 ms of
-// full-chip time per 2^20 Groth16 key, and whatever runs beside it is slowed by what it takes ("what overlap can and
-// cannot buy") -- so the only choice is how it is spread over the calls: each call gets a build CREDIT proportional to its own work
-// (msm.h, kBuildCreditPerUnitTerm: ~+80 % of a table-free call), spends it on whole slabs of the pending table (the balance, at most one
-// slab either way, stays on the context), and the call that enqueues the last slab installs the table and uses it -- stream order makes
-// that safe without a host wait.  A fresh 2^20 key: 24 ms, then ~16 proofs of <= 2x the steady time, then steady; a proof never waits for
-// more than its own instalment.  GS_TABLE_BUDGET_PCT scales the credit (100 = as described; 100000 = everything inside the second call).
-constexpr uint32_t kTableAfterUses = 2;
-
-template <class T>
-static void enqueue_pending_slabs(Ctx& c, BaseTable& t, size_t first, size_t last, size_t slab) {
-  enqueue_table_slabs<T>(c.main_stream, msm_state(c).table_scratch_bg, t.pending_src, t.pending_n, t.pending_c, t.pending, first, last, slab);
-}
-static size_t instalment_slab(size_t n, bool g2) {
-  // As LARGE as possible: a builder thread walks its point through 14 x 17 dependent doublings, ~1.3 ms for a lone wave whatever the
-  // slab holds, so a slab must fill the chip to be worth its launch.  2^18 points for G1 (4 waves per SIMD: 5 ms) and 2^17 for G2
-  // (5.7 ms), the whole table when it is smaller (GS_TABLE_BG_SLAB_LOG2 caps the G1 figure).  Measured on fresh keys
-  // (profiles/r06_auto_instalments.txt): with slabs of n / 8 points a 2^16 key's tables took 75 ms of instalments instead of 9, and
-  // 2^17-point G1 slabs cost a 2^20 key 168 ms against the 130 ms `always` spends in 2^18-point launches.
-  static const size_t cap = (size_t)1 << run_knob("GS_TABLE_BG_SLAB_LOG2", 18, 10, 18);
-  return std::min(g2 ? std::max<size_t>(cap / 2, (size_t)1 << 12) : cap, std::max<size_t>(n, 1));
-}
-// all streams of the context wait for the table's last slab (accumulations run on the main stream, where the slabs are: this is for
-// whatever else may come to read a table)
-static void order_streams_behind(Ctx& c, hipEvent_t ev) {
-  for (auto a : c.aux_stream) if (a && a != c.main_stream) GS_HIP(hipStreamWaitEvent(a, ev, 0));
-}
-
-void table_settle(Ctx& c, BaseTable& t, bool install) {
-  if (!t.pending.p) return;
-  if (install && !t.pending_complete()) {              // finish the missing instalments now (gs_build_tables on a key that was warming up)
-    const size_t slab = (size_t)1 << 18;
-    if (t.pending_g2) enqueue_pending_slabs<Fq2Tag>(c, t, t.pending_next, t.pending_n, slab);
-    else enqueue_pending_slabs<FqTag>(c, t, t.pending_next, t.pending_n, slab);
-    t.pending_next = t.pending_n;
-    GS_HIP(hipEventRecord(t.pending_done, c.main_stream));
-  }
-  // this table's own build only
-  if (t.pending_done && t.pending_next > 0) GS_HIP(hipEventSynchronize(t.pending_done));
-  else if (t.pending_next > 0) GS_HIP(hipStreamSynchronize(c.main_stream));
-  if (install) {
-    t.rows = std::move(t.pending);
-    t.n = t.pending_n; t.c = t.pending_c; t.W = 254 / t.pending_c + 1;
-    t.uses = 0;
-  } else t.pending.release();
-  t.pending_c = 0; t.pending_n = 0; t.pending_next = 0; t.pending_src = nullptr;
-}
-
-// install a table whose last slab has been ENQUEUED (not necessarily executed): everything that reads it is ordered behind the slab
-static void install_enqueued(Ctx& c, BaseTable& t) {
-  if (hipEventQuery(t.pending_done) != hipSuccess) order_streams_behind(c, t.pending_done);
-  (void)hipGetLastError();                                                     // hipErrorNotReady is not an error
-  // (the old rows, if any, are released by the move: hipFree waits for the device, i.e. for every reader of them)
-  t.rows = std::move(t.pending);
-  t.n = t.pending_n; t.c = t.pending_c; t.W = 254 / t.pending_c + 1;
-  t.uses = 0;
-  t.pending_c = 0; t.pending_n = 0; t.pending_next = 0; t.pending_src = nullptr;
-}
-
-static bool begin_pending(Ctx& c, BaseTable& t, const TableRef& r, int cbits) {
-  if (!t.pending_done) GS_HIP(hipEventCreateWithFlags(&t.pending_done, hipEventDisableTiming));
-  const int W = 254 / cbits + 1;
-  const size_t aw = r.g2 ? PointIO<Fq2Tag>::kAffineWords : PointIO<FqTag>::kAffineWords;
-  try {
-    // the slab scratch at its G2 size BEFORE the first launch: growing it later releases the old buffer, and hipFree waits for the
-    // device -- for the slabs just enqueued (round 5: that, not the builds' share of the chip, was most of a second proof's 88 ms)
-    constexpr size_t sw2 = PointIO<Fq2Tag>::kXyzzWords + PointIO<Fq2Tag>::kXyzzWords / 4;
-    if (W > 2) {      // (a G1 slab may be twice a G2 slab's points, and a G1 point's scratch is half a G2 point's: the same bytes)
-      constexpr size_t sw1 = PointIO<FqTag>::kXyzzWords + PointIO<FqTag>::kXyzzWords / 4;
-      const size_t s2 = instalment_slab(r.n, true), s1 = instalment_slab(r.n, false);
-      const size_t bytes = std::max((s2 + s2 / 4) * sw2, (s1 + s1 / 4) * sw1);
-      msm_state(c).table_scratch_bg.ensure(bytes * (size_t)(W - 1) * 4);
-    }
-    t.pending.alloc(std::max<size_t>(r.n, 1) * W * aw * 4);
-  } catch (const HipError& e) {
-    if (e.e != hipErrorOutOfMemory) throw;      // no room for a table: keep summing table-free
-    t.pending.release();
-    return false;
-  }
-  t.pending_c = cbits; t.pending_n = r.n; t.pending_next = 0; t.pending_src = r.row0; t.pending_g2 = r.g2;
-  return true;
-}
-
-// spend credit on the next slabs of t's pending table; true when the last slab has been enqueued
-static bool advance_pending(Ctx& c, BaseTable& t, double& credit) {
-  const double unit = t.pending_g2 ? kG2BuildCost : 1.0;
-  const size_t slab = instalment_slab(t.pending_n, t.pending_g2);
-  for (;;) {
-    if (t.pending_next >= t.pending_n) break;
-    // (a remainder of up to a quarter slab rides with the last one: a key of 2^k + 1 variables must not end on a one-point launch)
-    const size_t last = t.pending_n - t.pending_next <= slab + slab / 4 ? t.pending_n : t.pending_next + slab;
-    // a slab is bought when the credit covers at least half of it (the call overdraws by at most half a slab, ~2.5 ms at 2^20, and the
-    // next call's grant is that much smaller): the instalments of consecutive calls then differ by one slab at most
-    if (credit < 0.5 * (double)(last - t.pending_next) * unit) break;
-    if (t.pending_g2) enqueue_pending_slabs<Fq2Tag>(c, t, t.pending_next, last, last - t.pending_next);
-    else enqueue_pending_slabs<FqTag>(c, t, t.pending_next, last, last - t.pending_next);
-    credit -= (double)(last - t.pending_next) * unit;
-    t.pending_next = last;
-  }
-  if (t.pending_next < t.pending_n) return false;
-  GS_HIP(hipEventRecord(t.pending_done, c.main_stream));
-  return true;
-}
-
-void stamp_tables(Ctx& c, const std::vector<BaseTable*>& tables) {
-  for (BaseTable* t : tables) if (t) t->last_use = c.call_clock;
-}
-
-bool prepare_tables(Ctx& c, const std::vector<TableRef>& group, uint32_t nterms, int* cbits, double* credit) {
-  int cb = choose_window_bits(std::max<uint32_t>(nterms, 1u), c.window_bits);
-  // A group whose tables are all resident at ONE width next to the model's serves at that width (gs_build_tables sizes a
-  // key's tables for the arrays it holds, a proof asks for the width of its term range -- near a boundary of the model the warmed
-  // table was silently ignored or rebuilt, and callers alternating two MSM lengths over one array flip-flopped it).
-  if (c.window_bits == 0 && !group.empty() && group[0].t->rows.p) {
-    const int tc = group[0].t->c;
-    bool same = tc >= cb - 1 && tc <= cb + 1;
-    for (const TableRef& r : group) same = same && r.t->ready(r.n, tc);
-    if (same) cb = tc;
-  }
-  bool all_ready = true;
-  for (const TableRef& r : group) {
-    r.t->last_use = c.call_clock;
-    all_ready = all_ready && r.t->ready(r.n, cb);
-  }
-  if (all_ready) {
-    for (const TableRef& r : group) r.t->last_table_use = c.call_clock;
-    *cbits = cb;
-    return true;
-  }
-  if (c.table_policy == 1) {                                                   // always: inside the call, as rounds 1-4 did
-    for (const TableRef& r : group) {
-      if (r.g2) ensure_table_g2(c, *r.t, r.row0, r.n, cb); else ensure_table_g1(c, *r.t, r.row0, r.n, cb);
-      r.t->last_table_use = c.call_clock;
-    }
-    *cbits = cb;
-    return true;
-  }
-  if (c.table_policy == 0) {
-    static const double scale = (double)run_knob("GS_TABLE_BUDGET_PCT", 100, 1, 1000000) / 100.0;
-    // what this call may still enqueue: its grant (what an earlier group of the same call left of it) minus the last call's overdraft
-    const double grant = credit ? *credit : 0.0;
-    double avail = grant * scale + c.build_balance;
-    // G2 arrays first: the G2 sum is the longest of a proof, so its table is the one that pays most per call
-    std::vector<const TableRef*> order;
-    for (const TableRef& r : group) if (r.g2) order.push_back(&r);
-    for (const TableRef& r : group) if (!r.g2) order.push_back(&r);
-    for (const TableRef* pr : order) {
-      const TableRef& r = *pr;
-      BaseTable& t = *r.t;
-      if (t.ready(r.n, cb)) continue;
-      if (t.pending.p && (t.pending_c != cb || t.pending_n != r.n || t.pending_src != r.row0)) table_settle(c, t, false);   // superseded
-      if (!t.pending.p) {
-        t.uses += 1;
-        // a table of another width that still serves other calls stays (callers alternating two lengths over one array)
-        const bool serving = t.rows.p && c.call_clock - t.last_table_use <= 8;
-        if (t.uses < kTableAfterUses || !r.n || serving) continue;
-        if (!begin_pending(c, t, r, cb)) continue;
-      }
-      if (advance_pending(c, t, avail)) install_enqueued(c, t);
-    }
-    c.build_balance = std::min(avail, 0.0);                       // an overdraft (less than one slab) comes off the next call's grant
-    if (credit) *credit = std::max(avail, 0.0) / scale;           // the rest of the grant is the call's next group's
-    bool now_ready = true;
-    for (const TableRef& r : group) now_ready = now_ready && r.t->ready(r.n, cb);
-    if (now_ready) {                                              // this call enqueued the last slab: it is the first to use the tables
-      for (const TableRef& r : group) r.t->last_table_use = c.call_clock;
-      *cbits = cb;
-      return true;
-    }
-  }
-  *cbits = choose_window_bits_free(std::max<uint32_t>(nterms, 1u), c.window_bits);
-  return false;
 }
 
 template <class T>
@@ -785,6 +551,5 @@ Xyzz<T> HostFixedBase<T>::mul(const uint64_t k[4]) const {
 }
 template struct HostFixedBase<FqTag>;
 template struct HostFixedBase<Fq2Tag>;
-
 
 }  // namespace gs

@@ -8,8 +8,6 @@
 
 namespace gs {
 
-static inline dim3 grid1(size_t n, int block = 256) { return dim3((unsigned)((n + block - 1) / block)); }
-
 int ceil_log2(size_t n) {
   int l = 0;
   while (((size_t)1 << l) < n) ++l;
@@ -197,7 +195,6 @@ static void copy_padded(Ctx& c, const uint32_t* src, size_t n, uint32_t* dst, si
   GS_HIP(hipMemcpyAsync(dst, src, n * 32, hipMemcpyDeviceToDevice, c.stream));
   if (total > n) GS_HIP(hipMemsetAsync(dst + n * 8, 0, (total - n) * 32, c.stream));
 }
-
 
 void poly_mul_dev(Ctx& c, const uint32_t* a, size_t na, Form fa, const uint32_t* b, size_t nb, Form fb, uint32_t* out) {
   if (na == 0 || nb == 0) return;

@@ -235,7 +235,7 @@ int proof_enqueue(Ctx& c, ProverKey* pk, DevScalars w, DevScalars px, const Shar
   } else shard_range(nh, shard, hlo, hhi);
   const size_t held_lo = eval ? pk->e_lo : pk->h_lo;
   const size_t wbase = wlo - pk->w_lo, hbase = hlo - std::min(held_lo, hlo);      // offsets into the arrays this key holds
-  // window tables or table-free, per plan (msm.h, prepare_tables: the arrays over w share one plan, so they go one way together)
+  // window tables or table-free, per plan (tables.h, prepare_tables: the arrays over w share one plan, so they go one way together)
   // (before any table instalment goes onto the main stream: the plans on the aux streams wait for the inputs, not for the slabs)
   if (wait_inputs) {
     hipEvent_t start;
@@ -250,7 +250,7 @@ int proof_enqueue(Ctx& c, ProverKey* pk, DevScalars w, DevScalars px, const Shar
   const size_t n_harr = eval ? pk->n_e : quot ? pk->n_q : pk->n_h;
   // every table of the call is stamped before one is built (an allocation for the first group must not evict the second group's), and
   // under policy `auto` the call grants itself a build credit for its job-units over w and h (a G1 sum = 1, the G2 sum = 2.76: ~6.8
-  // for a Groth16 proof; msm.h, prepare_tables)
+  // for a Groth16 proof; tables.h, prepare_tables)
   std::vector<BaseTable*> stamps;
   std::vector<TableRef> refs_w;
   for (int i = 0; i < ng; ++i) {

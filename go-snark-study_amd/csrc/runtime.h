@@ -129,10 +129,11 @@ struct Object {
   explicit Object(Kind k) : kind(k) {}
 };
 
+struct BaseTable;                 // tables.h
 struct Bases : Object {          // packed affine Montgomery points, resident (+ their lazily built window table)
   DevBuf buf;
   size_t n = 0;
-  std::shared_ptr<void> table;   // gs::BaseTable (msm.h), created on first MSM use
+  std::shared_ptr<BaseTable> table;   // created on first MSM use (tables.h, table_of)
   explicit Bases(Kind k) : Object(k) {}
 };
 struct R1csObj : Object {        // sparse R1CS resident on the device: A, B, C in CSR (values standard form) + per-proof workspaces
@@ -273,12 +274,11 @@ struct Ctx {
                                  // order for evict_tables_for; a table stamped with the running call's tick is never its victim)
   uint64_t evictions = 0;        // window tables dropped by evict_tables_for so far
   int window_bits = 0;           // 0 = auto
-  // gs_set_table_policy -- when a base array gets its 15-row window table (msm.h, prepare_tables): 0 auto (sum table-free until the
-  // array has been used twice, then build in the background and switch when the build is through), 1 always (build on first use,
-  // inside the call: rounds 1-4), 2 never
+  // gs_set_table_policy -- when a base array gets its 15-row window table (tables.h, prepare_tables): 0 auto (sum table-free until the
+  // array has been used twice, then build in instalments and switch with the call that enqueues the last one), 1 always (build on
+  // first use, inside the call: rounds 1-4), 2 never
   int table_policy = 0;
-  hipStream_t table_stream = nullptr;   // (round 5: background table builds; round 6 builds in instalments on the main stream, msm.hip)
-  double build_balance = 0;             // build credit a call overdrew (less than one slab): taken off the next call's (msm.hip, prepare_tables)
+  double build_balance = 0;             // build credit a call overdrew (less than one slab): taken off the next call's (tables.hip, prepare_tables)
   bool eval_basis = true;        // gs_set_eval_basis: witness route over H's values when the key has an evaluation-basis array
   gs_timing timing{};
   std::mutex timing_mu;          // msm_finish of several groups may run on different host threads
@@ -287,7 +287,7 @@ struct Ctx {
   DevBuf ws_buckets[kWsSets], ws_chunks[kWsSets], ws_partials[kWsSets], ws_out[kWsSets];
   // per-context state of the engines (plan buffers, NTT twiddles, node trees, staging buffers): device memory belongs to
   // one device, so nothing of this may be a process-wide static
-  std::shared_ptr<void> msm_state, poly_state, prove_state;
+  std::shared_ptr<void> msm_state, poly_state, prove_state, table_state;
   DevBuf ws_misc;
   DevBuf g1_pow2, g2_pow2;       // fixed-base window tables d * 2^(8 w) * G, 32 x 256 entries (lazy)
   std::vector<hipEvent_t> events;
@@ -468,6 +468,9 @@ inline void copy_between(Ctx& dst, void* d, const Ctx& src, const void* s, size_
   if (dst.device == src.device) GS_HIP(hipMemcpyAsync(d, s, bytes, hipMemcpyDeviceToDevice, dst.stream));
   else GS_HIP(hipMemcpyPeerAsync(d, dst.device, s, src.device, bytes, dst.stream));
 }
+
+// one-dimensional launch grid for n threads
+inline dim3 grid1(size_t n, int block = 256) { return dim3((unsigned)((n + block - 1) / block)); }
 
 // run a section of engine calls on another stream of the context
 struct StreamScope {

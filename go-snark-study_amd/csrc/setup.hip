@@ -398,8 +398,7 @@ static int pk_set_eval_impl(Ctx& c, const char* fn, Kind kind, const char* slice
   const size_t n = b->n;
   if (n < 2 || pk->nz == 0 || (pk->nz - 1 != n - 1 && pk->nz - 1 != n))
     return fail(GS_ERR_SHAPE, "%s: %zu points, but deg Z = %zu needs n = deg Z or deg Z + 1 constraints", fn, n, pk->nz ? pk->nz - 1 : 0);
-  table_settle(c, pk->h_eval.table, false);
-  pk->h_eval.table.drop();
+  pk->h_eval.table.invalidate();
   pk->h_eval.pts.alloc(n * 64);
   GS_HIP(hipMemcpyAsync(pk->h_eval.pts.p, b->buf.p, n * 64, hipMemcpyDeviceToDevice, c.stream));
   GS_HIP(hipStreamSynchronize(c.stream));
@@ -420,8 +419,7 @@ int gs_groth16_pk_set_eval_domain(gs_handle hpk, gs_handle hbases, size_t log2_d
     const size_t n = (size_t)1 << log2_domain;
     if (b->n != n) return fail(GS_ERR_SHAPE, "%s: %zu points, the domain has %zu", fn, b->n, n);
     c.drain();                                  // an outstanding ticket may read the array that goes
-    table_settle(c, pk->h_eval.table, false);
-    pk->h_eval.table.drop();
+    pk->h_eval.table.invalidate();
     pk->n_eval = 0; pk->n_e = 0;
     pk->h_eval.pts.alloc(n * 64);
     GS_HIP(hipMemcpyAsync(pk->h_eval.pts.p, b->buf.p, n * 64, hipMemcpyDeviceToDevice, c.stream));
@@ -449,8 +447,7 @@ static int pk_set_quot_impl(Ctx& c, const char* fn, Kind kind, gs_handle hpk, gs
   if (pk->shard_count != 1) return fail(GS_ERR_ARG, "%s: the key is a slice (key slices carry no quotient-basis array)", fn);
   if (b && (b->n == 0 || b->n != pk->len_h)) return fail(GS_ERR_SHAPE, "%s: %zu points, but the key's h array has %zu", fn, b->n, pk->len_h);
   c.drain();                                  // an outstanding ticket may read the array that goes
-  table_settle(c, pk->h_quot.table, false);
-  pk->h_quot.table.drop();
+  pk->h_quot.table.invalidate();
   pk->n_q = 0;
   if (!b) { pk->h_quot.pts.release(); return GS_OK; }
   pk->h_quot.pts.alloc(b->n * 64);
