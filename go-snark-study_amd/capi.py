@@ -80,6 +80,11 @@ _SIGS = {
                               ctypes.POINTER(Handle)],
     "gs_groth16_pk_derive_eval_domain": [Handle, ctypes.c_size_t],
     "gs_groth16_pk_set_eval_domain": [Handle, Handle, ctypes.c_size_t],
+    "gs_g1_upload_affine_mont": [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(Handle)],
+    "gs_g2_upload_affine_mont": [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(Handle)],
+    "gs_r1cs_upload_zkey": [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(Handle)],
+    "gs_groth16_pk_create_domain": [Handle, Handle, Handle, Handle, Handle, u64p, u64p, u64p, u64p, u64p,
+                                    ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(Handle)],
     "gs_groth16_pk_create": [Handle, Handle, Handle, Handle, Handle, u64p, u64p, u64p, u64p, u64p,
                              u64p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(Handle)],
     "gs_groth16_prove": [Handle, u64p, ctypes.c_size_t, u64p, ctypes.c_size_t, u64p, u64p, u64p, intp],
@@ -467,6 +472,31 @@ def g1_upload(points_u64):
 
 def g2_upload(points_u64):
     return _upload("gs_g2_upload", points_u64, 24)
+
+
+def byte_ptr(buf):
+    """A uint8 array of any alignment, writable or not (a memory-mapped file section) -> (void pointer, the array that keeps it alive)."""
+    a = np.ascontiguousarray(buf).reshape(-1).view(np.uint8)
+    return ctypes.c_void_p(a.ctypes.data if a.size else None), a
+
+
+def _upload_affine_mont(name, buf, point_bytes):
+    init()
+    p, a = byte_ptr(buf)
+    if a.size % point_bytes:
+        raise ValueError("%s: %d bytes are not a whole number of %d-byte points" % (name, a.size, point_bytes))
+    cell = HandleCell()
+    call(name, p, a.size // point_bytes, cell.ref)
+    return cell.result()
+
+
+def g1_upload_affine_mont(buf):
+    """gs_g1_upload_affine_mont: n x 64 bytes as a snarkjs .zkey holds G1 points -> a base-array handle."""
+    return _upload_affine_mont("gs_g1_upload_affine_mont", buf, 64)
+
+
+def g2_upload_affine_mont(buf):
+    return _upload_affine_mont("gs_g2_upload_affine_mont", buf, 128)
 
 
 def scalars_upload(s_u64):

@@ -50,11 +50,14 @@ void gs::r1cs_values_dev(Ctx& c, R1csObj& o, const uint32_t* w_dev) {
   o.w_mont.ensure(m * 32); o.vals.ensure(3 * np * 32);
   GS_HIP(hipMemcpyAsync(o.w_mont.p, w_dev, m * 32, hipMemcpyDeviceToDevice, c.stream));
   poly_canon_dev(c, o.w_mont.as<uint32_t>(), m, 1);                                         // w -> Montgomery
-  for (int k = 0; k < 3; ++k) {
+  for (int k = 0; k < (o.product ? 2 : 3); ++k) {
     uint32_t* out = o.vals.as<uint32_t>() + k * np * 8;
     spmv_dev(c, o.rowptr[k].as<uint32_t>(), o.col[k].as<uint32_t>(), o.val[k].as<uint32_t>(), o.w_mont.as<uint32_t>(), n, m, out);
     if (np > n) GS_HIP(hipMemsetAsync(out + n * 8, 0, (np - n) * 32, c.stream));
   }
+  // a product system: [A w | B w | a o b], the third vector by one point-wise kernel (not fused into the first transform pass: that
+  // pass is shared with every other caller of ntt_forward_n, and the vector is 32 B per point against the three transforms' 6 passes)
+  if (o.product) r1cs_product_dev(c, o.vals.as<uint32_t>(), np);
 }
 
 // w -> o.coef = [ax | bx | cx] (o.points() each) and px_out (o.npx()), canonical standard form

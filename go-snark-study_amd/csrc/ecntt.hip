@@ -167,6 +167,7 @@ int pk_derive_quot_impl(Ctx& c, const char* fn, Kind kind, gs_handle hpk) {
   ProverKey* pk = c.get<ProverKey>(hpk, kind);
   if (!pk) return fail(GS_ERR_ARG, "%s: bad proving-key handle", fn);
   if (pk->shard_count != 1) return fail(GS_ERR_ARG, "%s: the key is a slice (key slices carry no quotient-basis array)", fn);
+  if (pk->coset_only) return refuse_coset_only(fn);
   const size_t n = pk->len_h;
   if (n == 0 || pk->nz == 0) return fail(GS_ERR_SHAPE, "%s: the key has no h array or no Z", fn);
   const int logn = ceil_log2(2 * n - 1);
@@ -220,6 +221,7 @@ int pk_derive_eval_impl(Ctx& c, const char* fn, Kind kind, gs_handle hpk, size_t
   ProverKey* pk = c.get<ProverKey>(hpk, kind);
   if (!pk) return fail(GS_ERR_ARG, "%s: bad proving-key handle", fn);
   if (pk->shard_count != 1) return fail(GS_ERR_ARG, "%s: the key is a slice (derive the array on the full key, then cut it)", fn);
+  if (pk->coset_only) return refuse_coset_only(fn);
   if (pk->len_h == 0 || pk->nz == 0) return fail(GS_ERR_SHAPE, "%s: the key has no h array or no Z", fn);
   if (n < 2 || n > pk->len_h || (pk->nz - 1 != n - 1 && pk->nz - 1 != n))
     return fail(GS_ERR_SHAPE, "%s: n = %zu, but deg Z = %zu needs n = deg Z or deg Z + 1 constraints (at least 2, at most the %zu points of the h array)", fn, n,
@@ -284,6 +286,7 @@ int pk_derive_eval_domain_impl(Ctx& c, gs_handle hpk, size_t log2_domain) {
   GrothPkObj* pk = c.get<GrothPkObj>(hpk, Kind::GrothPk);
   if (!pk) return fail(GS_ERR_ARG, "%s: bad proving-key handle", fn);
   if (pk->shard_count != 1) return fail(GS_ERR_ARG, "%s: the key is a slice", fn);
+  if (pk->coset_only) return refuse_coset_only(fn);
   if (log2_domain < 1 || pk->domain_log2 == 0 || (size_t)pk->domain_log2 != log2_domain)
     return fail(GS_ERR_SHAPE, "%s: the key's Z (%zu coefficients) is not x^(2^%zu) - 1", fn, pk->nz, log2_domain);
   const int k = (int)log2_domain;

@@ -451,6 +451,30 @@ static uint32_t upload_jacobian(Ctx& c, const uint64_t* jac_host, uint32_t n, ui
 }
 uint32_t upload_jacobian_g1(Ctx& c, const uint64_t* jac_host, uint32_t n, uint32_t* out, uint32_t* first_bad) { return upload_jacobian<FqTag>(c, jac_host, n, out, first_bad); }
 uint32_t upload_jacobian_g2(Ctx& c, const uint64_t* jac_host, uint32_t n, uint32_t* out, uint32_t* first_bad) { return upload_jacobian<Fq2Tag>(c, jac_host, n, out, first_bad); }
+// gs_g1_upload_affine_mont / gs_g2_upload_affine_mont: the same path for points that are affine and in Montgomery form already (a
+// .zkey section as it lies in the file): staged copy, one conversion kernel, the same flag words.
+template <class T>
+static uint32_t upload_affine_mont(Ctx& c, const void* bytes_host, uint32_t n, uint32_t* out, uint32_t* first_bad) {
+  if (!n) return 0;
+  const size_t bytes = (size_t)n * PointIO<T>::kAffineWords * 4;
+  DevBuf once;
+  DevBuf& scratch = bytes <= kUploadScratchKeep ? msm_state(c).upload_scratch : once;
+  scratch.ensure(bytes);
+  staged_h2d(c, scratch.p, bytes_host, bytes, c.stream);
+  DevBuf& flag = msm_state(c).upload_flag;
+  flag.ensure(8);
+  const uint32_t init[2] = {0u, 0xffffffffu};
+  GS_HIP(hipMemcpyAsync(flag.p, init, 8, hipMemcpyHostToDevice, c.stream));
+  hipLaunchKernelGGL(k_affine_mont_to_affine<T>, grid1(n), dim3(256), 0, c.stream, scratch.as<uint32_t>(), n, out, flag.as<uint32_t>());
+  GS_HIP(hipGetLastError());
+  uint32_t res[2] = {0, 0};
+  GS_HIP(hipMemcpyAsync(res, flag.p, 8, hipMemcpyDeviceToHost, c.stream));
+  GS_HIP(hipStreamSynchronize(c.stream));                // `once` may go
+  if (first_bad) *first_bad = res[1];
+  return res[0];
+}
+uint32_t upload_affine_mont_g1(Ctx& c, const void* b, uint32_t n, uint32_t* out, uint32_t* first_bad) { return upload_affine_mont<FqTag>(c, b, n, out, first_bad); }
+uint32_t upload_affine_mont_g2(Ctx& c, const void* b, uint32_t n, uint32_t* out, uint32_t* first_bad) { return upload_affine_mont<Fq2Tag>(c, b, n, out, first_bad); }
 uint32_t jacobian_to_affine_g1(Ctx& c, const uint32_t* jac, uint32_t n, uint32_t* out, uint32_t* first_bad) {
   return jacobian_to_affine_checked<FqTag>(c, jac, n, out, first_bad);
 }

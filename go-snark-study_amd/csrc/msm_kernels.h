@@ -28,6 +28,7 @@
 
 #include "ec.h"
 #include "point_io.h"
+#include "zkey_convert.h"
 
 namespace gs {
 
@@ -779,6 +780,42 @@ __global__ void __launch_bounds__(256) k_jacobian_to_affine(const uint32_t* __re
     atomicMin(off_curve + 1, i);
   }
   PointIO<T>::store_affine(out + (size_t)i * PointIO<T>::kAffineWords, a);
+}
+
+// Affine points as a snarkjs .zkey holds them (x | y, every base-field coordinate 8 words of value * 2^256 mod q, all-zero words =
+// the point at infinity) -> packed canonical Montgomery affine: one product by a constant per coordinate (zkey_convert.h).
+// A coordinate >= q and a point off its curve are counted and located like k_jacobian_to_affine's (bad[0], bad[1]).
+template <class T>
+__global__ void __launch_bounds__(256) k_affine_mont_to_affine(const uint32_t* __restrict__ in, uint32_t n, uint32_t* __restrict__ out,
+                                                                uint32_t* __restrict__ bad) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  constexpr int nc = PointIO<T>::kAffineWords / 8;          // base-field coordinates per point: 2 (G1) or 4 (G2), in the packed order
+  const uint32_t* p = in + (size_t)i * nc * 8;
+  uint32_t* o = out + (size_t)i * nc * 8;
+  bool all_zero = true, in_range = true;
+  Fe<ModQ, 1> c[nc];
+#pragma unroll
+  for (int k = 0; k < nc; ++k) {
+    uint32_t w[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { w[j] = p[k * 8 + j]; all_zero = all_zero && w[j] == 0u; }
+    in_range = in_range && zkey_words_below<ModQ>(w);
+    c[k] = zkey_coord_to_engine(w);
+  }
+  if (all_zero) {                                           // the engine's infinity is all-zero words too (is_inf)
+#pragma unroll
+    for (int j = 0; j < nc * 8; ++j) o[j] = 0u;
+    return;
+  }
+  Affine<T> a;
+  if constexpr (nc == 2) { a.x = c[0]; a.y = c[1]; }
+  else { a.x.c0 = c[0]; a.x.c1 = c[1]; a.y.c0 = c[2]; a.y.c1 = c[3]; }
+  if (!in_range || !on_curve(a)) {
+    atomicAdd(bad, 1u);
+    atomicMin(bad + 1, i);
+  }
+  PointIO<T>::store_affine(o, a);
 }
 
 // packed affine -> standard-form Jacobian triple [x, y, 1] / [0, 0, 0]

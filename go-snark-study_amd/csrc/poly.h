@@ -66,6 +66,8 @@ bool hx_direct_dev(Ctx& c, const uint32_t* vals_std, size_t n, size_t dz, uint32
 // it collects the proof, and takes the exact route if it is not zero); hx_from_values_dev: values -> coefficients.
 bool hx_values_dev(Ctx& c, const uint32_t* vals_std, size_t n, size_t dz, uint32_t* hv_out_std);
 void r1cs_check_dev(Ctx& c, const uint32_t* vals_std, size_t n, size_t dz, uint32_t* bad_dev);
+// r1cs_product_dev: the third vector of vals = [a | b | .] (n each) becomes a_j b_j -- a product system has no C matrix (enqueue only)
+void r1cs_product_dev(Ctx& c, uint32_t* vals_std, size_t n);
 void hx_from_values_dev(Ctx& c, const uint32_t* hv_std, size_t n, size_t dz, uint32_t* hx_out_std);
 // The same stage for a QAP over the power-of-two domain 2^k (domain.h; snarkjs / circom keys).  vals: [A w | B w | C w], m = 2^k each
 // (rows past the last constraint zero), standard form, natural order.  All three work IN PLACE on vals:

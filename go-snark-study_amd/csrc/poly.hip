@@ -545,6 +545,14 @@ void r1cs_check_dev(Ctx& c, const uint32_t* vals_std, size_t n, size_t dz, uint3
   GS_HIP(hipGetLastError());
 }
 
+// vals = [a | b | .] (n each, standard form): the third vector becomes a_j b_j.  Enqueue only.
+void r1cs_product_dev(Ctx& c, uint32_t* vals_std, size_t n) {
+  Fe<ModR, 1> r2;
+  for (int i = 0; i < NL; ++i) r2.l[i] = ModR::r2(i);
+  if (n) hipLaunchKernelGGL(k_r1cs_product, grid1(n), dim3(256), 0, c.stream, vals_std, (uint32_t)n, to_const(relax<2>(r2)));
+  GS_HIP(hipGetLastError());
+}
+
 // hv[k - 1] = H(n + k), k = 1..n (canonical standard form): the values of A, B, C at the nodes n+1..2n by three cyclic
 // convolutions with 1 / (t + 1) (batched), then (a b - c) / Z point-wise.  No host wait once the tables of (n, dz) exist.
 bool hx_values_dev(Ctx& c, const uint32_t* vals_std, size_t n, size_t dz, uint32_t* hv_out) {

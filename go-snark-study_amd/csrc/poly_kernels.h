@@ -717,6 +717,14 @@ __global__ void __launch_bounds__(256) k_r1cs_check(const uint32_t* __restrict__
   const Fr2 ab = mul(mul(load_fr(vals + (size_t)j * 8), load_fr(vals + ((size_t)n + j) * 8)), from_const(r2));      // standard a b
   if (!is_zero(sub(ab, load_fr(vals + ((size_t)2 * n + j) * 8)))) atomicAdd(bad, 1u);
 }
+// c_j = a_j b_j for j < n from vals = [a | b | .] (n each, standard form) into the third vector, standard form: the C side of a
+// product system (an R1CS that holds no C matrix: snarkjs .zkey keys)
+__global__ void __launch_bounds__(256) k_r1cs_product(uint32_t* __restrict__ vals, uint32_t n, const FrConst r2) {
+  wave_priority<GS_PRIO_POLY>();
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  store_fr(vals + ((size_t)2 * n + j) * 8, mul(mul(load_fr(vals + (size_t)j * 8), load_fr(vals + ((size_t)n + j) * 8)), from_const(r2)));
+}
 // Taylor shift, step 1: p[i'] = g[n-1-i'] (n-1-i')! for i' < n, zero padded to N
 __global__ void __launch_bounds__(256) k_hx_shift_in(const uint32_t* __restrict__ g, const uint32_t* __restrict__ fact, uint32_t n, uint32_t N, uint32_t* __restrict__ p) {
   wave_priority<GS_PRIO_POLY>();

@@ -43,6 +43,10 @@ struct ProverKey : Object {
   // eval_domain_log2 says which basis h_eval holds: 0 = the Lagrange basis over the nodes n+1 .. 2n above, k = the coset
   // evaluation basis of the domain 2^k (m points, natural order).  The evaluation-basis route is taken only when it matches the R1CS.
   int domain_log2 = 0, eval_domain_log2 = 0;
+  // A coset-only key (gs_groth16_pk_create_domain; what a snarkjs .zkey holds): domain_log2 = eval_domain_log2 = k, h_eval = the m coset
+  // points, and NO monomial h array (len_h = n_h = 0, h.pts empty).  It proves from a witness on the evaluation-basis route and
+  // nowhere else: whatever needs h -- the px routes, the derivations, the quotient basis, key slices -- refuses it (refuse_coset_only).
+  bool coset_only = false;
   // Quotient-basis twin of h (optional; the setups build it, gs_*_pk_set_quot attaches one): with D = deg Z and g = 1 / rev(Z) as a
   // power series (z.inv_rev_mont),  h_quot[m] = sum_{d <= m} g_d h[m - d],  m < n_q = len_h.  floor(x^i / Z) = sum_d g_d x^(i-D-d), so
   // for every px with nh = len(px) - D >= 1 coefficients of floor(px / Z):
@@ -84,6 +88,10 @@ struct ProverKey : Object {
 };
 inline ProverKey* as_prover_key(Object* o) {
   return o && (o->kind == Kind::GrothPk || o->kind == Kind::PinocchioPk) ? static_cast<ProverKey*>(o) : nullptr;
+}
+inline int refuse_coset_only(const char* fn) {
+  return fail(GS_ERR_SHAPE, "%s: the key holds the coset evaluation basis only (it has no monomial h array): it proves from a witness "
+              "with a domain R1CS on the evaluation-basis route, and nothing else", fn);
 }
 void pk_scan_sparsity(Ctx& c, ProverKey& pk);      // fills b_index / b_finite (synchronises the stream)
 

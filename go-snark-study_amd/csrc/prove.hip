@@ -216,6 +216,7 @@ int proof_enqueue(Ctx& c, ProverKey* pk, DevScalars w, DevScalars px, const Shar
   DevBuf& hxbuf = prove_state(c).hx[parity];
   if (w.n != pk->nvars) return fail(GS_ERR_SHAPE, "len(w) = %zu but the key has %zu variables", w.n, pk->nvars);
   const bool eval = (bool)px.produce_hv || px.hv_slice;   // h-MSM over H's values against the evaluation-basis table (the caller checked the key has one)
+  if (!eval && pk->coset_only) return refuse_coset_only(pk->kind == Kind::GrothPk ? "gs_groth16_prove" : "gs_pinocchio_prove");   // every px route ends up here
   const size_t nh = eval ? pk->n_eval : quotient_len(px.n, pk->nz);
   if (!eval && nh > pk->len_h) return fail(GS_ERR_SHAPE, pk->hx_too_long, nh, pk->len_h);
   const bool sliced = pk->shard_count > 1;
@@ -657,7 +658,7 @@ int check_domain_pair(const char* fn, const ProverKey* pk, const R1csObj* o) {
   if (pk->shard_count != 1) return fail(GS_ERR_SHAPE, "%s: an R1CS over a power-of-two domain proves with a full key, not with a key slice", fn);
   if (pk->domain_log2 != k)
     return fail(GS_ERR_SHAPE, "%s: the R1CS lives on the domain of 2^%d points, but the key's Z (%zu coefficients) is not x^(2^%d) - 1", fn, k, pk->nz, k);
-  if (pk->len_h + 1 < ((size_t)1 << k))
+  if (!pk->coset_only && pk->len_h + 1 < ((size_t)1 << k))      // (a coset-only key needs no h array: prove.h)
     return fail(GS_ERR_SHAPE, "%s: the key's h array has %zu points, H needs 2^%d - 1", fn, pk->len_h, k);
   return GS_OK;
 }
@@ -668,17 +669,26 @@ bool eval_route(const Ctx& c, const ProverKey* pk, const R1csObj* o) {
   return pk->eval_domain_log2 == 0 && pk->n_eval == o->n && hx_shape(o->n, pk->nz);
 }
 
+// a coset-only key (prove.h) has one route: refuse the call when that route is not open (another kind of R1CS, gs_set_eval_basis(0))
+int check_coset_only_route(const Ctx& c, const char* fn, const ProverKey* pk, const R1csObj* o) {
+  return pk->coset_only && !eval_route(c, pk, o) ? refuse_coset_only(fn) : GS_OK;
+}
+
 // the three ways to the h-scalars of a witness proof, in the order the prover tries them (a domain R1CS has two: the coset
 // evaluation-basis route, then px -- its quotient by x^m - 1 goes through the key's Divisor / quotient-basis array like any Z)
-DevScalars witness_scalars(R1csObj* o, const uint32_t* wdev, size_t nz, bool eval, std::function<uint32_t*(Ctx&)> px_buffer) {
+// `check`: count the violated constraints, so that the proof can be redone on the exact route.  Off for a product system (c = a b by
+// definition: nothing to check) and for a coset-only key (no exact route to go to): the count is 0, and a wrong witness gives a proof
+// that the verifier rejects, as in snarkjs.
+DevScalars witness_scalars(R1csObj* o, const uint32_t* wdev, size_t nz, bool eval, std::function<uint32_t*(Ctx&)> px_buffer, bool check = true) {
   const size_t npx = o->npx(), dz = nz - 1;
   DevScalars dp{nullptr, npx};
   if (o->domain_log2) {
     const int k = o->domain_log2;
     if (eval)
-      dp.produce_hv = [o, wdev, k](Ctx& cc, uint32_t* hv, uint32_t* bad) {
+      dp.produce_hv = [o, wdev, k, check](Ctx& cc, uint32_t* hv, uint32_t* bad) {
         r1cs_values_dev(cc, *o, wdev);
-        r1cs_check_domain_dev(cc, o->vals.as<uint32_t>(), k, bad);
+        if (check) r1cs_check_domain_dev(cc, o->vals.as<uint32_t>(), k, bad);
+        else GS_HIP(hipMemsetAsync(bad, 0, 4, cc.stream));
         hx_values_domain_dev(cc, o->vals.as<uint32_t>(), k, hv);
       };
     dp.produce = [o, wdev, px_buffer](Ctx& cc) { r1cs_px_dev(cc, *o, wdev, px_buffer(cc)); };
@@ -706,9 +716,9 @@ uint32_t* exact_px_buffer(Ctx& c, R1csObj* o, int slot) {
   return b.as<uint32_t>();
 }
 // the h-scalars of a BLOCKING witness proof (its px buffer is the blocking slot's)
-DevScalars witness_scalars_blocking(Ctx& c, R1csObj* o, const uint32_t* wdev, size_t nz, bool eval) {
+DevScalars witness_scalars_blocking(Ctx& c, R1csObj* o, const uint32_t* wdev, size_t nz, bool eval, bool check = true) {
   uint32_t* pxdev = exact_px_buffer(c, o, c.blocking_slot());
-  DevScalars dp = witness_scalars(o, wdev, nz, eval, [pxdev](Ctx&) { return pxdev; });
+  DevScalars dp = witness_scalars(o, wdev, nz, eval, [pxdev](Ctx&) { return pxdev; }, check);
   dp.p = pxdev;
   return dp;
 }
@@ -726,11 +736,12 @@ int witness_blocking_inputs(Ctx& c, const char* fn, ProverKey* pk, R1csObj* o, c
   if (nw != o->m) return fail(GS_ERR_SHAPE, "len(w) = %zu but the system has %zu variables", nw, o->m);
   if (chk.need_z && pk->nz == 0) return fail(GS_ERR_SHAPE, "the key has no Z");
   if (int rc = check_domain_pair(fn, pk, o)) return rc;
+  if (int rc = check_coset_only_route(c, fn, pk, o)) return rc;
   reset_timing(c);
   const uint32_t* wdev = w ? w->buf.as<uint32_t>() : upload_tmp(c, prove_state(c).up_w, w_host, nw);
   const bool eval = !(chk.eval_full_key_only && pk->shard_count != 1) && eval_route(c, pk, o);
   dw = DevScalars{wdev, nw};
-  dp = witness_scalars_blocking(c, o, wdev, pk->nz, eval);
+  dp = witness_scalars_blocking(c, o, wdev, pk->nz, eval, !o->product && !pk->coset_only);
   return GS_OK;
 }
 
@@ -773,6 +784,7 @@ int begin_ticket(Ctx& c, const TicketRequest& q, const std::function<std::unique
   if (q.refuse_slice && pk->shard_count != 1) return fail(GS_ERR_ARG, "%s: the key is a slice", q.fn);
   if (q.need_z && pk->nz == 0) return fail(GS_ERR_SHAPE, "the key has no Z");
   if (q.witness) if (int rc = check_domain_pair(q.fn, pk, o)) return rc;
+  if (q.witness) if (int rc = check_coset_only_route(c, q.fn, pk, o)) return rc;
   const int parity = c.free_parity();
   if (parity < 0) return fail(GS_ERR_BUSY, "%s: three operations are already outstanding; call gs_%s_prove_end first", q.fn, pk->scheme);
   std::unique_ptr<ProofInFlight> st = make(pk);
@@ -791,7 +803,7 @@ int begin_ticket(Ctx& c, const TicketRequest& q, const std::function<std::unique
     const bool eval = eval_route(c, pk, o);
     const uint32_t* wdev = dw.p;
     const size_t nz = pk->nz;
-    dp = witness_scalars(o, wdev, nz, eval, [o, parity](Ctx& cc) { return exact_px_buffer(cc, o, parity); });
+    dp = witness_scalars(o, wdev, nz, eval, [o, parity](Ctx& cc) { return exact_px_buffer(cc, o, parity); }, !o->product && !pk->coset_only);
     if (!eval) {                               // the monomial route may have to write px at once (its check is a host wait inside enqueue)
       dp.p = exact_px_buffer(c, o, parity);
     } else {                                   // with an evaluation-basis key nothing in here waits for the device
@@ -881,6 +893,7 @@ template <class Pk>
 static int pk_shard_impl(Ctx& c, Ctx& from, const char* scheme, Pk* full, size_t shard_index, size_t shard_count, gs_handle* out) {
   if (!full || !out) return fail(GS_ERR_ARG, "gs_%s_pk_shard: bad proving-key handle or null output", scheme);
   if (full->shard_count != 1) return fail(GS_ERR_ARG, "gs_%s_pk_shard: the source key is itself a slice", scheme);
+  if (full->coset_only) return refuse_coset_only("gs_groth16_pk_shard");
   if (shard_count == 0 || shard_index >= shard_count) return fail(GS_ERR_ARG, "gs_%s_pk_shard: bad shard %zu of %zu", scheme, shard_index, shard_count);
   auto pk = std::make_unique<Pk>();
   pk->nvars = full->nvars; pk->npublic = full->npublic; pk->nz = full->nz; pk->len_h = full->len_h;
@@ -1003,6 +1016,60 @@ int gs_groth16_pk_create(gs_handle g1_at, gs_handle g1_bacgamma, gs_handle g2_ba
   return guarded([&](Ctx& c) -> int {
     return groth_pk_create_impl(c, g1_at, g1_bacgamma, g2_bacgamma, bacdelta, ptd, g1_alpha, g1_beta, g1_delta, g2_beta, g2_delta, z, nz,
                                 nvars, npublic, 0, 0, 1, out);
+  }, true, false, g1_at);
+}
+
+// A coset-only key (prove.h): the five arrays and five points of gs_groth16_pk_create, but in place of PowersTauDelta the m = 2^log2_domain
+// points of the coset evaluation basis E (domain.h) -- section 9 of a snarkjs .zkey.  Z = x^m - 1 is built here.
+int gs_groth16_pk_create_domain(gs_handle g1_at, gs_handle g1_bacgamma, gs_handle g2_bacgamma, gs_handle bacdelta, gs_handle h_coset,
+                                const uint64_t g1_alpha[12], const uint64_t g1_beta[12], const uint64_t g1_delta[12],
+                                const uint64_t g2_beta[24], const uint64_t g2_delta[24], size_t log2_domain, size_t nvars, size_t npublic, gs_handle* out) {
+  return guarded([&](Ctx& c) -> int {
+    const char* fn = "gs_groth16_pk_create_domain";
+    Bases* at = c.get<Bases>(g1_at, Kind::G1Bases);
+    Bases* b1 = c.get<Bases>(g1_bacgamma, Kind::G1Bases);
+    Bases* b2 = c.get<Bases>(g2_bacgamma, Kind::G2Bases);
+    Bases* cd = c.get<Bases>(bacdelta, Kind::G1Bases);
+    Bases* he = c.get<Bases>(h_coset, Kind::G1Bases);
+    if (!at || !b1 || !b2 || !cd || !he) return fail(GS_ERR_ARG, "%s: bad base handle", fn);
+    if (!g1_alpha || !g1_beta || !g1_delta || !g2_beta || !g2_delta || !out) return fail(GS_ERR_ARG, "%s: null argument", fn);
+    if (log2_domain < 1 || log2_domain > (size_t)kDomainMaxLog2) return fail(GS_ERR_ARG, "%s: log2_domain = %zu, must be 1 .. %d", fn, log2_domain, kDomainMaxLog2);
+    if (npublic + 1 > nvars) return fail(GS_ERR_SHAPE, "NPublic + 1 > NVars");
+    const size_t m = (size_t)1 << log2_domain, nz = m + 1;
+    if (at->n != nvars || b1->n != nvars || b2->n != nvars || cd->n != nvars)
+      return fail(GS_ERR_SHAPE, "%s: At/BACGamma/BACDelta must have NVars = %zu points, got %zu/%zu/%zu/%zu", fn, nvars, at->n, b1->n, b2->n, cd->n);
+    if (he->n != m) return fail(GS_ERR_SHAPE, "%s: the coset evaluation basis must have 2^%zu = %zu points, got %zu", fn, log2_domain, m, he->n);
+    auto pk = std::make_unique<GrothPkObj>();
+    pk->nvars = nvars; pk->npublic = npublic; pk->nz = nz; pk->len_h = 0;
+    set_shard(*pk, 0, 1);                                  // a full key: n_w = nvars, n_h = 0
+    pk->coset_only = true;
+    copy_points(c, at, kG1Aff, pk->at());
+    copy_points(c, b1, kG1Aff, pk->bacgamma1());
+    copy_points(c, cd, kG1Aff, pk->bacdelta());
+    copy_points(c, b2, kG2Aff, pk->bacgamma2());
+    copy_points(c, he, kG1Aff, pk->ptd_eval());
+    groth_force_public(c, *pk);
+    pk->alpha = g1_affine_from_jacobian_std(g1_alpha);
+    pk->beta = g1_affine_from_jacobian_std(g1_beta);
+    pk->delta = g1_affine_from_jacobian_std(g1_delta);
+    pk->beta2 = g2_affine_from_jacobian_std(g2_beta);
+    pk->delta2 = g2_affine_from_jacobian_std(g2_delta);
+    pk->domain_log2 = (int)log2_domain;
+    pk->n_eval = m; pk->e_lo = 0; pk->n_e = m; pk->eval_domain_log2 = (int)log2_domain;
+    {                                                      // Z = x^m - 1, standard form: r - 1, zeros, 1
+      uint32_t lo[8], hi[8] = {1u, 0, 0, 0, 0, 0, 0, 0};
+      for (int i = 0; i < 8; ++i) lo[i] = ModR::p32(i);
+      lo[0] -= 1u;                                         // r is odd: no borrow
+      DevBuf zc(nz * 32);
+      GS_HIP(hipMemsetAsync(zc.p, 0, nz * 32, c.stream));
+      GS_HIP(hipMemcpyAsync(zc.p, lo, 32, hipMemcpyHostToDevice, c.stream));
+      GS_HIP(hipMemcpyAsync(zc.as<uint32_t>() + m * 8, hi, 32, hipMemcpyHostToDevice, c.stream));
+      divisor_init(c, pk->z, zc.as<uint32_t>(), nz);
+      GS_HIP(hipStreamSynchronize(c.stream));              // `zc` is released here
+    }
+    pk_scan_sparsity(c, *pk);
+    *out = c.put(std::move(pk));
+    return GS_OK;
   }, true, false, g1_at);
 }
 

@@ -143,6 +143,9 @@ struct R1csObj : Object {        // sparse R1CS resident on the device: A, B, C 
   // 0: the reference's QAP, row j at the node j + 1.  k >= 1: the QAP over the domain of the 2^k-th roots of unity (domain.h), row j at
   // omega^j, n <= 2^k; the value and coefficient vectors then have 2^k elements each (rows n .. 2^k - 1 are zero).
   int domain_log2 = 0;
+  // A product system (gs_r1cs_upload_zkey; snarkjs .zkey keys): the object holds A and B only and c_j = a_j b_j at every point of the
+  // domain by definition -- nothing to check, no violated constraint.  Index 2 of the CSR arrays stays empty.
+  bool product = false;
   size_t points() const { return domain_log2 ? (size_t)1 << domain_log2 : n; }      // elements per value / coefficient vector
   size_t npx() const { return 2 * points() - 1; }                                    // coefficients of px = ax bx - cx
   R1csObj() : Object(Kind::R1cs) {}

@@ -395,6 +395,7 @@ static int pk_set_eval_impl(Ctx& c, const char* fn, Kind kind, const char* slice
   Bases* b = c.get<Bases>(hbases, Kind::G1Bases);
   if (!pk || !b) return fail(GS_ERR_ARG, "%s: bad handle", fn);
   if (pk->shard_count != 1) return fail(GS_ERR_ARG, "%s: the key is a slice%s", fn, slice_hint);
+  if (pk->coset_only) return refuse_coset_only(fn);          // its coset basis is the only thing it proves with
   const size_t n = b->n;
   if (n < 2 || pk->nz == 0 || (pk->nz - 1 != n - 1 && pk->nz - 1 != n))
     return fail(GS_ERR_SHAPE, "%s: %zu points, but deg Z = %zu needs n = deg Z or deg Z + 1 constraints", fn, n, pk->nz ? pk->nz - 1 : 0);
@@ -445,6 +446,7 @@ static int pk_set_quot_impl(Ctx& c, const char* fn, Kind kind, gs_handle hpk, gs
   Bases* b = hbases ? c.get<Bases>(hbases, Kind::G1Bases) : nullptr;
   if (!pk || (hbases && !b)) return fail(GS_ERR_ARG, "%s: bad handle", fn);
   if (pk->shard_count != 1) return fail(GS_ERR_ARG, "%s: the key is a slice (key slices carry no quotient-basis array)", fn);
+  if (pk->coset_only) return refuse_coset_only(fn);
   if (b && (b->n == 0 || b->n != pk->len_h)) return fail(GS_ERR_SHAPE, "%s: %zu points, but the key's h array has %zu", fn, b->n, pk->len_h);
   c.drain();                                  // an outstanding ticket may read the array that goes
   pk->h_quot.table.invalidate();

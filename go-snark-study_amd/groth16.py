@@ -68,6 +68,18 @@ def device_pk_from_handles(at, bacgamma1, bacgamma2, bacdelta, ptd, alpha, beta,
     return _pk_create("gs_groth16_pk_create", at, bacgamma1, bacgamma2, bacdelta, ptd, alpha, beta, delta, beta2, delta2, z_u64, nvars, npublic)
 
 
+def device_pk_domain_from_handles(at, bacgamma1, bacgamma2, bacdelta, h_coset, alpha, beta, delta, beta2, delta2, log2_domain, nvars, npublic):
+    """A coset-only key (gs_groth16_pk_create_domain): `h_coset` holds the 2^log2_domain points of the coset evaluation basis in place
+    of PowersTauDelta; Z = x^(2^log2_domain) - 1 is built by the library."""
+    capi.init()
+    a = capi.g1_points_to_u64([alpha, beta, delta])
+    b = capi.g2_points_to_u64([beta2, delta2])
+    cell = capi.HandleCell()
+    capi.call("gs_groth16_pk_create_domain", *map(capi.raw, (at, bacgamma1, bacgamma2, bacdelta, h_coset)),
+              *map(capi.ptr64, (a[0], a[1], a[2], b[0], b[1])), int(log2_domain), nvars, npublic, cell.ref)
+    return DevicePk(cell.result(), nvars, npublic)
+
+
 def device_pk_shard_from_handles(at, bacgamma1, bacgamma2, bacdelta, ptd, alpha, beta, delta, beta2, delta2, z_u64, nvars, npublic,
                                  nptd_total, shard_index, shard_count):
     return _pk_create("gs_groth16_pk_create_shard", at, bacgamma1, bacgamma2, bacdelta, ptd, alpha, beta, delta, beta2, delta2, z_u64,

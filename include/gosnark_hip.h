@@ -214,6 +214,40 @@ int gs_r1cs_upload_domain(size_t log2_domain, size_t n, size_t m,
 int gs_groth16_pk_derive_eval_domain(gs_handle pk, size_t log2_domain);
 int gs_groth16_pk_set_eval_domain(gs_handle pk, gs_handle bases, size_t log2_domain);
 
+/* ---- zkey: the binary files circom / snarkjs write today ---------------------------------------- */
+/* A circuit.zkey is not a re-encoding of proving_key.json: it has NO C matrix (the prover takes c_j = a_j b_j on the domain), NO
+ * monomial h array (section 9 is the coset evaluation basis E above), and its numbers are in machine form already.  Four entry points
+ * take its sections as they lie in the file -- e.g. memory-mapped; caller memory of any alignment, staged through the pinned buffers
+ * like gs_g1_upload -- and convert on the device.  (go-snark-study_amd/circom.py parses the container; no file written by snarkjs itself has been
+ * read yet, so the container layout is the parser's concern and these entry points do not depend on it.)
+ *
+ * gs_g1_upload_affine_mont / gs_g2_upload_affine_mont: n affine points, G1 as x | y, G2 as x.c0 | x.c1 | y.c0 | y.c1, every coordinate 32
+ * little-endian bytes of value * 2^256 mod q; all-zero bytes are the point at infinity.  One Montgomery product by a constant per
+ * coordinate.  A coordinate >= q and a point off its curve are GS_ERR_ARG with the first offending index.  The result is an ordinary
+ * base-array handle.
+ *
+ * gs_r1cs_upload_zkey: `coefs` = the ncoefs 44-byte records of section 4 (u32 matrix: 0 = A, 1 = B; u32 row < 2^log2_domain;
+ * u32 signal < nvars; 32 bytes of value * 2^512 mod r), any order, repeated (matrix, row, signal) add up.  The CSR arrays of A and B are
+ * built on the device (count, scan, scatter); a record out of range is GS_ERR_ARG with its index.  The handle is a domain R1CS that is a
+ * PRODUCT SYSTEM: it has no C matrix, the third value vector is a_j b_j (one point-wise kernel), there is nothing to check -- the
+ * violated-constraint count is 0, gs_timing.fallbacks stays 0, and a wrong witness gives a proof the verifier rejects, as in snarkjs.
+ * Every Groth16 witness entry point and gs_r1cs_px accept it, on the coset route and (with a key that has PowersTauDelta) on the px route;
+ * Pinocchio, key slices and the multi-device values routes refuse it like any domain R1CS.
+ *
+ * gs_groth16_pk_create_domain: the arrays and points of gs_groth16_pk_create, with `h_coset` = the 2^log2_domain points of E in place of
+ * PowersTauDelta; Z = x^m - 1 is built inside.  The result is a COSET-ONLY key: it proves from a witness with a domain R1CS of the same
+ * log2_domain (product system or not) on the evaluation-basis route, and has no other route and no fallback.  Whatever needs
+ * PowersTauDelta is GS_ERR_SHAPE ("the key holds the coset evaluation basis only"): gs_groth16_prove* with px, gs_groth16_prove_r1cs, a
+ * witness call after gs_set_eval_basis(0), gs_groth16_pk_derive_quot / _derive_eval* / _set_quot / _set_eval, gs_groth16_pk_shard*.
+ * gs_groth16_pk_export which = 4 has 0 points, which = 7 the m points of E. */
+int gs_g1_upload_affine_mont(const void* bytes /* n x 64 */, size_t n, gs_handle* out);
+int gs_g2_upload_affine_mont(const void* bytes /* n x 128 */, size_t n, gs_handle* out);
+int gs_r1cs_upload_zkey(size_t log2_domain, size_t nvars, const void* coefs /* ncoefs x 44 */, size_t ncoefs, gs_handle* out);
+int gs_groth16_pk_create_domain(gs_handle g1_at, gs_handle g1_bacgamma, gs_handle g2_bacgamma, gs_handle bacdelta, gs_handle h_coset,
+                                const uint64_t g1_alpha[12], const uint64_t g1_beta[12], const uint64_t g1_delta[12],
+                                const uint64_t g2_beta[24], const uint64_t g2_delta[24], size_t log2_domain, size_t nvars, size_t npublic,
+                                gs_handle* out);
+
 /* ---- Groth16 prover (groth16/groth16.go) --------------------------------------------------- */
 /* Device-resident proving key: groth16.Pk (groth16.go:15-32).  At, BACGamma (G1), BACDelta:
  * m points; G2 BACGamma: m points; PowersTauDelta: len(Z) points; single points as Jacobian
