@@ -155,17 +155,8 @@ int gs_r1cs_px(gs_handle hr1cs, gs_handle hw, gs_handle* px_inout) {
     if (!o || !w || !px_inout) return fail(GS_ERR_ARG, "gs_r1cs_px: bad handle");
     if (w->n != o->m) return fail(GS_ERR_SHAPE, "len(w) = %zu but the system has %zu variables", w->n, o->m);
     const size_t npx = o->npx();
-    Scalars* px = nullptr;
-    if (*px_inout) {
-      px = c.get<Scalars>(*px_inout, Kind::Scalars);
-      if (!px || px->n != npx) return fail(GS_ERR_ARG, "gs_r1cs_px: the px handle does not hold 2n - 1 = %zu coefficients", npx);
-    } else {
-      auto fresh = std::make_unique<Scalars>();
-      fresh->n = npx;
-      fresh->buf.alloc(npx * 32);
-      px = fresh.get();
-      *px_inout = c.put(std::move(fresh));
-    }
+    Scalars* px = inout_scalars(c, px_inout, npx, "%s: the px handle does not hold 2n - 1 = %zu coefficients", "gs_r1cs_px");
+    if (!px) return GS_ERR_ARG;
     // On the stream that carries every proof's polynomial stage: stream order keeps the engine's workspaces consistent, so
     // the px of proof k+1 may be computed while proofs are in flight (it queues behind their H(x), not behind their MSMs).
     StreamScope sc(c, c.aux_stream[1]);

@@ -1,11 +1,11 @@
-// Internal: device-resident proving keys (described as data the prover engine in prove.hip reads) and what the other
-// translation units need of the prover's staging and of the R1CS routines (capi_poly.hip, capi_r1cs.hip).
+// Internal: device-resident proving keys (described as data the prover engine in prove.hip reads; built in keys.hip) and what the
+// other translation units need of the prover's staging and of the R1CS routines (capi_poly.hip, capi_r1cs.hip).
 #pragma once
-#include <functional>
 #include <vector>
 #include <mutex>
 #include "msm.h"
 #include "poly.h"
+#include "route.h"
 #include "runtime.h"
 
 namespace gs {
@@ -93,7 +93,14 @@ inline int refuse_coset_only(const char* fn) {
   return fail(GS_ERR_SHAPE, "%s: the key holds the coset evaluation basis only (it has no monomial h array): it proves from a witness "
               "with a domain R1CS on the evaluation-basis route, and nothing else", fn);
 }
+// what the route decision (route.h) reads of a key
+inline KeyFacts key_facts(const ProverKey& pk) {
+  return KeyFacts{pk.nz, pk.len_h, pk.shard_index, pk.shard_count, pk.h_lo, pk.n_h, pk.n_eval, pk.e_lo, pk.n_e, pk.n_q, pk.coset_only, pk.serves_quot()};
+}
+// keys.hip
 void pk_scan_sparsity(Ctx& c, ProverKey& pk);      // fills b_index / b_finite (synchronises the stream)
+bool bad_shard(size_t shard_index, size_t shard_count);
+void force_infinity(Ctx& c, DevBuf& pts, size_t count, size_t words);   // zero the first `count` packed points (-> infinity)
 
 struct GrothPkObj : ProverKey {   // groth16.Pk (groth16/groth16.go:15-32), resident
   static constexpr Kind kKind = Kind::GrothPk;
@@ -146,6 +153,19 @@ struct ProveState {
 inline ProveState& prove_state(Ctx& c) { return c.state<ProveState>(c.prove_state); }
 const uint32_t* upload_tmp(Ctx& c, DevBuf& buf, const uint64_t* host, size_t n);   // host scalars -> a scratch buffer (books h2d_ms)
 void download(Ctx& c, uint64_t* host, const void* dev, size_t n);                  // n scalars to the host; synchronises c.stream
+// An "inout" scalar vector of an entry point: *handle == 0 creates a resident vector of n scalars and stores its handle; otherwise the
+// handle must hold exactly n, or the call fails with `wording` (a format of fn and n: one %s, one %zu).  nullptr = failed.
+inline Scalars* inout_scalars(Ctx& c, gs_handle* handle, size_t n, const char* wording, const char* fn) {
+  if (!*handle) {
+    auto fresh = std::make_unique<Scalars>();
+    fresh->n = n;
+    fresh->buf.alloc(n * 32);
+    *handle = c.put(std::move(fresh));
+  }
+  Scalars* s = c.get<Scalars>(*handle, Kind::Scalars);
+  if (!s || s->n != n) { fail(GS_ERR_ARG, wording, fn, n); return nullptr; }
+  return s;
+}
 // capi_r1cs.hip: w (standard form, m elements, device) -> o.vals = [A w | B w | C w], and -> o.coef = [ax | bx | cx] and px_out
 void r1cs_values_dev(Ctx& c, R1csObj& o, const uint32_t* w_dev);
 void r1cs_px_dev(Ctx& c, R1csObj& o, const uint32_t* w_dev, uint32_t* px_out);

@@ -4,14 +4,13 @@
 #include "prove.h"
 
 #include <algorithm>
-#include <cstdlib>
 #include <cstring>
 #include <functional>
 #include <chrono>
 #include <future>
+#include <variant>
 #include <vector>
 
-#include "domain.h"
 #include "hostcopy.h"
 #include "point_io.h"
 
@@ -35,36 +34,34 @@ void gs::download(Ctx& c, uint64_t* host, const void* dev, size_t n) {
 
 namespace {
 
-constexpr size_t kG1Aff = 16, kG2Aff = 32;      // u32 words per packed affine point
+struct DevVec { const uint32_t* p; size_t n; };   // the witness of a prove call (device, not owned): landed, or ordered on the stream that reads it
+DevVec resident(const Scalars* s) { return DevVec{s->buf.as<uint32_t>(), s->n}; }
 
-// copy n packed points [off, off+n) of a base handle into an owned buffer
-void copy_points(Ctx& c, const Bases* b, size_t words, DevBuf& dst) {
-  dst.alloc(std::max<size_t>(b->n, 1) * words * 4);
-  if (b->n) GS_HIP(hipMemcpyAsync(dst.p, b->buf.p, b->n * words * 4, hipMemcpyDeviceToDevice, c.stream));
+// What the h-sum of a proof runs over, by who hands it to the engine -- plain data; route.h (HSourceKind, in this order) decides
+// from it and from the key which of the key's h arrays the sum goes against.
+struct PxResident { const uint32_t* px; size_t n; };     // px on the device: a resident vector, or a host-buffer ticket's after staging
+struct PxOnHost {                                        // px still in host memory (the blocking gs_*_prove): copied into `stage` on the
+  uint32_t* stage; const uint64_t* host; size_t n;       // polynomial stream, behind the enqueue of the accumulations over w (h2d_ms)
+};
+struct PxFromR1cs { R1csObj* r1cs; const uint32_t* w; uint32_t* px_out; };   // px = r1csqap.go:161-210 of w, into the caller's vector
+// A witness (the witness routes below): H's values when the evaluation-basis route is open, else hx directly (nodes R1CS) or through
+// px, which goes into the exact-px buffer of `slot` -- allocated only when that route is taken.  `check`: count the violated
+// constraints on the evaluation-basis route, so that the proof can be redone on the exact route.
+struct WitnessSource { R1csObj* r1cs; const uint32_t* w; int slot; bool check, eval_open; };
+// H's values of this key slice's range [e_lo, e_lo + n_e), computed by another rank and scattered (gs_*_prove_partials_values)
+struct ValuesSlice { const uint32_t* values; size_t n_e; };
+using HSource = std::variant<PxResident, PxOnHost, PxFromR1cs, WitnessSource, ValuesSlice>;
+HSourceKind kind_of(const HSource& s) { return (HSourceKind)s.index(); }
+static_assert(std::is_same_v<std::variant_alternative_t<(size_t)HSourceKind::Witness, HSource>, WitnessSource> &&
+              std::is_same_v<std::variant_alternative_t<(size_t)HSourceKind::Values, HSource>, ValuesSlice>, "HSource follows HSourceKind");
+PxResident resident_px(const Scalars* s) { return PxResident{s->buf.as<uint32_t>(), s->n}; }
+ValuesSlice values_slice(const Scalars* hv) { return ValuesSlice{hv->buf.as<uint32_t>(), hv->n}; }
+// the exact-route retry: this witness source with the evaluation-basis route closed, as a blocking proof of `slot`
+HSource exact_retry(const HSource& src, int slot) {
+  const WitnessSource& wit = std::get<WitnessSource>(src);
+  return WitnessSource{wit.r1cs, wit.w, slot, wit.check, false};
 }
 
-struct DevScalars {            // a scalar vector used by a prove call (not owned)
-  const uint32_t* p;           // resident copy (device)
-  size_t n;
-  const uint64_t* host = nullptr;   // if set: `p` is a staging buffer that still has to be filled from here, on the stream
-                                    // that consumes it (so the PCIe copy of px overlaps the accumulations over w)
-  hipStream_t host_stream = nullptr;   // ... or (host-buffer tickets) on this stream, with the consumer waiting for `host_done`,
-  hipEvent_t host_done = nullptr;      //     so that the DMA does not queue behind the previous proof's polynomial stage
-  std::function<void(Ctx&)> produce;   // if set: `p` is an output buffer this call still has to compute, on the stream that
-                                       // consumes it (px from the resident R1CS, behind the accumulations over w)
-  std::function<bool(Ctx&, uint32_t*)> produce_hx;   // if set: try to compute hx = px / Z directly (poly.h: hx_direct_dev) into the given
-                                                     // buffer; false = not applicable, fall back to produce + quotient
-  // Evaluation-basis route (keys with an h_eval array): if set, the h-MSM runs over H's VALUES at the nodes n+1..2n, which this
-  // writes (n_eval of them) into the first buffer; the second is a device word that receives the number of violated constraints.
-  // No host wait: the word is read when the proof is collected, and a non-zero count sends the caller down the exact route.
-  std::function<void(Ctx&, uint32_t*, uint32_t*)> produce_hv;
-  // ... or the values of this key slice's range [e_lo, e_lo + n_e) are already there (computed by another rank and scattered:
-  // gs_groth16_prove_partials_values); n = n_e then
-  const uint32_t* hv_slice = nullptr;
-};
-DevScalars resident(const Scalars* s) { return DevScalars{s->buf.as<uint32_t>(), s->n}; }
-
-size_t quotient_len(size_t npx, size_t nz) { return npx >= nz ? npx - nz + 1 : 0; }
 // internal status of proof_collect: the witness violates a constraint, so the optimistic evaluation-basis result is void --
 // run the exact route (px, floor quotient) instead.  Never crosses the C ABI.
 constexpr int kRetryExact = 1;
@@ -84,27 +81,6 @@ struct ProofSums {
   G1Xyzz h;
 };
 
-// Shard of the term ranges this call sums over (multi-GPU: rank k of N takes [k/N, (k+1)/N) of both ranges).
-struct Shard { size_t index = 0, count = 1; };
-static void shard_range(size_t n, const Shard& sh, size_t& lo, size_t& hi) {
-  const size_t q = n / sh.count, rem = n % sh.count;
-  lo = sh.index * q + std::min(sh.index, rem);
-  hi = lo + q + (sh.index < rem ? 1 : 0);
-}
-
-// GS_HOST_STAGE (scheduling only, same results): how a host-buffer ticket's arrays reach its slot.
-//   0  copy stream + event: the kernels that read the vector wait for the copy's event on their own streams
-//   1  copy stream, and the host waits for the copy to land before it enqueues the readers (what gs_scalars_update + _begin does)
-//   2  on the stream of the first reader itself (w: the plan(w) stream, px: the polynomial stream); other readers wait for its event
-// Measured at 2^20, three in flight, eight rotating witnesses (profiles/r05_ab_host_stage.txt; resident: 10.03-10.07 / px 8.84-9.01 ms):
-//   witness from the host   0: 11.2-11.3   1: 10.12-10.17   2: 10.1-11.0        w + px from the host   0: 10.9   1: 9.45-9.51   2: 11.4-11.5
-// The cross-stream event of mode 0 costs more than the host wait of mode 1 (the host has nothing else to do: the device is busy with the
-// two tickets before this one), hence 1.
-static long host_stage_mode() {
-  static const long mode = run_knob("GS_HOST_STAGE", 1, 0, 2);
-  return mode;
-}
-// w: staged at once (everything of a proof starts with plan(w))
 // The streams ONE proof's device work is enqueued on, decided once per proof (round 4 toggled a context flag between two
 // evaluations of an accessor instead).  plan(w) of a pipelined proof gets its own stream (aux 2, every tail then shares aux 0) where
 // the polynomial stage is long: on aux 1 the NEXT proof's plan(w) queues behind this proof's H stage and plan(h), and the
@@ -139,17 +115,6 @@ static ProofStreams proof_streams(Ctx& c, bool pipelined, size_t nterms, bool fr
   return ps;
 }
 
-// Inputs that arrive in host memory with a ticket (gs_*_host_begin): staged on the copy stream into the slot's own buffers.
-struct HostInputs {
-  hipEvent_t w_done = nullptr, px_done = nullptr;       // recorded on the copy stream behind the last DMA of w / px
-  std::shared_ptr<PhaseTimer> th2d;                     // read when the ticket is collected (a read here would wait for the copy)
-  void create() {
-    if (!w_done) GS_HIP(hipEventCreateWithFlags(&w_done, hipEventDisableTiming));
-    if (!px_done) GS_HIP(hipEventCreateWithFlags(&px_done, hipEventDisableTiming));
-  }
-  ~HostInputs() { for (hipEvent_t e : {w_done, px_done}) if (e) (void)hipEventDestroy(e); }
-};
-
 // the part of a term list that falls into the held range [base, base + nterms): pointer into the device list and count
 static const uint32_t* term_list_range(const DevBuf& index_dev, const std::vector<uint32_t>& index_host, size_t base, size_t nterms, uint32_t& count) {
   const auto lo = std::lower_bound(index_host.begin(), index_host.end(), (uint32_t)base);
@@ -164,7 +129,9 @@ static const uint32_t* term_list_range(const DevBuf& index_dev, const std::vecto
 struct ProofInFlight : InFlightBase {
   ProverKey* pk = nullptr;
   ProofStreams streams;
-  HostInputs in;
+  DevVec w{nullptr, 0};                    // what the proof was enqueued with (a ticket's exact-route retry starts from it)
+  HSource src;
+  std::shared_ptr<PhaseTimer> th2d;        // host-buffer tickets: the staging copies (read when the ticket is collected: a read at once would wait for them)
   // done_g2 / done_g1w / done_h: one per MSM group, recorded behind that group's reduction tail, so the host can add up a
   // group's partial sums while the later groups are still on the device
   hipEvent_t planw = nullptr, planh = nullptr, done_main = nullptr, done_g2 = nullptr, done_g1w = nullptr, done_h = nullptr;
@@ -178,7 +145,6 @@ struct ProofInFlight : InFlightBase {
   MsmPending pend_g1w, pend_g2w, pend_h;
   std::shared_ptr<PhaseTimer> tpoly, tplanw, tplanh;
   const uint32_t* bad_host = nullptr;      // evaluation-basis route: the violated-constraint count (valid once done_h has fired)
-  std::function<int(Ctx&, ProofSums&)> exact_route;   // ... and what to run instead when it is not zero (witness tickets)
   // The scheme's hook into the fold of the G1 group over w (runs on that group's worker thread, with the sums in key order, while
   // the group over h is still on the device): Groth16's early tail products.
   std::function<void(const std::vector<G1Xyzz>&)> on_g1w;
@@ -207,35 +173,75 @@ static long split_b_percent() {
   return pct;
 }
 
+// ---- what a witness source computes, on the polynomial stream --------------------------------------------------------------------
+// px of the exact route: one buffer per slot (the three tickets and the blocking entry points), allocated only if that route is
+// ever taken.  Round 3 handed every in-flight ticket -- and the blocking entry points' host uploads -- the SAME staging buffer and
+// leaned on all polynomial stages being serialised on one stream (ADVICE r3); a slot's buffer is only ever touched by the
+// operation that owns the slot, and a slot is re-used only after its operation was collected.
+uint32_t* exact_px_buffer(Ctx& c, R1csObj* o, int slot) {
+  const size_t npx = o->npx();
+  o->prod.ensure(npx * 32);
+  DevBuf& b = prove_state(c).exact_px[slot % Ctx::kSlots];
+  b.ensure(npx * 32);
+  return b.as<uint32_t>();
+}
+// The three ways to the h-scalars of a witness proof, in the order the prover tries them (a domain R1CS has two: the coset
+// evaluation-basis route, then px -- its quotient by x^m - 1 goes through the key's Divisor / quotient-basis array like any Z).
+// 1. Evaluation-basis route: H's values (n_eval of them) into `hv`, the number of violated constraints into the device word `bad`
+// (read when the proof is collected).  The check is off for a product system (c = a b by definition: nothing to check) and for a
+// coset-only key (no exact route to go to): the count is 0, and a wrong witness gives a proof that the verifier rejects, as in snarkjs.
+void witness_values(Ctx& c, const WitnessSource& s, size_t dz, uint32_t* hv, uint32_t* bad) {
+  R1csObj* o = s.r1cs;
+  r1cs_values_dev(c, *o, s.w);
+  if (const int k = o->domain_log2) {
+    if (s.check) r1cs_check_domain_dev(c, o->vals.as<uint32_t>(), k, bad);
+    else GS_HIP(hipMemsetAsync(bad, 0, 4, c.stream));
+    hx_values_domain_dev(c, o->vals.as<uint32_t>(), k, hv);
+  } else {
+    r1cs_check_dev(c, o->vals.as<uint32_t>(), o->n, dz, bad);
+    hx_values_dev(c, o->vals.as<uint32_t>(), o->n, dz, hv);
+  }
+}
+// 2. hx = px / Z directly from the constraint values (poly.h, hx_direct_dev: a nodes R1CS and a satisfying witness); false = not
+// applicable, go through px
+bool witness_hx(Ctx& c, const WitnessSource& s, size_t dz, uint32_t* hx) {
+  R1csObj* o = s.r1cs;
+  if (o->domain_log2) return false;
+  r1cs_values_dev(c, *o, s.w);
+  return hx_direct_dev(c, o->vals.as<uint32_t>(), o->n, dz, hx);
+}
+// 3. px itself (r1csqap.go:161-210 on the sparse system) -- also what a PxFromR1cs source does; the engine then divides by Z, or not
+
 // Enqueue every device operation of one proof (no host wait).  `wait_inputs`: w / px were uploaded on the main stream
 // in this call, so the aux streams must order themselves behind that point.  Ticket `parity` owns plan slots 2p / 2p + 1, workspace
 // sets 8p .. 8p + 7 and pinned slots 3p .. 3p + 2.  `shard`: the term ranges this call sums over (several GPUs: rank k of N; the
 // sums of the ranks add up to the proof's).
-int proof_enqueue(Ctx& c, ProverKey* pk, DevScalars w, DevScalars px, const Shard& shard, int parity, bool wait_inputs, bool pipelined,
+int proof_enqueue(Ctx& c, ProverKey* pk, DevVec w, const HSource& src, const Shard& shard, int parity, bool wait_inputs, bool pipelined,
                   ProofInFlight& st) {
   DevBuf& hxbuf = prove_state(c).hx[parity];
   if (w.n != pk->nvars) return fail(GS_ERR_SHAPE, "len(w) = %zu but the key has %zu variables", w.n, pk->nvars);
-  const bool eval = (bool)px.produce_hv || px.hv_slice;   // h-MSM over H's values against the evaluation-basis table (the caller checked the key has one)
-  if (!eval && pk->coset_only) return refuse_coset_only(pk->kind == Kind::GrothPk ? "gs_groth16_prove" : "gs_pinocchio_prove");   // every px route ends up here
-  const size_t nh = eval ? pk->n_eval : quotient_len(px.n, pk->nz);
-  if (!eval && nh > pk->len_h) return fail(GS_ERR_SHAPE, pk->hx_too_long, nh, pk->len_h);
-  const bool sliced = pk->shard_count > 1;
-  // Quotient-basis route (prove.h, h_quot): px is given, or comes out of px.produce, and the key holds the array -- the h-sum runs over
-  // px[D ..] directly.  Decided here because it decides which array's table the call prepares.  (A witness proof that may compute H
-  // itself -- produce_hx -- keeps its route, and with it the division when that route does not apply.)
-  const bool quot = !eval && !px.produce_hx && !sliced && nh >= 1 && pk->serves_quot() && nh <= pk->n_q;
-  if (sliced && (shard.index != pk->shard_index || shard.count != pk->shard_count))
+  const WitnessSource* wit = std::get_if<WitnessSource>(&src);
+  const PxFromR1cs* from_r1cs = std::get_if<PxFromR1cs>(&src);
+  const ValuesSlice* values = std::get_if<ValuesSlice>(&src);
+  R1csObj* r1cs = wit ? wit->r1cs : from_r1cs ? from_r1cs->r1cs : nullptr;      // the source computes on the polynomial stream, from
+  const uint32_t* r1cs_w = wit ? wit->w : from_r1cs ? from_r1cs->w : nullptr;   // this system and this witness
+  // px's coefficients where the source has them or puts them, and how many it holds or would produce
+  const uint32_t* px = from_r1cs ? from_r1cs->px_out : nullptr;
+  size_t npx = r1cs ? r1cs->npx() : 0;
+  if (const auto* p = std::get_if<PxResident>(&src)) { px = p->px; npx = p->n; }
+  else if (const auto* p = std::get_if<PxOnHost>(&src)) { px = p->stage; npx = p->n; }
+  // The route (route.h): which of the key's h arrays the sum runs against -- hence which table this call prepares -- and its lengths
+  const RoutePlan rp = decide_route(key_facts(*pk), HQuery{kind_of(src), npx, wit && wit->eval_open, wit && !wit->r1cs->domain_log2}, shard);
+  if (rp.err == RouteError::CosetOnly) return refuse_coset_only(pk->kind == Kind::GrothPk ? "gs_groth16_prove" : "gs_pinocchio_prove");
+  if (rp.err == RouteError::HxTooLong) return fail(GS_ERR_SHAPE, pk->hx_too_long, rp.nh, pk->len_h);
+  if (rp.err == RouteError::ShardMismatch)
     return fail(GS_ERR_ARG, "this key holds shard %zu of %zu of the term ranges only: call gs_%s_prove_partials with that shard "
                 "(asked for %zu of %zu)", pk->shard_index, pk->shard_count, pk->scheme, shard.index, shard.count);
-  size_t wlo, whi, hlo, hhi;
+  const HRoute route = rp.route; const size_t nh = rp.nh, hlo = rp.hlo, hhi = rp.hhi, hbase = rp.hbase;
+  size_t wlo, whi;
   shard_range(w.n, shard, wlo, whi);
-  if (sliced && eval) { hlo = pk->e_lo; hhi = pk->e_lo + pk->n_e; }
-  else if (sliced) {                // a slice's range of the h array was fixed at key creation (split of len_h, clipped to len(hx))
-    hlo = std::min(pk->h_lo, nh);
-    hhi = std::min(pk->h_lo + pk->n_h, nh);
-  } else shard_range(nh, shard, hlo, hhi);
-  const size_t held_lo = eval ? pk->e_lo : pk->h_lo;
-  const size_t wbase = wlo - pk->w_lo, hbase = hlo - std::min(held_lo, hlo);      // offsets into the arrays this key holds
+  const size_t wbase = wlo - pk->w_lo;      // offset into the arrays over w this key holds
+  if (wit && route != HRoute::Values) px = exact_px_buffer(c, wit->r1cs, wit->slot);      // (only here does that buffer come into being)
   // window tables or table-free, per plan (tables.h, prepare_tables: the arrays over w share one plan, so they go one way together)
   // (before any table instalment goes onto the main stream: the plans on the aux streams wait for the inputs, not for the slabs)
   if (wait_inputs) {
@@ -247,8 +253,8 @@ int proof_enqueue(Ctx& c, ProverKey* pk, DevScalars w, DevScalars px, const Shar
   }
   int cw = 0, ch = 0;
   const int ng = pk->n_g1w, bg = pk->b_g1;
-  KeyArray& harr = eval ? pk->h_eval : quot ? pk->h_quot : pk->h;
-  const size_t n_harr = eval ? pk->n_e : quot ? pk->n_q : pk->n_h;
+  KeyArray& harr = route == HRoute::Values ? pk->h_eval : route == HRoute::Quot ? pk->h_quot : pk->h;
+  const size_t n_harr = route == HRoute::Values ? pk->n_e : route == HRoute::Quot ? pk->n_q : pk->n_h;
   // every table of the call is stamped before one is built (an allocation for the first group must not evict the second group's), and
   // under policy `auto` the call grants itself a build credit for its job-units over w and h (a G1 sum = 1, the G2 sum = 2.76: ~6.8
   // for a Groth16 proof; tables.h, prepare_tables)
@@ -264,7 +270,7 @@ int proof_enqueue(Ctx& c, ProverKey* pk, DevScalars w, DevScalars px, const Shar
   double credit = build_credit((double)ng + 2.76 + 1.0, whi - wlo);
   const bool tab_w = prepare_tables(c, refs_w, (uint32_t)(whi - wlo), &cw, &credit);
   const bool tab_h = prepare_tables(c, {TableRef{&harr.table, harr.pts.as<uint32_t>(), n_harr, false}}, (uint32_t)(hhi - hlo), &ch, &credit);
-  if (!quot) hxbuf.ensure(std::max<size_t>(nh, 1) * 32);
+  if (route != HRoute::Quot) hxbuf.ensure(std::max<size_t>(nh, 1) * 32);
   auto base_w = [&](KeyArray& a) { return MsmBase{&a.table, wbase, a.pts.as<uint32_t>(), pk->n_w}; };
   st.pk = pk;
   st.total = std::make_unique<PhaseTimer>(c.main_stream);
@@ -272,16 +278,8 @@ int proof_enqueue(Ctx& c, ProverKey* pk, DevScalars w, DevScalars px, const Shar
   MsmPlan plan_w, plan_h;
   // The main stream carries NOTHING but the ALU-bound bucket accumulations (G2, then the G1 arrays over w, then h),
   // so with two proofs in flight it never idles: both plans, H(x) and every combine/reduce tail run on the aux streams.
-  const ProofStreams ps = proof_streams(c, pipelined, whi - wlo, (bool)px.produce_hv || (bool)px.produce_hx || (bool)px.produce, parity);   // (not hv_slice: no polynomial work here)
+  const ProofStreams ps = proof_streams(c, pipelined, whi - wlo, r1cs != nullptr, parity);   // (not a values slice: no polynomial work here)
   st.streams = ps;
-  if (w.host && w.host_done) {                                   // host-buffer ticket, GS_HOST_STAGE=2: w is copied on the plan(w) stream itself
-    staged_h2d(c, const_cast<uint32_t*>(w.p), w.host, w.n * 32, ps.planw);
-    GS_HIP(hipEventRecord(w.host_done, ps.planw));
-    if (ps.poly != ps.planw) GS_HIP(hipStreamWaitEvent(ps.poly, w.host_done, 0));
-  } else if (w.host_done) {                                      // w was staged on the copy stream: its readers wait for the DMA
-    GS_HIP(hipStreamWaitEvent(ps.planw, w.host_done, 0));
-    if (ps.poly != ps.planw) GS_HIP(hipStreamWaitEvent(ps.poly, w.host_done, 0));
-  }
   const size_t nterms_w = whi - wlo;
   st.split_b = pk->b_index.p != nullptr && nterms_w >= 4096 && !plan_partitions_first(cw) && pk->b_finite * 100 < (size_t)split_b_percent() * pk->n_w;
   MsmPlan plan_b;
@@ -327,40 +325,37 @@ int proof_enqueue(Ctx& c, ProverKey* pk, DevScalars w, DevScalars px, const Shar
   // got SLOWER, 11.5-11.7 vs 11.0-11.25 ms -- the NTT passes then overlap the G2 accumulation's first milliseconds more densely.)
   auto enqueue_poly = [&] {                                      // aux 1 again: (late upload of px,) H(x), plan(h)
     StreamScope sc(c, ps.poly);
-    if (px.host && px.n && px.host_stream) {   // host-buffer ticket: on the copy stream, beside whatever aux 1 still carries of the previous proof
-      staged_h2d(c, const_cast<uint32_t*>(px.p), px.host, px.n * 32, px.host_stream);
-      if (host_stage_mode() == 1) GS_HIP(hipStreamSynchronize(px.host_stream));
-      else {
-        GS_HIP(hipEventRecord(px.host_done, px.host_stream));
-        GS_HIP(hipStreamWaitEvent(c.stream, px.host_done, 0));
-      }
-    } else if (px.host && px.n && pipelined) {      // host-buffer ticket, GS_HOST_STAGE=2: in stream order on the polynomial stream, no host wait
-      staged_h2d(c, const_cast<uint32_t*>(px.p), px.host, px.n * 32, c.stream);
-    } else if (px.host && px.n) {     // the device is already busy with ~8 ms of accumulations: this copy is off the critical path
+    if (const auto* h = std::get_if<PxOnHost>(&src); h && h->n) {   // the device is already busy with ~8 ms of accumulations: this copy is off the critical path
       PhaseTimer th(c.stream);
-      staged_h2d(c, const_cast<uint32_t*>(px.p), px.host, px.n * 32, c.stream);
+      staged_h2d(c, h->stage, h->host, h->n * 32, c.stream);
       th.stop();
       c.timing.h2d_ms += th.ms();
     }
-    const bool no_poly = quot && !px.produce;                                    // nothing between px and plan(h): no polynomial phase to time
+    const bool no_poly = route == HRoute::Quot && !r1cs;                         // nothing between px and plan(h): no polynomial phase to time
     if (!no_poly) st.tpoly = std::make_shared<PhaseTimer>(c.stream);
-    bool have_hx = false;
-    if (px.hv_slice) have_hx = true;                                           // H's values came from another rank
-    else if (eval) {                                                           // H's values, for the evaluation-basis table
-      px.produce_hv(c, hxbuf.as<uint32_t>(), c.bad_dev.as<uint32_t>() + parity);
-      GS_HIP(hipMemcpyAsync(c.bad_host + parity, c.bad_dev.as<uint32_t>() + parity, 4, hipMemcpyDeviceToHost, c.stream));
-      st.bad_host = c.bad_host + parity;
-      have_hx = true;
-    }
-    if (!have_hx && px.produce_hx && nh) have_hx = px.produce_hx(c, hxbuf.as<uint32_t>());  // H from the constraint values (satisfying witness)
-    if (!have_hx) {
-      if (px.produce) px.produce(c);                                           // r1csqap.go:161-210 on the sparse system
-      if (nh && !quot) poly_quotient_dev(c, pk->z, px.p, px.n, hxbuf.as<uint32_t>());    // groth16.go:266, snark.go:280
+    uint32_t* hx = hxbuf.as<uint32_t>();
+    const size_t dz = pk->nz - 1;
+    switch (route) {
+      case HRoute::Values:                                                       // (a slice of H's values came from another rank)
+        if (wit) {
+          witness_values(c, *wit, dz, hx, c.bad_dev.as<uint32_t>() + parity);
+          GS_HIP(hipMemcpyAsync(c.bad_host + parity, c.bad_dev.as<uint32_t>() + parity, 4, hipMemcpyDeviceToHost, c.stream));
+          st.bad_host = c.bad_host + parity;
+        }
+        break;
+      case HRoute::Quot:
+        if (r1cs) r1cs_px_dev(c, *r1cs, r1cs_w, const_cast<uint32_t*>(px));
+        break;
+      case HRoute::Hx:
+        if (wit && nh && witness_hx(c, *wit, dz, hx)) break;                     // H from the constraint values (satisfying witness)
+        if (r1cs) r1cs_px_dev(c, *r1cs, r1cs_w, const_cast<uint32_t*>(px));
+        if (nh) poly_quotient_dev(c, pk->z, px, npx, hx);                        // groth16.go:266, snark.go:280
+        break;
     }
     if (st.tpoly) st.tpoly->stop();
     st.tplanh = std::make_shared<PhaseTimer>(c.stream);
     // the scalars of the h-sum: H's values of this slice, px's coefficients from deg Z up (any 256-bit words: k_digits canonicalises), or hx
-    const uint32_t* hscal = px.hv_slice ? px.hv_slice : quot ? px.p + (pk->nz - 1 + hlo) * 8 : hxbuf.as<uint32_t>() + hlo * 8;
+    const uint32_t* hscal = values ? values->values : route == HRoute::Quot ? px + (dz + hlo) * 8 : hx + hlo * 8;
     build_plan(c, 1 + 2 * parity, hscal, (uint32_t)(hhi - hlo), plan_h, {{1, false}}, ch, !tab_h);
     st.tplanh->stop();
     GS_HIP(hipEventRecord(st.planh, c.stream));
@@ -420,7 +415,7 @@ int proof_collect(Ctx& c, ProofInFlight& st, ProofSums& sums) {
   if (st.tpoly) c.timing.poly_ms += st.tpoly->ms();
   c.timing.plan_ms += st.tplanw->ms() + st.tplanh->ms();
   c.timing.total_ms += st.total->ms();
-  if (st.in.th2d) c.timing.h2d_ms += st.in.th2d->ms();
+  if (st.th2d) c.timing.h2d_ms += st.th2d->ms();
   sums.g2w = g2w[0]; sums.h = g1h[0];
   // evaluation-basis route: H's values only determine H when A B - C vanishes at every root of Z
   if (st.bad_host && *st.bad_host != 0) return kRetryExact;
@@ -429,20 +424,20 @@ int proof_collect(Ctx& c, ProofInFlight& st, ProofSums& sums) {
 
 // The blocking proof: enqueue, collect, and once more through px and the floor quotient when the evaluation-basis route met a
 // violated constraint.  `on_g1w` (ProofInFlight) rides on the first pass only: the sums over w do not depend on the route.
-int proof_sums_blocking(Ctx& c, ProverKey* pk, DevScalars w, DevScalars px, const Shard& shard, ProofSums& sums,
+int proof_sums_blocking(Ctx& c, ProverKey* pk, DevVec w, HSource src, const Shard& shard, ProofSums& sums,
                         std::function<void(const std::vector<G1Xyzz>&)> on_g1w = nullptr) {
   for (;;) {
     const double t0 = host_trace() ? host_now_ms() : 0;
     ProofInFlight st;
     st.on_g1w = std::move(on_g1w);
     on_g1w = nullptr;
-    int rc = proof_enqueue(c, pk, w, px, shard, c.blocking_slot(), true, false, st);
+    int rc = proof_enqueue(c, pk, w, src, shard, c.blocking_slot(), true, false, st);
     if (rc != GS_OK) return rc;
     const double t1 = host_trace() ? host_now_ms() : 0;
     rc = proof_collect(c, st, sums);
     if (host_trace()) fprintf(stderr, "[gs host] prove: enqueue %.3f ms, collect %.3f ms (entered at %.3f)\n", t1 - t0, host_now_ms() - t1, t0);
     if (rc != kRetryExact) return rc;
-    px.produce_hv = nullptr;                   // violated constraint: once more through px and the floor quotient
+    src = exact_retry(src, c.blocking_slot());   // violated constraint: once more through px and the floor quotient
     c.timing.fallbacks += 1;
   }
 }
@@ -521,13 +516,13 @@ struct GrothInFlight : ProofInFlight {      // what a Groth16 ticket carries bes
   GrothTail tail;
 };
 
-int groth16_prove_impl(Ctx& c, GrothPkObj* pk, DevScalars w, DevScalars px, const uint64_t r[4], const uint64_t s[4],
+int groth16_prove_impl(Ctx& c, GrothPkObj* pk, DevVec w, const HSource& src, const uint64_t r[4], const uint64_t s[4],
                        uint64_t out_proof[32], int inf[3]) {
   // the result-independent tail products run on other host cores while this thread enqueues and waits for the device
   GrothTail tail;
   tail.start(pk, r, s);
   ProofSums sums;
-  const int rc = proof_sums_blocking(c, pk, w, px, Shard{}, sums, [&tail](const std::vector<G1Xyzz>& g1w) { tail.early(g1w); });
+  const int rc = proof_sums_blocking(c, pk, w, src, Shard{}, sums, [&tail](const std::vector<G1Xyzz>& g1w) { tail.early(g1w); });
   if (rc != GS_OK) return rc;
   const double t2 = host_trace() ? host_now_ms() : 0;
   tail.finish(sums, out_proof, inf);
@@ -572,16 +567,11 @@ void pinocchio_pack(const ProofSums& sums, uint64_t out[72], int inf[8]) {
   inf[6] = g1_to_affine_std(sums.h, out + 56) ? 1 : 0;
   inf[7] = g1_to_affine_std(sums.g1w[PinocchioPkObj::kKp], out + 64) ? 1 : 0;
 }
-int pinocchio_prove_impl(Ctx& c, PinocchioPkObj* pk, DevScalars w, DevScalars px, uint64_t out[72], int inf[8], const Shard& shard = Shard{}) {
+int pinocchio_prove_impl(Ctx& c, PinocchioPkObj* pk, DevVec w, const HSource& src, uint64_t out[72], int inf[8], const Shard& shard = Shard{}) {
   ProofSums sums;
-  const int rc = proof_sums_blocking(c, pk, w, px, shard, sums);
+  const int rc = proof_sums_blocking(c, pk, w, src, shard, sums);
   if (rc == GS_OK) pinocchio_pack(sums, out, inf);
   return rc;
-}
-
-// zero the first `count` packed points (-> infinity)
-void force_infinity(Ctx& c, DevBuf& pts, size_t count, size_t words) {
-  if (count) GS_HIP(hipMemsetAsync(pts.p, 0, count * words * 4, c.stream));
 }
 
 // ---- host-buffer tickets -----------------------------------------------------------------------------------------------------
@@ -589,48 +579,20 @@ void force_infinity(Ctx& c, DevBuf& pts, size_t count, size_t words) {
 // gs_scalars_upload + gs_*_begin + gs_free costs a hipMalloc, a blocking copy and a hipFree (a device-wide synchronisation) per proof
 // and breaks a pipeline of three; a host-buffer ticket instead stages the caller's arrays into buffers its SLOT owns (grow-only:
 // nothing is allocated or freed once the three slots have been used), on the copy stream -- the DMA of proof k + 3 runs beside the
-// accumulations of proofs k + 1 and k + 2 -- and enqueues the proof when the copy has landed (GS_HOST_STAGE above: measured against
-// a cross-stream event and against copying on the readers' own streams).  The caller's arrays are consumed when _begin returns (cgo
-// pointer rule).
-static void ensure_copy_stream(Ctx& c) {
-  if (!c.copy_stream) GS_HIP(hipStreamCreateWithFlags(&c.copy_stream, hipStreamNonBlocking));
-}
-// px_follows: slot_px_from_host stages px on the same stream right after and waits for both (one DMA tail instead of two)
-DevScalars stage_slot_w(Ctx& c, int parity, const uint64_t* host, size_t n, HostInputs& in, bool px_follows = false) {
-  ensure_copy_stream(c);
-  in.create();
-  DevBuf& b = prove_state(c).slot_w[parity];
+// accumulations of proofs k + 1 and k + 2 -- and enqueues the proof when the copies have landed: the host waits for them once, after
+// px when px follows w (one DMA tail instead of two), so what the engine sees are ordinary device vectors.  The host has nothing
+// else to do then -- the device is busy with the two tickets before this one.  Measured at 2^20, three in flight, eight rotating
+// witnesses (profiles/r05_ab_host_stage.txt) against a cross-stream event that the readers wait for, and against copying on the
+// readers' own streams:  witness from the host 10.12-10.17 ms against 11.2-11.3 / 10.1-11.0,  w + px from the host 9.45-9.51 against
+// 10.9 / 11.4-11.5 (resident: 10.03-10.07 / 8.84-9.01).  The caller's arrays are consumed when _begin returns (cgo pointer rule).
+static const uint32_t* stage_on_copy_stream(Ctx& c, DevBuf& b, const uint64_t* host, size_t n) {
   b.ensure(std::max<size_t>(n, 1) * 32);
-  DevScalars d{b.as<uint32_t>(), n};
-  if (host_stage_mode() == 2) {          // copied by the enqueue function on the plan(w) stream
-    d.host = host;
-    d.host_done = in.w_done;
-    return d;
-  }
-  in.th2d = std::make_shared<PhaseTimer>(c.copy_stream);
   if (n) staged_h2d(c, b.p, host, n * 32, c.copy_stream);
-  if (host_stage_mode() == 1) { if (!px_follows) GS_HIP(hipStreamSynchronize(c.copy_stream)); }
-  else {
-    GS_HIP(hipEventRecord(in.w_done, c.copy_stream));
-    d.host_done = in.w_done;
-  }
-  return d;
+  return b.as<uint32_t>();
 }
-// px: staged by the enqueue function AFTER the accumulations over w were queued (they do not need it), on the copy stream
-DevScalars slot_px_from_host(Ctx& c, int parity, const uint64_t* host, size_t n, HostInputs& in) {
-  ensure_copy_stream(c);
-  in.create();
-  DevBuf& b = prove_state(c).slot_px[parity];
-  b.ensure(std::max<size_t>(n, 1) * 32);
-  if (host_stage_mode() == 1) {          // landed before anything of the proof is enqueued (the device is busy with the tickets before this one)
-    if (n) staged_h2d(c, b.p, host, n * 32, c.copy_stream);
-    GS_HIP(hipStreamSynchronize(c.copy_stream));
-    return DevScalars{b.as<uint32_t>(), n};
-  }
-  DevScalars d{b.as<uint32_t>(), n, host};
-  d.host_stream = host_stage_mode() == 2 ? nullptr : c.copy_stream;      // (nullptr: on the polynomial stream itself, as the blocking entry points do)
-  d.host_done = in.px_done;
-  return d;
+DevVec stage_slot_w(Ctx& c, int parity, const uint64_t* host, size_t n) { return DevVec{stage_on_copy_stream(c, prove_state(c).slot_w[parity], host, n), n}; }
+PxResident slot_px_from_host(Ctx& c, int parity, const uint64_t* host, size_t n) {
+  return PxResident{stage_on_copy_stream(c, prove_state(c).slot_px[parity], host, n), n};
 }
 // a resident vector that a ticket reads: gs_scalars_update must wait for these points (runtime.h, Scalars::reads)
 void mark_ticket_reads(const ProofStreams& ps, Scalars* w, Scalars* px_or_hv) {
@@ -674,53 +636,8 @@ int check_coset_only_route(const Ctx& c, const char* fn, const ProverKey* pk, co
   return pk->coset_only && !eval_route(c, pk, o) ? refuse_coset_only(fn) : GS_OK;
 }
 
-// the three ways to the h-scalars of a witness proof, in the order the prover tries them (a domain R1CS has two: the coset
-// evaluation-basis route, then px -- its quotient by x^m - 1 goes through the key's Divisor / quotient-basis array like any Z)
-// `check`: count the violated constraints, so that the proof can be redone on the exact route.  Off for a product system (c = a b by
-// definition: nothing to check) and for a coset-only key (no exact route to go to): the count is 0, and a wrong witness gives a proof
-// that the verifier rejects, as in snarkjs.
-DevScalars witness_scalars(R1csObj* o, const uint32_t* wdev, size_t nz, bool eval, std::function<uint32_t*(Ctx&)> px_buffer, bool check = true) {
-  const size_t npx = o->npx(), dz = nz - 1;
-  DevScalars dp{nullptr, npx};
-  if (o->domain_log2) {
-    const int k = o->domain_log2;
-    if (eval)
-      dp.produce_hv = [o, wdev, k, check](Ctx& cc, uint32_t* hv, uint32_t* bad) {
-        r1cs_values_dev(cc, *o, wdev);
-        if (check) r1cs_check_domain_dev(cc, o->vals.as<uint32_t>(), k, bad);
-        else GS_HIP(hipMemsetAsync(bad, 0, 4, cc.stream));
-        hx_values_domain_dev(cc, o->vals.as<uint32_t>(), k, hv);
-      };
-    dp.produce = [o, wdev, px_buffer](Ctx& cc) { r1cs_px_dev(cc, *o, wdev, px_buffer(cc)); };
-    return dp;
-  }
-  if (eval)
-    dp.produce_hv = [o, wdev, dz](Ctx& cc, uint32_t* hv, uint32_t* bad) {
-      r1cs_values_dev(cc, *o, wdev);
-      r1cs_check_dev(cc, o->vals.as<uint32_t>(), o->n, dz, bad);
-      hx_values_dev(cc, o->vals.as<uint32_t>(), o->n, dz, hv);
-    };
-  dp.produce_hx = [o, wdev, dz](Ctx& cc, uint32_t* hx) { r1cs_values_dev(cc, *o, wdev); return hx_direct_dev(cc, o->vals.as<uint32_t>(), o->n, dz, hx); };
-  dp.produce = [o, wdev, px_buffer](Ctx& cc) { r1cs_px_dev(cc, *o, wdev, px_buffer(cc)); };
-  return dp;
-}
-// px of the exact route: one buffer per slot (the three tickets and the blocking entry points), allocated only if that route is
-// ever taken.  Round 3 handed every in-flight ticket -- and the blocking entry points' host uploads -- the SAME staging buffer and
-// leaned on all polynomial stages being serialised on one stream (ADVICE r3); a slot's buffer is only ever touched by the
-// operation that owns the slot, and a slot is re-used only after its operation was collected.
-uint32_t* exact_px_buffer(Ctx& c, R1csObj* o, int slot) {
-  const size_t npx = o->npx();
-  o->prod.ensure(npx * 32);
-  DevBuf& b = prove_state(c).exact_px[slot % Ctx::kSlots];
-  b.ensure(npx * 32);
-  return b.as<uint32_t>();
-}
-// the h-scalars of a BLOCKING witness proof (its px buffer is the blocking slot's)
-DevScalars witness_scalars_blocking(Ctx& c, R1csObj* o, const uint32_t* wdev, size_t nz, bool eval, bool check = true) {
-  uint32_t* pxdev = exact_px_buffer(c, o, c.blocking_slot());
-  DevScalars dp = witness_scalars(o, wdev, nz, eval, [pxdev](Ctx&) { return pxdev; }, check);
-  dp.p = pxdev;
-  return dp;
+WitnessSource witness_source(const ProverKey* pk, R1csObj* o, const uint32_t* wdev, int slot, bool eval_open) {   // of a proof in `slot`
+  return WitnessSource{o, wdev, slot, !o->product && !pk->coset_only, eval_open};
 }
 
 // What a blocking witness entry point checks beyond its handles, as each did before they shared this preamble (the two schemes
@@ -732,7 +649,7 @@ struct WitnessChecks {
 // The preamble of the blocking witness entry points, after the handle / null checks: shapes, the witness onto the device (`w`
 // resident, or `w_host` uploaded as part of the call), the route.
 int witness_blocking_inputs(Ctx& c, const char* fn, ProverKey* pk, R1csObj* o, const Scalars* w, const uint64_t* w_host, size_t nw, const WitnessChecks& chk,
-                            DevScalars& dw, DevScalars& dp) {
+                            DevVec& dw, HSource& src) {
   if (nw != o->m) return fail(GS_ERR_SHAPE, "len(w) = %zu but the system has %zu variables", nw, o->m);
   if (chk.need_z && pk->nz == 0) return fail(GS_ERR_SHAPE, "the key has no Z");
   if (int rc = check_domain_pair(fn, pk, o)) return rc;
@@ -740,8 +657,8 @@ int witness_blocking_inputs(Ctx& c, const char* fn, ProverKey* pk, R1csObj* o, c
   reset_timing(c);
   const uint32_t* wdev = w ? w->buf.as<uint32_t>() : upload_tmp(c, prove_state(c).up_w, w_host, nw);
   const bool eval = !(chk.eval_full_key_only && pk->shard_count != 1) && eval_route(c, pk, o);
-  dw = DevScalars{wdev, nw};
-  dp = witness_scalars_blocking(c, o, wdev, pk->nz, eval, !o->product && !pk->coset_only);
+  dw = DevVec{wdev, nw};
+  src = witness_source(pk, o, wdev, c.blocking_slot(), eval);
   return GS_OK;
 }
 
@@ -765,8 +682,33 @@ struct TicketRequest {
   bool refuse_slice;                 // witness forms: refuse a key slice
   bool need_z;                       // witness forms: refuse a key with nz == 0
 };
+// Install a proof ticket once every check of its front has passed: the free slot (or GS_ERR_BUSY: "<fn>: three operations are already
+// outstanding; <busy_hint>"), the in-flight object from `make()` holding `keep` alive, its inputs from `inputs(slot, st)` -- which
+// sets st.w / st.src, staging a host-buffer ticket's arrays into the slot --, the enqueue, the read marks on the resident vectors,
+// the ticket number.
+template <class Make, class Inputs>
+int install_ticket(Ctx& c, const char* fn, const char* busy_hint, ProverKey* pk, std::vector<std::shared_ptr<Object>> keep, const Shard& shard,
+                   Scalars* w_resident, Scalars* h_resident, uint64_t* ticket, Make make, Inputs inputs) {
+  const int parity = c.free_parity();
+  if (parity < 0) return fail(GS_ERR_BUSY, "%s: three operations are already outstanding; %s", fn, busy_hint);
+  std::unique_ptr<ProofInFlight> st = make();
+  st->keep = std::move(keep);
+  const double h0 = host_trace() ? host_now_ms() : 0;
+  inputs(parity, *st);
+  const double h1 = host_trace() ? host_now_ms() : 0;
+  const int rc = proof_enqueue(c, pk, st->w, st->src, shard, parity, false, true, *st);
+  if (rc != GS_OK) return rc;
+  if (host_trace()) fprintf(stderr, "[gs host] begin: inputs %.3f ms, enqueue %.3f ms\n", h1 - h0, host_now_ms() - h1);
+  if (st->th2d) st->th2d->stop();
+  mark_ticket_reads(st->streams, w_resident, h_resident);
+  st->ticket = c.new_ticket();
+  *ticket = st->ticket;
+  c.inflight[parity] = std::move(st);
+  return GS_OK;
+}
 // `make` builds the in-flight object once every check has passed (Groth16 starts its tail there).
-int begin_ticket(Ctx& c, const TicketRequest& q, const std::function<std::unique_ptr<ProofInFlight>(ProverKey*)>& make) {
+template <class Make>
+int begin_ticket(Ctx& c, const TicketRequest& q, Make make) {
   const bool host = q.w_host != nullptr || q.px_host != nullptr;
   ProverKey* pk = c.get<ProverKey>(q.hpk, q.kind);
   R1csObj* o = q.witness ? c.get<R1csObj>(q.hr1cs, Kind::R1cs) : nullptr;
@@ -785,143 +727,36 @@ int begin_ticket(Ctx& c, const TicketRequest& q, const std::function<std::unique
   if (q.need_z && pk->nz == 0) return fail(GS_ERR_SHAPE, "the key has no Z");
   if (q.witness) if (int rc = check_domain_pair(q.fn, pk, o)) return rc;
   if (q.witness) if (int rc = check_coset_only_route(c, q.fn, pk, o)) return rc;
-  const int parity = c.free_parity();
-  if (parity < 0) return fail(GS_ERR_BUSY, "%s: three operations are already outstanding; call gs_%s_prove_end first", q.fn, pk->scheme);
-  std::unique_ptr<ProofInFlight> st = make(pk);
-  st->pk = pk;
-  st->keep = {c.share<Object>(q.hpk, q.kind)};
-  if (q.witness) st->keep.push_back(c.share<Object>(q.hr1cs, Kind::R1cs));
-  if (w) st->keep.push_back(c.share<Object>(q.hw, Kind::Scalars));
-  if (px) st->keep.push_back(c.share<Object>(q.hpx, Kind::Scalars));
-  const double h0 = host_trace() ? host_now_ms() : 0;
-  // (a host witness lives in the slot's buffer until the ticket is collected -- the exact-route retry below still finds it there)
-  const DevScalars dw = host ? stage_slot_w(c, parity, q.w_host, nw, st->in, !q.witness) : resident(w);
-  const double h1 = host_trace() ? host_now_ms() : 0;
-  DevScalars dp;
-  if (!q.witness) dp = host ? slot_px_from_host(c, parity, q.px_host, q.npx, st->in) : resident(px);
-  else {
-    const bool eval = eval_route(c, pk, o);
-    const uint32_t* wdev = dw.p;
-    const size_t nz = pk->nz;
-    dp = witness_scalars(o, wdev, nz, eval, [o, parity](Ctx& cc) { return exact_px_buffer(cc, o, parity); }, !o->product && !pk->coset_only);
-    if (!eval) {                               // the monomial route may have to write px at once (its check is a host wait inside enqueue)
-      dp.p = exact_px_buffer(c, o, parity);
-    } else {                                   // with an evaluation-basis key nothing in here waits for the device
-      dp.produce_hx = nullptr; dp.produce = nullptr;
-      st->exact_route = [pk, o, wdev, nw, nz](Ctx& cc, ProofSums& sums) {      // the retry is a blocking proof at collection time
-        return proof_sums_blocking(cc, pk, DevScalars{wdev, nw}, witness_scalars_blocking(cc, o, wdev, nz, false), Shard{}, sums);
-      };
+  std::vector<std::shared_ptr<Object>> keep = {c.share<Object>(q.hpk, q.kind)};
+  if (q.witness) keep.push_back(c.share<Object>(q.hr1cs, Kind::R1cs));
+  if (w) keep.push_back(c.share<Object>(q.hw, Kind::Scalars));
+  if (px) keep.push_back(c.share<Object>(q.hpx, Kind::Scalars));
+  const char* busy_hint = q.kind == Kind::GrothPk ? "call gs_groth16_prove_end first" : "call gs_pinocchio_prove_end first";
+  return install_ticket(c, q.fn, busy_hint, pk, std::move(keep), Shard{}, w, px, q.ticket, [&] { return make(pk); }, [&](int parity, ProofInFlight& st) {
+    if (host) {                                  // staged on the copy stream; one host wait for what was staged
+      if (!c.copy_stream) GS_HIP(hipStreamCreateWithFlags(&c.copy_stream, hipStreamNonBlocking));
+      st.th2d = std::make_shared<PhaseTimer>(c.copy_stream);
+      // (a host witness lives in the slot's buffer until the ticket is collected -- the exact-route retry still finds it there)
+      st.w = stage_slot_w(c, parity, q.w_host, nw);
+      if (!q.witness) st.src = slot_px_from_host(c, parity, q.px_host, q.npx);
+      GS_HIP(hipStreamSynchronize(c.copy_stream));
+    } else {
+      st.w = resident(w);
+      if (!q.witness) st.src = resident_px(px);
     }
-  }
-  const double h2 = host_trace() ? host_now_ms() : 0;
-  const int rc = proof_enqueue(c, pk, dw, dp, Shard{}, parity, false, true, *st);
-  if (rc != GS_OK) return rc;
-  if (host_trace()) fprintf(stderr, "[gs host] begin: stage w %.3f ms, stage px %.3f ms, enqueue %.3f ms\n", h1 - h0, h2 - h1, host_now_ms() - h2);
-  if (st->in.th2d) st->in.th2d->stop();
-  mark_ticket_reads(st->streams, w, px);
-  st->ticket = c.new_ticket();
-  *q.ticket = st->ticket;
-  c.inflight[parity] = std::move(st);
-  return GS_OK;
+    // (with an evaluation-basis key nothing in the enqueue waits for the device; the other witness routes check on the host in there)
+    if (q.witness) st.src = witness_source(pk, o, st.w.p, parity, eval_route(c, pk, o));
+  });
 }
 // Collect a proof ticket that the caller took out of its slot: the sums, by the exact route if the witness broke a constraint.
 int collect_ticket(Ctx& c, ProofInFlight& st, ProofSums& sums) {
   reset_timing(c);
-  int rc = proof_collect(c, st, sums);
-  if (rc == kRetryExact && st.exact_route) { c.timing.fallbacks += 1; rc = st.exact_route(c, sums); }
-  return rc;
+  const int rc = proof_collect(c, st, sums);
+  if (rc != kRetryExact) return rc;
+  c.timing.fallbacks += 1;                       // the retry is a blocking proof at collection time
+  return proof_sums_blocking(c, st.pk, st.w, exact_retry(st.src, c.blocking_slot()), Shard{}, sums);
 }
 
-// ---- keys ----------------------------------------------------------------------------------------------------------------------
-// the list of the variables with a finite point in either array: the device scans (one bit per variable), the host turns the bits
-// into the ascending index list and uploads it
-static size_t scan_finite_terms(Ctx& c, const uint32_t* g1_pts, const uint32_t* g2_pts, size_t n, DevBuf& index_dev, std::vector<uint32_t>& index_host) {
-  index_host.clear();
-  index_dev.release();
-  if (n == 0) return 0;
-  const size_t words = (n + 31) / 32;
-  DevBuf mask(words * 4);
-  const size_t finite = finite_mask_dev(c, g1_pts, g2_pts, (uint32_t)n, mask.as<uint32_t>());
-  if (finite == n) return finite;                        // nothing missing: no list, no second plan
-  std::vector<uint32_t> bits(words);
-  GS_HIP(hipMemcpyAsync(bits.data(), mask.p, words * 4, hipMemcpyDeviceToHost, c.stream));
-  GS_HIP(hipStreamSynchronize(c.stream));
-  index_host.reserve(finite);
-  for (size_t wd = 0; wd < words; ++wd)
-    for (uint32_t m = bits[wd]; m; m &= m - 1) index_host.push_back((uint32_t)(wd * 32 + (size_t)__builtin_ctz(m)));
-  index_dev.alloc(std::max<size_t>(index_host.size(), 1) * 4);
-  if (!index_host.empty()) {
-    GS_HIP(hipMemcpyAsync(index_dev.p, index_host.data(), index_host.size() * 4, hipMemcpyHostToDevice, c.stream));
-    GS_HIP(hipStreamSynchronize(c.stream));
-  }
-  return finite;
-}
-
-// Shared builder of full keys and key slices: copies [lo, lo + n) of each source array (device, packed affine).
-struct PkSrc { const DevBuf* buf; size_t lo; };
-// `from`: the context the source arrays live on (another GPU for gs_*_pk_shard_to)
-static void copy_slice(Ctx& c, Ctx& from, const PkSrc& s, size_t n, size_t words, DevBuf& dst) {
-  dst.alloc(std::max<size_t>(n, 1) * words * 4);
-  copy_between(c, dst.p, from, static_cast<const char*>(s.buf->p) + s.lo * words * 4, n * words * 4);
-}
-// groth16.go:177-180 / :248: the C sum runs over i > NPublic; global entries [0, NPublic] of BACDelta become infinity
-static void groth_force_public(Ctx& c, GrothPkObj& pk) {
-  const size_t zero_hi = std::min(pk.npublic + 1, pk.w_lo + pk.n_w);
-  if (zero_hi > pk.w_lo) force_infinity(c, pk.bacdelta(), zero_hi - pk.w_lo, kG1Aff);
-}
-static void set_shard(ProverKey& pk, size_t index, size_t count) {
-  Shard sh; sh.index = index; sh.count = count;
-  size_t lo, hi;
-  pk.shard_index = index; pk.shard_count = count;
-  shard_range(pk.nvars, sh, lo, hi);
-  pk.w_lo = lo; pk.n_w = hi - lo;
-  shard_range(pk.len_h, sh, lo, hi);
-  pk.h_lo = lo; pk.n_h = hi - lo;
-}
-// what a slice takes over from the full key beside the arrays
-static void shard_extras(Ctx& c, GrothPkObj& pk, const GrothPkObj& full) {
-  groth_force_public(c, pk);
-  pk.alpha = full.alpha; pk.beta = full.beta; pk.delta = full.delta; pk.beta2 = full.beta2; pk.delta2 = full.delta2;
-}
-// (A / Ap of the full key already hold infinity for i <= NPublic, snark.go:265: the slices inherit it)
-static void shard_extras(Ctx&, PinocchioPkObj&, const PinocchioPkObj&) {}
-
-// A slice of a resident full key (device-to-device copies): what each rank keeps when the full key was built or loaded
-// locally; the caller then frees the full key.  `c` is the context the slice is created on -- the key's own, or another
-// logical device's (gs_*_pk_shard_to: the copies then cross xGMI, or stay on the GPU when both share one).
-template <class Pk>
-static int pk_shard_impl(Ctx& c, Ctx& from, const char* scheme, Pk* full, size_t shard_index, size_t shard_count, gs_handle* out) {
-  if (!full || !out) return fail(GS_ERR_ARG, "gs_%s_pk_shard: bad proving-key handle or null output", scheme);
-  if (full->shard_count != 1) return fail(GS_ERR_ARG, "gs_%s_pk_shard: the source key is itself a slice", scheme);
-  if (full->coset_only) return refuse_coset_only("gs_groth16_pk_shard");
-  if (shard_count == 0 || shard_index >= shard_count) return fail(GS_ERR_ARG, "gs_%s_pk_shard: bad shard %zu of %zu", scheme, shard_index, shard_count);
-  auto pk = std::make_unique<Pk>();
-  pk->nvars = full->nvars; pk->npublic = full->npublic; pk->nz = full->nz; pk->len_h = full->len_h;
-  set_shard(*pk, shard_index, shard_count);
-  for (int i = 0; i < pk->n_g1w; ++i) copy_slice(c, from, PkSrc{&full->g1w[i].pts, pk->w_lo}, pk->n_w, kG1Aff, pk->g1w[i].pts);
-  copy_slice(c, from, PkSrc{&full->h.pts, pk->h_lo}, pk->n_h, kG1Aff, pk->h.pts);
-  copy_slice(c, from, PkSrc{&full->g2w.pts, pk->w_lo}, pk->n_w, kG2Aff, pk->g2w.pts);
-  if (full->n_eval && !full->eval_domain_log2) {        // the evaluation-basis array is cut like the other term ranges (its own split of [0, n)); a coset basis (domain.h) stays behind
-    Shard sh; sh.index = shard_index; sh.count = shard_count;
-    size_t lo, hi;
-    shard_range(full->n_eval, sh, lo, hi);
-    pk->n_eval = full->n_eval; pk->e_lo = lo; pk->n_e = hi - lo;
-    copy_slice(c, from, PkSrc{&full->h_eval.pts, lo}, pk->n_e, kG1Aff, pk->h_eval.pts);
-  }
-  shard_extras(c, *pk, *full);
-  {                                                     // Z travels with every slice
-    DevBuf zc(std::max<size_t>(full->nz, 1) * 32);
-    copy_between(c, zc.p, from, full->z.b_std.p, full->nz * 32);
-    divisor_init(c, pk->z, zc.as<uint32_t>(), full->nz);
-    GS_HIP(hipStreamSynchronize(c.stream));             // `zc` is released here
-  }
-  GS_HIP(hipStreamSynchronize(c.stream));
-  pk_scan_sparsity(c, *pk);
-  *out = c.put(std::move(pk));
-  return GS_OK;
-}
-
-bool bad_shard(size_t shard_index, size_t shard_count) { return shard_count == 0 || shard_index >= shard_count; }
 // gs_*_prove_partials_values: the vector must hold exactly the values of the shard's evaluation-basis range
 int check_values_slice(const char* fn, ProverKey* pk, const Scalars* hv, const Shard& sh, bool say_shard) {
   if (pk->n_eval == 0) return fail(GS_ERR_SHAPE, "%s: the key has no evaluation-basis array", fn);
@@ -932,168 +767,10 @@ int check_values_slice(const char* fn, ProverKey* pk, const Scalars* hv, const S
   if (!say_shard) return fail(GS_ERR_SHAPE, "%s: the shard covers %zu values, the vector holds %zu", fn, hi - lo, hv->n);
   return fail(GS_ERR_SHAPE, "%s: shard %zu of %zu covers %zu of the %zu values, the vector holds %zu", fn, sh.index, sh.count, hi - lo, pk->n_eval, hv->n);
 }
-DevScalars values_slice(const Scalars* hv) {
-  DevScalars dh{nullptr, 0};
-  dh.hv_slice = hv->buf.as<uint32_t>();
-  return dh;
-}
 
 }  // namespace
 
-void gs::pk_scan_sparsity(Ctx& c, ProverKey& pk) {
-  pk.b_finite = scan_finite_terms(c, pk.g1w[pk.b_g1].pts.as<uint32_t>(), pk.g2w.pts.as<uint32_t>(), pk.n_w, pk.b_index, pk.b_index_host);
-}
-
 extern "C" {
-
-// ---- Groth16 ----------------------------------------------------------------------------------------------
-// k >= 1 when Z (nz coefficients, any representatives mod r) is exactly x^m - 1 with m = 2^k <= 2^27, else 0: the keys of a QAP over a
-// power-of-two domain (domain.h).  Host work, once per key.
-static int z_domain_log2(const uint64_t* z, size_t nz) {
-  if (nz < 3 || ((nz - 1) & (nz - 2)) != 0 || nz - 1 > ((size_t)1 << kDomainMaxLog2)) return 0;
-  const size_t m = nz - 1;
-  const uint64_t zero[4] = {0, 0, 0, 0}, one[4] = {1, 0, 0, 0};
-  uint64_t d[4];
-  fr_sub_words(z + 4 * m, one, d);
-  if (!fr_is_zero_words(d)) return 0;
-  fr_sub_words(zero, z, d);                              // -z[0] - 1
-  fr_sub_words(d, one, d);
-  if (!fr_is_zero_words(d)) return 0;
-  for (size_t i = 1; i < m; ++i) {
-    const uint64_t* v = z + 4 * i;
-    if ((v[0] | v[1] | v[2] | v[3]) != 0 && !fr_is_zero_words(v)) return 0;
-  }
-  return ceil_log2(m);
-}
-static int groth_pk_create_impl(Ctx& c, gs_handle g1_at, gs_handle g1_bacgamma, gs_handle g2_bacgamma, gs_handle bacdelta, gs_handle ptd,
-                                const uint64_t g1_alpha[12], const uint64_t g1_beta[12], const uint64_t g1_delta[12],
-                                const uint64_t g2_beta[24], const uint64_t g2_delta[24], const uint64_t* z, size_t nz,
-                                size_t nvars, size_t npublic, size_t nptd_total, size_t shard_index, size_t shard_count, gs_handle* out) {
-  Bases* at = c.get<Bases>(g1_at, Kind::G1Bases);
-  Bases* b1 = c.get<Bases>(g1_bacgamma, Kind::G1Bases);
-  Bases* b2 = c.get<Bases>(g2_bacgamma, Kind::G2Bases);
-  Bases* cd = c.get<Bases>(bacdelta, Kind::G1Bases);
-  Bases* pt = c.get<Bases>(ptd, Kind::G1Bases);
-  if (!at || !b1 || !b2 || !cd || !pt) return fail(GS_ERR_ARG, "gs_groth16_pk_create: bad base handle");
-  if (!g1_alpha || !g1_beta || !g1_delta || !g2_beta || !g2_delta || !z || !out || nz == 0) return fail(GS_ERR_ARG, "null argument");
-  if (bad_shard(shard_index, shard_count)) return fail(GS_ERR_ARG, "gs_groth16_pk_create_shard: bad shard %zu of %zu", shard_index, shard_count);
-  if (npublic + 1 > nvars) return fail(GS_ERR_SHAPE, "NPublic + 1 > NVars");
-  bool lead_zero = true;
-  for (int i = 0; i < 4; ++i) lead_zero = lead_zero && z[4 * (nz - 1) + i] == 0;
-  if (lead_zero) return fail(GS_ERR_ARG, "leading coefficient of Z is zero");
-  auto pk = std::make_unique<GrothPkObj>();
-  pk->nvars = nvars; pk->npublic = npublic; pk->nz = nz; pk->len_h = shard_count == 1 ? pt->n : nptd_total;
-  set_shard(*pk, shard_index, shard_count);
-  if (at->n != pk->n_w || b1->n != pk->n_w || b2->n != pk->n_w || cd->n != pk->n_w)
-    return fail(GS_ERR_SHAPE, "At/BACGamma/BACDelta must have %zu points (NVars = %zu, shard %zu of %zu), got %zu/%zu/%zu/%zu", pk->n_w, nvars,
-                shard_index, shard_count, at->n, b1->n, b2->n, cd->n);
-  if (pt->n != pk->n_h)
-    return fail(GS_ERR_SHAPE, "PowersTauDelta must have %zu points (total %zu, shard %zu of %zu), got %zu", pk->n_h, pk->len_h, shard_index, shard_count, pt->n);
-  copy_points(c, at, kG1Aff, pk->at());
-  copy_points(c, b1, kG1Aff, pk->bacgamma1());
-  copy_points(c, cd, kG1Aff, pk->bacdelta());
-  copy_points(c, pt, kG1Aff, pk->ptd());
-  copy_points(c, b2, kG2Aff, pk->bacgamma2());
-  groth_force_public(c, *pk);
-  pk->alpha = g1_affine_from_jacobian_std(g1_alpha);
-  pk->beta = g1_affine_from_jacobian_std(g1_beta);
-  pk->delta = g1_affine_from_jacobian_std(g1_delta);
-  pk->beta2 = g2_affine_from_jacobian_std(g2_beta);
-  pk->delta2 = g2_affine_from_jacobian_std(g2_delta);
-  if (shard_count == 1) pk->domain_log2 = z_domain_log2(z, nz);
-  const uint32_t* dz = upload_tmp(c, prove_state(c).up_a, z, nz);
-  divisor_init(c, pk->z, dz, nz);
-  GS_HIP(hipStreamSynchronize(c.stream));
-  pk_scan_sparsity(c, *pk);
-  *out = c.put(std::move(pk));
-  return GS_OK;
-}
-
-int gs_groth16_pk_create(gs_handle g1_at, gs_handle g1_bacgamma, gs_handle g2_bacgamma, gs_handle bacdelta, gs_handle ptd,
-                         const uint64_t g1_alpha[12], const uint64_t g1_beta[12], const uint64_t g1_delta[12],
-                         const uint64_t g2_beta[24], const uint64_t g2_delta[24], const uint64_t* z, size_t nz,
-                         size_t nvars, size_t npublic, gs_handle* out) {
-  return guarded([&](Ctx& c) -> int {
-    return groth_pk_create_impl(c, g1_at, g1_bacgamma, g2_bacgamma, bacdelta, ptd, g1_alpha, g1_beta, g1_delta, g2_beta, g2_delta, z, nz,
-                                nvars, npublic, 0, 0, 1, out);
-  }, true, false, g1_at);
-}
-
-// A coset-only key (prove.h): the five arrays and five points of gs_groth16_pk_create, but in place of PowersTauDelta the m = 2^log2_domain
-// points of the coset evaluation basis E (domain.h) -- section 9 of a snarkjs .zkey.  Z = x^m - 1 is built here.
-int gs_groth16_pk_create_domain(gs_handle g1_at, gs_handle g1_bacgamma, gs_handle g2_bacgamma, gs_handle bacdelta, gs_handle h_coset,
-                                const uint64_t g1_alpha[12], const uint64_t g1_beta[12], const uint64_t g1_delta[12],
-                                const uint64_t g2_beta[24], const uint64_t g2_delta[24], size_t log2_domain, size_t nvars, size_t npublic, gs_handle* out) {
-  return guarded([&](Ctx& c) -> int {
-    const char* fn = "gs_groth16_pk_create_domain";
-    Bases* at = c.get<Bases>(g1_at, Kind::G1Bases);
-    Bases* b1 = c.get<Bases>(g1_bacgamma, Kind::G1Bases);
-    Bases* b2 = c.get<Bases>(g2_bacgamma, Kind::G2Bases);
-    Bases* cd = c.get<Bases>(bacdelta, Kind::G1Bases);
-    Bases* he = c.get<Bases>(h_coset, Kind::G1Bases);
-    if (!at || !b1 || !b2 || !cd || !he) return fail(GS_ERR_ARG, "%s: bad base handle", fn);
-    if (!g1_alpha || !g1_beta || !g1_delta || !g2_beta || !g2_delta || !out) return fail(GS_ERR_ARG, "%s: null argument", fn);
-    if (log2_domain < 1 || log2_domain > (size_t)kDomainMaxLog2) return fail(GS_ERR_ARG, "%s: log2_domain = %zu, must be 1 .. %d", fn, log2_domain, kDomainMaxLog2);
-    if (npublic + 1 > nvars) return fail(GS_ERR_SHAPE, "NPublic + 1 > NVars");
-    const size_t m = (size_t)1 << log2_domain, nz = m + 1;
-    if (at->n != nvars || b1->n != nvars || b2->n != nvars || cd->n != nvars)
-      return fail(GS_ERR_SHAPE, "%s: At/BACGamma/BACDelta must have NVars = %zu points, got %zu/%zu/%zu/%zu", fn, nvars, at->n, b1->n, b2->n, cd->n);
-    if (he->n != m) return fail(GS_ERR_SHAPE, "%s: the coset evaluation basis must have 2^%zu = %zu points, got %zu", fn, log2_domain, m, he->n);
-    auto pk = std::make_unique<GrothPkObj>();
-    pk->nvars = nvars; pk->npublic = npublic; pk->nz = nz; pk->len_h = 0;
-    set_shard(*pk, 0, 1);                                  // a full key: n_w = nvars, n_h = 0
-    pk->coset_only = true;
-    copy_points(c, at, kG1Aff, pk->at());
-    copy_points(c, b1, kG1Aff, pk->bacgamma1());
-    copy_points(c, cd, kG1Aff, pk->bacdelta());
-    copy_points(c, b2, kG2Aff, pk->bacgamma2());
-    copy_points(c, he, kG1Aff, pk->ptd_eval());
-    groth_force_public(c, *pk);
-    pk->alpha = g1_affine_from_jacobian_std(g1_alpha);
-    pk->beta = g1_affine_from_jacobian_std(g1_beta);
-    pk->delta = g1_affine_from_jacobian_std(g1_delta);
-    pk->beta2 = g2_affine_from_jacobian_std(g2_beta);
-    pk->delta2 = g2_affine_from_jacobian_std(g2_delta);
-    pk->domain_log2 = (int)log2_domain;
-    pk->n_eval = m; pk->e_lo = 0; pk->n_e = m; pk->eval_domain_log2 = (int)log2_domain;
-    {                                                      // Z = x^m - 1, standard form: r - 1, zeros, 1
-      uint32_t lo[8], hi[8] = {1u, 0, 0, 0, 0, 0, 0, 0};
-      for (int i = 0; i < 8; ++i) lo[i] = ModR::p32(i);
-      lo[0] -= 1u;                                         // r is odd: no borrow
-      DevBuf zc(nz * 32);
-      GS_HIP(hipMemsetAsync(zc.p, 0, nz * 32, c.stream));
-      GS_HIP(hipMemcpyAsync(zc.p, lo, 32, hipMemcpyHostToDevice, c.stream));
-      GS_HIP(hipMemcpyAsync(zc.as<uint32_t>() + m * 8, hi, 32, hipMemcpyHostToDevice, c.stream));
-      divisor_init(c, pk->z, zc.as<uint32_t>(), nz);
-      GS_HIP(hipStreamSynchronize(c.stream));              // `zc` is released here
-    }
-    pk_scan_sparsity(c, *pk);
-    *out = c.put(std::move(pk));
-    return GS_OK;
-  }, true, false, g1_at);
-}
-
-int gs_groth16_pk_create_shard(gs_handle g1_at, gs_handle g1_bacgamma, gs_handle g2_bacgamma, gs_handle bacdelta, gs_handle ptd,
-                               const uint64_t g1_alpha[12], const uint64_t g1_beta[12], const uint64_t g1_delta[12],
-                               const uint64_t g2_beta[24], const uint64_t g2_delta[24], const uint64_t* z, size_t nz,
-                               size_t nvars, size_t npublic, size_t nptd_total, size_t shard_index, size_t shard_count, gs_handle* out) {
-  return guarded([&](Ctx& c) -> int {
-    return groth_pk_create_impl(c, g1_at, g1_bacgamma, g2_bacgamma, bacdelta, ptd, g1_alpha, g1_beta, g1_delta, g2_beta, g2_delta, z, nz,
-                                nvars, npublic, nptd_total, shard_index, shard_count, out);
-  }, true, false, g1_at);
-}
-
-int gs_groth16_pk_shard(gs_handle hfull, size_t shard_index, size_t shard_count, gs_handle* out) {
-  return guarded([&](Ctx& c) -> int {
-    return pk_shard_impl(c, c, "groth16", c.get<GrothPkObj>(hfull, Kind::GrothPk), shard_index, shard_count, out);
-  }, true, false, hfull);
-}
-
-int gs_groth16_pk_shard_to(gs_handle hfull, size_t shard_index, size_t shard_count, int target_device, gs_handle* out) {
-  return guarded_pair(hfull, target_device, [&](Ctx& src, Ctx& dst) -> int {
-    return pk_shard_impl(dst, src, "groth16", src.get<GrothPkObj>(hfull, Kind::GrothPk), shard_index, shard_count, out);
-  });
-}
 
 int gs_groth16_prove(gs_handle hpk, const uint64_t* w, size_t nw, const uint64_t* px, size_t npx,
                      const uint64_t r[4], const uint64_t s[4], uint64_t out_proof[32], int inf[3]) {
@@ -1102,9 +779,9 @@ int gs_groth16_prove(gs_handle hpk, const uint64_t* w, size_t nw, const uint64_t
     if (!pk) return fail(GS_ERR_ARG, "gs_groth16_prove: bad proving-key handle");
     if (!w || !px || !r || !s || !out_proof || !inf) return fail(GS_ERR_ARG, "null argument");
     reset_timing(c);
-    DevScalars dw{upload_tmp(c, prove_state(c).up_w, w, nw), nw};
+    const DevVec dw{upload_tmp(c, prove_state(c).up_w, w, nw), nw};
     prove_state(c).up_px.ensure(std::max<size_t>(npx, 1) * 32);
-    DevScalars dp{prove_state(c).up_px.as<uint32_t>(), npx, px};               // copied inside, behind the work that only needs w
+    const PxOnHost dp{prove_state(c).up_px.as<uint32_t>(), px, npx};            // copied inside, behind the work that only needs w
     return groth16_prove_impl(c, pk, dw, dp, r, s, out_proof, inf);
   }, true, false, hpk);
 }
@@ -1118,7 +795,7 @@ int gs_groth16_prove_resident(gs_handle hpk, gs_handle hw, gs_handle hpx, const 
     if (!pk || !w || !px) return fail(GS_ERR_ARG, "gs_groth16_prove_resident: bad handle");
     if (!r || !s || !out_proof || !inf) return fail(GS_ERR_ARG, "null argument");
     reset_timing(c);
-    return groth16_prove_impl(c, pk, resident(w), resident(px), r, s, out_proof, inf);
+    return groth16_prove_impl(c, pk, resident(w), resident_px(px), r, s, out_proof, inf);
   }, true, false, hpk);
 }
 
@@ -1189,7 +866,7 @@ int gs_groth16_prove_partials(gs_handle hpk, gs_handle hw, gs_handle hpx, size_t
     reset_timing(c);
     ProofSums sums;
     Shard sh; sh.index = shard_index; sh.count = shard_count;
-    const int rc = proof_sums_blocking(c, pk, resident(w), resident(px), sh, sums);
+    const int rc = proof_sums_blocking(c, pk, resident(w), resident_px(px), sh, sums);
     if (rc == GS_OK) groth16_pack_sums(sums, out_sums, inf);
     return rc;
   }, true, false, hpk);
@@ -1213,17 +890,8 @@ static int witness_values_impl(Ctx& c, const char* fn, Kind kind, gs_handle hpk,
   if (o->domain_log2) return fail(GS_ERR_SHAPE, "%s: an R1CS over a power-of-two domain is not served by the multi-device entry points", fn);
   if (!hx_shape(o->n, nz) || pk->n_eval != o->n || pk->eval_domain_log2)
     return fail(GS_ERR_SHAPE, "%s: the key has no evaluation-basis array for a system of %zu constraints", fn, o->n);
-  Scalars* hv = nullptr;
-  if (*hv_inout) {
-    hv = c.get<Scalars>(*hv_inout, Kind::Scalars);
-    if (!hv || hv->n != o->n) return fail(GS_ERR_ARG, "%s: the output handle does not hold n = %zu values", fn, o->n);
-  } else {
-    auto fresh = std::make_unique<Scalars>();
-    fresh->n = o->n;
-    fresh->buf.alloc(o->n * 32);
-    hv = fresh.get();
-    *hv_inout = c.put(std::move(fresh));
-  }
+  Scalars* hv = inout_scalars(c, hv_inout, o->n, "%s: the output handle does not hold n = %zu values", fn);
+  if (!hv) return GS_ERR_ARG;
   StreamScope sc(c, c.aux_stream[1]);             // the stream that carries every proof's polynomial stage (as capi_r1cs.hip's resident px)
   PhaseTimer t(c.stream);
   uint32_t* bad = c.bad_dev.as<uint32_t>() + c.blocking_slot();
@@ -1279,17 +947,9 @@ int gs_groth16_partials_values_begin(gs_handle hpk, gs_handle hw, gs_handle hv_s
     if (bad_shard(shard_index, shard_count)) return fail(GS_ERR_ARG, "%s: bad shard", fn);
     Shard sh; sh.index = shard_index; sh.count = shard_count;
     if (int rc = check_values_slice(fn, pk, hv, sh, false)) return rc;
-    const int parity = c.free_parity();
-    if (parity < 0) return fail(GS_ERR_BUSY, "%s: three operations are already outstanding; collect one first", fn);
-    auto st = std::make_unique<GrothInFlight>();
-    st->keep = {c.share<Object>(hpk, Kind::GrothPk), c.share<Object>(hw, Kind::Scalars), c.share<Object>(hv_slice, Kind::Scalars)};
-    const int rc = proof_enqueue(c, pk, resident(w), values_slice(hv), sh, parity, false, true, *st);
-    if (rc != GS_OK) return rc;
-    mark_ticket_reads(st->streams, w, hv);
-    st->ticket = c.new_ticket();
-    *ticket = st->ticket;
-    c.inflight[parity] = std::move(st);
-    return GS_OK;
+    return install_ticket(c, fn, "collect one first", pk, {c.share<Object>(hpk, Kind::GrothPk), c.share<Object>(hw, Kind::Scalars), c.share<Object>(hv_slice, Kind::Scalars)},
+                          sh, w, hv, ticket, [] { return std::make_unique<GrothInFlight>(); },
+                          [&](int, ProofInFlight& st) { st.w = resident(w); st.src = values_slice(hv); });
   }, true, true, hpk);
 }
 
@@ -1339,24 +999,11 @@ int gs_groth16_prove_r1cs(gs_handle hpk, gs_handle hr1cs, gs_handle hw, gs_handl
     if (!r || !s || !out_proof || !inf) return fail(GS_ERR_ARG, "null argument");
     if (w->n != o->m) return fail(GS_ERR_SHAPE, "len(w) = %zu but the system has %zu variables", w->n, o->m);
     if (int rc = check_domain_pair("gs_groth16_prove_r1cs", pk, o)) return rc;
-    const size_t npx = o->npx();
-    Scalars* px = nullptr;
-    if (*px_inout) {
-      px = c.get<Scalars>(*px_inout, Kind::Scalars);
-      if (!px || px->n != npx) return fail(GS_ERR_ARG, "gs_groth16_prove_r1cs: the px handle does not hold 2n - 1 = %zu coefficients", npx);
-    } else {
-      auto fresh = std::make_unique<Scalars>();
-      fresh->n = npx;
-      fresh->buf.alloc(npx * 32);
-      px = fresh.get();
-      *px_inout = c.put(std::move(fresh));
-    }
+    Scalars* px = inout_scalars(c, px_inout, o->npx(), "%s: the px handle does not hold 2n - 1 = %zu coefficients", "gs_groth16_prove_r1cs");
+    if (!px) return GS_ERR_ARG;
     reset_timing(c);
-    DevScalars dp{px->buf.as<uint32_t>(), npx};
     const uint32_t* wdev = w->buf.as<uint32_t>();
-    uint32_t* pxdev = px->buf.as<uint32_t>();
-    dp.produce = [o, wdev, pxdev](Ctx& cc) { r1cs_px_dev(cc, *o, wdev, pxdev); };
-    return groth16_prove_impl(c, pk, DevScalars{wdev, w->n}, dp, r, s, out_proof, inf);
+    return groth16_prove_impl(c, pk, DevVec{wdev, w->n}, PxFromR1cs{o, wdev, px->buf.as<uint32_t>()}, r, s, out_proof, inf);
   }, true, false, hpk);
 }
 
@@ -1369,7 +1016,8 @@ static int groth16_prove_witness_impl(Ctx& c, const char* fn, gs_handle hpk, gs_
   Scalars* w = host ? nullptr : c.get<Scalars>(hw, Kind::Scalars);
   if (!pk || !o || (!host && !w)) return fail(GS_ERR_ARG, "%s: bad handle", fn);
   if ((host && !w_host) || !r || !s || !out_proof || !inf) return fail(GS_ERR_ARG, "null argument");
-  DevScalars dw, dp;
+  DevVec dw;
+  HSource dp;
   if (int rc = witness_blocking_inputs(c, fn, pk, o, w, w_host, w ? w->n : nw_host, WitnessChecks{false, true}, dw, dp)) return rc;
   return groth16_prove_impl(c, pk, dw, dp, r, s, out_proof, inf);
 }
@@ -1410,49 +1058,15 @@ int gs_groth16_prove_witness_host_begin(gs_handle hpk, gs_handle hr1cs, const ui
 }
 
 // ---- Pinocchio ----------------------------------------------------------------------------------------------
-int gs_pinocchio_pk_create(gs_handle a, gs_handle ap, gs_handle b_g2, gs_handle bp, gs_handle cc, gs_handle cp, gs_handle kp,
-                           gs_handle g1t, const uint64_t* z, size_t nz, size_t nvars, size_t npublic, gs_handle* out) {
-  return guarded([&](Ctx& c) -> int {
-    Bases* A = c.get<Bases>(a, Kind::G1Bases);
-    Bases* Ap = c.get<Bases>(ap, Kind::G1Bases);
-    Bases* B = c.get<Bases>(b_g2, Kind::G2Bases);
-    Bases* Bp = c.get<Bases>(bp, Kind::G1Bases);
-    Bases* C = c.get<Bases>(cc, Kind::G1Bases);
-    Bases* Cp = c.get<Bases>(cp, Kind::G1Bases);
-    Bases* Kp = c.get<Bases>(kp, Kind::G1Bases);
-    Bases* T = c.get<Bases>(g1t, Kind::G1Bases);
-    if (!A || !Ap || !B || !Bp || !C || !Cp || !Kp || !T) return fail(GS_ERR_ARG, "gs_pinocchio_pk_create: bad base handle");
-    if (!z || !out || nz == 0) return fail(GS_ERR_ARG, "null argument");
-    for (Bases* x : {A, Ap, B, Bp, C, Cp, Kp})
-      if (x->n != nvars) return fail(GS_ERR_SHAPE, "every per-variable key array must have NVars = %zu points (got %zu)", nvars, x->n);
-    if (npublic + 1 > nvars) return fail(GS_ERR_SHAPE, "NPublic + 1 > NVars");
-    auto pk = std::make_unique<PinocchioPkObj>();
-    pk->nvars = nvars; pk->npublic = npublic; pk->nz = nz; pk->len_h = T->n;
-    pk->n_w = nvars; pk->n_h = T->n;                                // a full key
-    const Bases* g1src[6] = {A, Ap, Bp, C, Cp, Kp};                 // the order of PinocchioPkObj's g1w
-    for (int i = 0; i < 6; ++i) copy_points(c, g1src[i], kG1Aff, pk->g1w[i].pts);
-    copy_points(c, T, kG1Aff, pk->g1t());
-    copy_points(c, B, kG2Aff, pk->b2());
-    force_infinity(c, pk->a(), npublic + 1, kG1Aff);                 // snark.go:265
-    force_infinity(c, pk->ap(), npublic + 1, kG1Aff);
-    const uint32_t* dz = upload_tmp(c, prove_state(c).up_a, z, nz);
-    divisor_init(c, pk->z, dz, nz);
-    GS_HIP(hipStreamSynchronize(c.stream));
-    pk_scan_sparsity(c, *pk);
-    *out = c.put(std::move(pk));
-    return GS_OK;
-  }, true, false, a);
-}
-
 int gs_pinocchio_prove(gs_handle hpk, const uint64_t* w, size_t nw, const uint64_t* px, size_t npx, uint64_t out_proof[72], int inf[8]) {
   return guarded([&](Ctx& c) -> int {
     PinocchioPkObj* pk = c.get<PinocchioPkObj>(hpk, Kind::PinocchioPk);
     if (!pk) return fail(GS_ERR_ARG, "gs_pinocchio_prove: bad proving-key handle");
     if (!w || !px || !out_proof || !inf) return fail(GS_ERR_ARG, "null argument");
     reset_timing(c);
-    DevScalars dw{upload_tmp(c, prove_state(c).up_w, w, nw), nw};
+    const DevVec dw{upload_tmp(c, prove_state(c).up_w, w, nw), nw};
     prove_state(c).up_px.ensure(std::max<size_t>(npx, 1) * 32);
-    DevScalars dp{prove_state(c).up_px.as<uint32_t>(), npx, px};               // copied inside, behind the work that only needs w
+    const PxOnHost dp{prove_state(c).up_px.as<uint32_t>(), px, npx};            // copied inside, behind the work that only needs w
     return pinocchio_prove_impl(c, pk, dw, dp, out_proof, inf);
   }, true, false, hpk);
 }
@@ -1507,25 +1121,13 @@ int gs_pinocchio_prove_resident(gs_handle hpk, gs_handle hw, gs_handle hpx, uint
     if (!pk || !w || !px) return fail(GS_ERR_ARG, "gs_pinocchio_prove_resident: bad handle");
     if (!out_proof || !inf) return fail(GS_ERR_ARG, "null argument");
     reset_timing(c);
-    return pinocchio_prove_impl(c, pk, resident(w), resident(px), out_proof, inf);
+    return pinocchio_prove_impl(c, pk, resident(w), resident_px(px), out_proof, inf);
   }, true, false, hpk);
 }
 
 // ---- Pinocchio over several GPUs (SURVEY 8e applied to snark.go:254-289) ------------------------------------------------------
 // A Pinocchio proof IS its eight MSM sums (there is no tail): rank k of N sums its term ranges, the eight partial points of the
 // ranks add up to the proof.  Key slices, partial sums (from px, or from the owner's slice of H's values), and the addition.
-int gs_pinocchio_pk_shard(gs_handle hfull, size_t shard_index, size_t shard_count, gs_handle* out) {
-  return guarded([&](Ctx& c) -> int {
-    return pk_shard_impl(c, c, "pinocchio", c.get<PinocchioPkObj>(hfull, Kind::PinocchioPk), shard_index, shard_count, out);
-  }, true, false, hfull);
-}
-
-int gs_pinocchio_pk_shard_to(gs_handle hfull, size_t shard_index, size_t shard_count, int target_device, gs_handle* out) {
-  return guarded_pair(hfull, target_device, [&](Ctx& src, Ctx& dst) -> int {
-    return pk_shard_impl(dst, src, "pinocchio", src.get<PinocchioPkObj>(hfull, Kind::PinocchioPk), shard_index, shard_count, out);
-  });
-}
-
 // the eight sums over this rank's term ranges, in the layout of a proof (PiA | PiAp | PiB | PiBp | PiC | PiCp | PiH | PiKp)
 int gs_pinocchio_prove_partials(gs_handle hpk, gs_handle hw, gs_handle hpx, size_t shard_index, size_t shard_count, uint64_t out_sums[72], int inf[8]) {
   return guarded([&](Ctx& c) -> int {
@@ -1536,7 +1138,7 @@ int gs_pinocchio_prove_partials(gs_handle hpk, gs_handle hw, gs_handle hpx, size
     if (!out_sums || !inf || bad_shard(shard_index, shard_count)) return fail(GS_ERR_ARG, "gs_pinocchio_prove_partials: bad shard or null output");
     reset_timing(c);
     Shard sh; sh.index = shard_index; sh.count = shard_count;
-    return pinocchio_prove_impl(c, pk, resident(w), resident(px), out_sums, inf, sh);
+    return pinocchio_prove_impl(c, pk, resident(w), resident_px(px), out_sums, inf, sh);
   }, true, false, hpk);
 }
 
@@ -1590,7 +1192,8 @@ static int pinocchio_prove_witness_impl(Ctx& c, const char* fn, gs_handle hpk, g
   Scalars* w = host ? nullptr : c.get<Scalars>(hw, Kind::Scalars);
   if (!pk || !o || (!host && !w)) return fail(GS_ERR_ARG, "%s: bad handle", fn);
   if ((host && !w_host) || !out_proof || !inf) return fail(GS_ERR_ARG, "null argument");
-  DevScalars dw, dp;
+  DevVec dw;
+  HSource dp;
   if (int rc = witness_blocking_inputs(c, fn, pk, o, w, w_host, w ? w->n : nw_host, WitnessChecks{true, false}, dw, dp)) return rc;
   return pinocchio_prove_impl(c, pk, dw, dp, out_proof, inf);
 }

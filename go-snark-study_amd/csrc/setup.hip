@@ -60,10 +60,6 @@ void eval_columns(Ctx& c, const HostCsc& csc, size_t n, size_t m, const uint32_t
   GS_HIP(hipStreamSynchronize(c.stream));
 }
 
-void force_infinity_points(Ctx& c, DevBuf& pts, size_t count, size_t words) {
-  if (count) GS_HIP(hipMemsetAsync(pts.p, 0, count * words * 4, c.stream));
-}
-
 // scalars of an evaluation-basis array: out[j-1] = scale * l_j(tau), l_j = Lagrange basis over the nodes n+1 .. 2n, j = 1..n
 // (canonical standard form).  l_j(tau) = L_j(tau - n) with L over 1..n, so the node tree's weights serve.  false when tau is
 // one of those nodes (the basis then degenerates; the key simply gets no evaluation-basis copy).
@@ -304,8 +300,8 @@ int gs_pinocchio_setup(size_t n, size_t m, size_t npublic,
       cp(o + 288, J1 + 48, nic * 24);   // IC
       GS_HIP(hipStreamSynchronize(c.stream));
     }
-    force_infinity_points(c, pk->a(), npublic + 1, 16);                               // the prover sums A, Ap over i > NPublic (snark.go:265)
-    force_infinity_points(c, pk->ap(), npublic + 1, 16);
+    force_infinity(c, pk->a(), npublic + 1, 16);                               // the prover sums A, Ap over i > NPublic (snark.go:265)
+    force_infinity(c, pk->ap(), npublic + 1, 16);
     GS_HIP(hipStreamSynchronize(c.stream));
     pk_scan_sparsity(c, *pk);
     *pk_out = c.put(std::move(pk));

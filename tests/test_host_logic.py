@@ -91,7 +91,7 @@ def test_pairing_header_constants_match_their_definitions():
 
 def test_shard_split_is_the_same_everywhere():
     """The contiguous split (first n % N ranges one longer) is written three times: parallel.shard_range (exchange layer),
-    groth16._shard_range (key slices, binary key files) and shard_range in csrc/prove.hip (the prover engine: key slices and gs_*_prove_partials, checked on
+    groth16._shard_range (key slices, binary key files) and shard_range in csrc/route.h (the prover engine: key slices and gs_*_prove_partials, checked on
     the GPU by the slice tests).  They must agree or a key slice would not match its rank's term range."""
     from gosnark_amd import groth16, parallel
     for n in (0, 1, 7, 8, 9, 4098, (1 << 20) + 1):
