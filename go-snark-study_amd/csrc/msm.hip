@@ -89,8 +89,8 @@ static uint32_t choose_chunk(uint64_t entries, uint32_t nbuckets, const std::vec
   return chunk;
 }
 
-// R >= 4 bucket ranges: partition by (window, range) first (msm_kernels.h); with two ranges reading the digit matrix twice is
-// cheaper than writing and re-reading 8-byte records
+// R >= 4 bucket ranges: partition by (window, range) first (msm_kernels.h); with two ranges reading the 2-byte digit matrix twice
+// (the second range's workgroup right behind the first's on the same XCD) is cheaper than writing and re-reading 8-byte records
 static uint32_t part_min_ranges() {
   static const uint32_t v = (uint32_t)dev_knob("GS_PART_MIN_R", 4, 2, 64);
   return v;
@@ -138,20 +138,23 @@ void build_plan(Ctx& c, int slot, const uint32_t* scalars_dev, uint32_t n, MsmPl
   {
     // (round 4: FLOOR, not ceiling -- a histogram / scatter workgroup holds 128 KiB of LDS, so exactly one fits a CU, and at c = 17
     //  the ceiling gave 15 windows x 2 ranges x 9 slices = 270 workgroups for 256 CUs: fourteen stragglers ran a second round of the
-    //  whole kernel, k_scatter 0.26 ms instead of ~0.15; 8 slices = 240 workgroups finish in one)
+    //  whole kernel, k_scatter 0.26 ms instead of ~0.15; 8 slices = 240 workgroups finish in one.  The grid itself pads the windows
+    //  to a multiple of 8 -- sort_block_of, msm_kernels.h -- with workgroups that exit at once: 256 ids at c = 17, still one round)
     const uint32_t want = std::max<uint32_t>(1u, 256u / (plan.W * pp.R));
     const uint32_t by_size = std::max<uint32_t>(1u, (n + 16383u) / 16384u);
     const uint32_t by_mem = std::max<uint32_t>(1u, (uint32_t)((64ull << 20) / ((uint64_t)plan.B * plan.W * 4)));
     pp.S = std::max<uint32_t>(1u, std::min(std::min<uint32_t>(16u, std::max<uint32_t>(want, 1u)), std::min(by_size, by_mem)));
     if (pp.R == 1 && !table_free) pp.S = std::max<uint32_t>(1u, std::min<uint32_t>(16u, by_size));     // narrow windows: as before
   }
-  pp.slice = (n + pp.S - 1) / pp.S;
+  pp.slice = sort_slice_terms(n, pp.S);
   pp.stride = (n + 63u) & ~63u;
   const bool wide = plan_partitions_first(plan.c);         // (= pp.R >= GS_PART_MIN_R)
   if (wide && term_index) throw HipError{hipErrorInvalidValue, "plans over a term list cannot be sorted partition-first (plan_partitions_first)", __LINE__};
   const uint32_t nparts = (uint32_t)plan.W * pp.R;
   if (wide && nparts > kMaxParts) throw HipError{hipErrorInvalidValue, "too many (window, range) partitions", __LINE__};
-  if (!wide) pb.digits.ensure((size_t)std::max<uint32_t>(pp.stride, 64u) * plan.W * sizeof(digit_t));
+  const bool narrow_digits = plan.c <= kNarrowDigitBits;   // 16-bit magnitudes (msm_kernels.h, k_digits)
+  const size_t mag_bytes = std::max<size_t>(digit_mag_bytes(pp), 64);
+  if (!wide) pb.digits.ensure(mag_bytes + std::max<size_t>(digit_plane_words(pp), 2) * 8);
   else {
     pb.recs.ensure(std::max<size_t>((size_t)n * plan.W, 1) * 8);
     pb.parts.ensure((size_t)(3 * kMaxParts + 4) * 4);
@@ -166,8 +169,10 @@ void build_plan(Ctx& c, int slot, const uint32_t* scalars_dev, uint32_t n, MsmPl
   const size_t lds = (size_t)std::min<uint32_t>(plan.B, kRangeBuckets) * 4;
   static const int sort_block = (int)dev_knob("GS_SORT_BLOCK", kSortBlock, 64, kSortBlock, 64);
   if (!ms.lds_attr_set) {       // B <= 2^15 counters = 128 KiB of the CU's 160 KiB LDS
-    GS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_hist), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-    GS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_scatter), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+    GS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_hist<uint16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+    GS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_hist<uint32_t>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+    GS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_scatter<uint16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+    GS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_scatter<uint32_t>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
     GS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_hist_part), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
     GS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_scatter_part), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
     ms.lds_attr_set = true;
@@ -177,6 +182,18 @@ void build_plan(Ctx& c, int slot, const uint32_t* scalars_dev, uint32_t n, MsmPl
   uint32_t* part_count = pb.parts.as<uint32_t>();
   uint32_t* part_base = part_count ? part_count + kMaxParts : nullptr;
   uint32_t* part_cursor = part_count ? part_base + kMaxParts + 4 : nullptr;
+  uint64_t* planes = wide ? nullptr : reinterpret_cast<uint64_t*>(static_cast<char*>(pb.digits.p) + mag_bytes);
+  // the narrow path's three kernels over the digit matrix, for its digit type
+  auto launch_digits = [&](auto* mags) {
+    using D = std::remove_pointer_t<decltype(mags)>;
+    hipLaunchKernelGGL(k_digits<D>, grid1(pp.stride), dim3(256), 0, c.stream, scalars_dev, pp, mags, planes, term_index, index_bias);
+    hipLaunchKernelGGL(k_hist<D>, dim3(sort_grid(pp)), dim3(sort_block), lds, c.stream, mags, planes, pp, pb.hist.as<uint32_t>());
+  };
+  auto launch_scatter = [&](auto* mags) {
+    using D = std::remove_pointer_t<decltype(mags)>;
+    hipLaunchKernelGGL(k_scatter<D>, dim3(sort_grid(pp)), dim3(sort_block), lds, c.stream, mags, planes, pp, pb.hist.as<uint32_t>(),
+                       pb.offsets.as<uint32_t>(), pb.entries.as<uint32_t>(), term_index, index_bias);
+  };
   if (n > 0 && wide) {
     GS_HIP(hipMemsetAsync(part_count, 0, (size_t)nparts * 4, c.stream));
     hipLaunchKernelGGL(k_part_count, grid1(n, kPartBlock), dim3(kPartBlock), 0, c.stream, scalars_dev, pp, part_count);
@@ -186,8 +203,7 @@ void build_plan(Ctx& c, int slot, const uint32_t* scalars_dev, uint32_t n, MsmPl
     hipLaunchKernelGGL(k_hist_part, dim3(8 * pp.S * ((nparts + 7) / 8)), dim3(sort_block), lds, c.stream, pb.recs.as<uint2>(), part_base, pp, pb.hist.as<uint32_t>());
     hipLaunchKernelGGL(k_colscan, grid1(plan.B), dim3(256), 0, c.stream, pb.hist.as<uint32_t>(), pp, pb.totals.as<uint32_t>());
   } else if (n > 0) {
-    hipLaunchKernelGGL(k_digits, grid1(n), dim3(256), 0, c.stream, scalars_dev, pp, pb.digits.as<digit_t>(), term_index, index_bias);
-    hipLaunchKernelGGL(k_hist, dim3(plan.W, pp.S, pp.R), dim3(sort_block), lds, c.stream, pb.digits.as<digit_t>(), pp, pb.hist.as<uint32_t>());
+    if (narrow_digits) launch_digits(pb.digits.as<uint16_t>()); else launch_digits(pb.digits.as<uint32_t>());
     if (table_free) hipLaunchKernelGGL(k_colscan_windows, grid1(plan.nbuckets), dim3(256), 0, c.stream, pb.hist.as<uint32_t>(), pp, pb.totals.as<uint32_t>());
     else hipLaunchKernelGGL(k_colscan, grid1(plan.B), dim3(256), 0, c.stream, pb.hist.as<uint32_t>(), pp, pb.totals.as<uint32_t>());
   } else {
@@ -197,8 +213,8 @@ void build_plan(Ctx& c, int slot, const uint32_t* scalars_dev, uint32_t n, MsmPl
   if (n > 0) {
     if (wide) hipLaunchKernelGGL(k_scatter_part, dim3(8 * pp.S * ((nparts + 7) / 8)), dim3(sort_block), lds, c.stream, pb.recs.as<uint2>(), part_base, pp,
                                  pb.hist.as<uint32_t>(), pb.offsets.as<uint32_t>(), pb.entries.as<uint32_t>());
-    else hipLaunchKernelGGL(k_scatter, dim3(plan.W, pp.S, pp.R), dim3(sort_block), lds, c.stream, pb.digits.as<digit_t>(), pp, pb.hist.as<uint32_t>(),
-                            pb.offsets.as<uint32_t>(), pb.entries.as<uint32_t>(), term_index, index_bias);
+    else if (narrow_digits) launch_scatter(pb.digits.as<uint16_t>());
+    else launch_scatter(pb.digits.as<uint32_t>());
     hipLaunchKernelGGL(k_chunk_map, grid1(plan.nbuckets), dim3(256), 0, c.stream, pb.offsets.as<uint32_t>(), plan.nbuckets, plan.chunk,
                        pb.chunk_bucket.as<uint32_t>(), pb.heavy_list.as<uint32_t>(), pb.counters.as<uint32_t>());
   }

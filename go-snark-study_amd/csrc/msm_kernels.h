@@ -6,7 +6,7 @@
 //
 // Pipeline (all on the library stream, no host round trips):
 //   plan (once per scalar vector, shared by every base array multiplied by it; no host round trip):
-//     k_digits        scalars -> signed c-bit digit matrix (u16)
+//     k_digits        scalars -> signed c-bit digit matrix (16-bit buckets up to c = 17 + a skip and a sign bit plane)
 //     k_hist          per (window, slice, bucket range) workgroup: histogram of 2^15 buckets in LDS (128 KiB of the 160 KiB)
 //     k_colscan+scan  exclusive prefix sums -> bucket offsets, per-slice cursors
 //     k_scatter       counting sort with LDS cursors: entries[] = term index (sign in bit 31) grouped by bucket
@@ -45,8 +45,8 @@ struct PlanParams {
 };
 // One histogram / scatter workgroup keeps the counters of ONE bucket range in LDS (2^15 u32 = 128 KiB of the CU's 160 KiB) and
 // counts the digits of its (window, slice) that fall into it; wide windows (c > 16) take R = B / 2^15 such workgroups per
-// (window, slice), each re-reading the slice's digits (sequential 4-byte reads: the sort is bandwidth-cheap, the accumulation is
-// not -- fewer, wider windows trade R passes over a 50 MiB digit matrix for 3 fewer point additions per term).
+// (window, slice), each re-reading the slice's digits (sequential 16-byte reads of 2-byte digits: the sort is bandwidth-cheap, the
+// accumulation is not -- fewer, wider windows trade R passes over a 30 MiB digit matrix for 3 fewer point additions per term).
 constexpr uint32_t kRangeLog = 15;
 constexpr uint32_t kRangeBuckets = 1u << kRangeLog;
 
@@ -58,26 +58,58 @@ GS_HD int32_t next_digit(const uint32_t (&k)[8], const PlanParams& pp, int w, ui
   return (int32_t)raw;
 }
 
-// ---- plan, step 1: scalars -> digit matrix digits[w][i] = d + B - 1, read once, coalesced ------------------------
-using digit_t = uint32_t;
+// ---- plan, step 1: scalars -> digit matrix, read once, coalesced ------------------------------------------------
+// A digit d in [-B+1, B] is kept as its bucket |d| - 1 (a magnitude row, 16 bits wide up to c = 17, where B = 2^16) and two bits:
+// `skip` (d == 0, or a padding term i >= n of the row) and `neg` (d < 0).  The bits of 64 consecutive terms are one 64-bit word of
+// the window's skip plane resp. sign plane, so the 8 terms a sort thread takes in one 16-byte load of magnitudes cost it one byte of
+// each plane.  Layout: mags[w][stride] (digit type D), then planes[w][2][stride / 64] (u64; 0 = skip, 1 = sign); the rows are padded
+// to `stride` (a multiple of 64) and every padding term is marked skip, so the sort kernels need no bound test per term.
+constexpr int kNarrowDigitBits = 17;                 // widest window whose buckets fit 16 bits
+struct DigitCode { uint32_t mag; bool neg, skip; };
+GS_HD DigitCode digit_encode(int32_t d) {
+  DigitCode e;
+  e.skip = d == 0;
+  e.neg = d < 0;
+  e.mag = e.skip ? 0u : (uint32_t)(d < 0 ? -d : d) - 1u;
+  return e;
+}
+GS_HD int32_t digit_decode(uint32_t mag, bool neg, bool skip) {
+  if (skip) return 0;
+  return neg ? -(int32_t)(mag + 1u) : (int32_t)(mag + 1u);
+}
+GS_HD size_t digit_mag_bytes(const PlanParams& pp) { return (size_t)pp.stride * pp.W * (pp.c <= kNarrowDigitBits ? 2 : 4); }
+GS_HD size_t digit_plane_words(const PlanParams& pp) { return (size_t)pp.W * 2 * (pp.stride >> 6); }
+template <class D> struct alignas(sizeof(D) * 8) Digit8 { D v[8]; };      // the magnitudes of 8 consecutive terms: one or two 16-byte loads
+
 // term_index (optional): the plan covers only the listed terms -- compact term i of the plan is term term_index[i] - index_bias of the
 // scalar vector (and of the base arrays: k_scatter writes that id into the entries).  For keys with sparse B arrays (prove.h,
 // ProverKey::b_index): the terms whose base points are the point at infinity never enter the digit matrix.
-__global__ void __launch_bounds__(256) k_digits(const uint32_t* __restrict__ scalars, PlanParams pp, digit_t* __restrict__ digits,
+// grid: one thread per term of the PADDED row (stride), so that whole waves write the plane words.
+template <class D>
+__global__ void __launch_bounds__(256) k_digits(const uint32_t* __restrict__ scalars, PlanParams pp, D* __restrict__ mags, uint64_t* __restrict__ planes,
                                                  const uint32_t* __restrict__ term_index, uint32_t index_bias) {
   wave_priority<GS_PRIO_PLAN>();
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= pp.n) return;
-  const uint32_t src = term_index ? term_index[i] - index_bias : i;
-  uint32_t k[8];
-  const uint4* s4 = reinterpret_cast<const uint4*>(scalars + (size_t)src * 8);
-  uint4 lo = s4[0], hi = s4[1];
-  k[0] = lo.x; k[1] = lo.y; k[2] = lo.z; k[3] = lo.w; k[4] = hi.x; k[5] = hi.y; k[6] = hi.z; k[7] = hi.w;
-  scalar_canon(k);
+  if (i >= pp.stride) return;                               // (whole waves: stride is a multiple of 64)
+  uint32_t k[8] = {0, 0, 0, 0, 0, 0, 0, 0};                 // a padding term has every digit zero
+  if (i < pp.n) {
+    const uint32_t src = term_index ? term_index[i] - index_bias : i;
+    const uint4* s4 = reinterpret_cast<const uint4*>(scalars + (size_t)src * 8);
+    uint4 lo = s4[0], hi = s4[1];
+    k[0] = lo.x; k[1] = lo.y; k[2] = lo.z; k[3] = lo.w; k[4] = hi.x; k[5] = hi.y; k[6] = hi.z; k[7] = hi.w;
+    scalar_canon(k);
+  }
+  const uint32_t words = pp.stride >> 6;
   uint32_t carry = 0;
   for (int w = 0; w < pp.W; ++w) {
-    const int32_t d = next_digit(k, pp, w, carry);
-    digits[(size_t)w * pp.stride + i] = (digit_t)(d + (int32_t)pp.B - 1);
+    const DigitCode e = digit_encode(next_digit(k, pp, w, carry));
+    mags[(size_t)w * pp.stride + i] = (D)e.mag;
+    const uint64_t skip = __ballot(e.skip), neg = __ballot(e.neg);
+    if ((threadIdx.x & 63u) == 0) {
+      uint64_t* p = planes + (size_t)w * 2 * words + (i >> 6);
+      p[0] = skip;
+      p[words] = neg;
+    }
   }
 }
 
@@ -97,30 +129,81 @@ __global__ void __launch_bounds__(256) k_finite_mask(const uint32_t* __restrict_
 }
 
 // ---- plan, step 2: per-(window, slice, range) bucket histogram in LDS -----------------------------------------
-// grid = (W, S, R): blockIdx.x = window, so that all slices of a window run on XCD (w % 8) and the window's
-// 4n-byte region of `entries` is assembled in ONE L2 by the scatter pass below.
+// grid: 1-D, 8 * S * R * ceil(W / 8) workgroups.  Workgroups go to the 8 XCDs round-robin by linear id (x fastest for a 3-D grid,
+// so a (W, S, R) grid puts window w on XCD w % 8 only when W is a multiple of 8 -- at c = 17, W = 15, it dealt the slices of one
+// window to eight XCDs).  sort_block_of gives every workgroup of window w an id with id % 8 == w % 8: all slices and ranges of a
+// window run on ONE XCD, the two ranges of a slice next to each other, so the second reads the slice's digits from that L2
+// (measured at 2^20, c = 17: the pair fetches 16 MB per plan for the 31.5 MB of magnitudes both read).  Ids whose window is >= W
+// (W padded to a multiple of 8) exit.
+// What the map does NOT buy is assembled writes: a scatter workgroup spreads its 4-byte entries over 2^15 buckets ~1 KB apart, far
+// more lines than an L2 holds, so each entry leaves as its own 32-byte masked write whichever XCD its neighbours are written from
+// (WRITE_SIZE of k_scatter 498 MB for 63 MB of entries, as with the 3-D grid: profiles/plan_sort_ab.txt).
 constexpr int kSortBlock = 1024;      // upper bound; the launch picks 256 .. 1024 threads (msm.hip: sort_block)
 
-__global__ void __launch_bounds__(kSortBlock) k_hist(const digit_t* __restrict__ digits, PlanParams pp, uint32_t* __restrict__ hist) {
+GS_HD uint32_t sort_grid(const PlanParams& pp) { return 8u * pp.S * pp.R * (((uint32_t)pp.W + 7u) / 8u); }
+GS_HD bool sort_block_of(uint32_t id, const PlanParams& pp, uint32_t& w, uint32_t& s, uint32_t& r) {
+  const uint32_t xcd = id & 7u, j = id >> 3, per = pp.S * pp.R;
+  w = xcd + 8u * (j / per);
+  s = (j % per) / pp.R;
+  r = (j % per) % pp.R;
+  return w < (uint32_t)pp.W;
+}
+// terms per slice: whole plane words, so that a sort thread takes 8 terms and one byte of each plane at a time
+GS_HD uint32_t sort_slice_terms(uint32_t n, uint32_t S) { return ((n + S - 1u) / S + 63u) & ~63u; }
+// the 8-term groups [lo, hi) of slice s of a padded row (the last slices of a short row may be empty)
+GS_HD void sort_slice_groups(const PlanParams& pp, uint32_t s, uint32_t& lo, uint32_t& hi) {
+  const uint32_t first = min(s * pp.slice, pp.stride);
+  lo = first >> 3;
+  hi = min(first + pp.slice, pp.stride) >> 3;
+}
+
+template <class D>
+__global__ void __launch_bounds__(kSortBlock) k_hist(const D* __restrict__ mags, const uint64_t* __restrict__ planes, PlanParams pp,
+                                                      uint32_t* __restrict__ hist) {
   wave_priority<GS_PRIO_PLAN>();
   extern __shared__ uint32_t sh[];
-  const uint32_t w = blockIdx.x, s = blockIdx.y, r = blockIdx.z;
+  uint32_t w, s, r;
+  if (!sort_block_of(blockIdx.x, pp, w, s, r)) return;
   const uint32_t nb = min(pp.B, kRangeBuckets), base = r << kRangeLog;
   for (uint32_t b = threadIdx.x; b < nb; b += blockDim.x) sh[b] = 0;
   __syncthreads();
-  const uint32_t lo = s * pp.slice, hi = min(pp.n, lo + pp.slice);
-  const digit_t* row = digits + (size_t)w * pp.stride;
-  const int32_t zero = (int32_t)pp.B - 1;
-  for (uint32_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
-    const int32_t d = (int32_t)row[i] - zero;
-    if (d != 0) {
-      const uint32_t b = (uint32_t)(d < 0 ? -d : d) - 1u;
-      if ((b >> kRangeLog) == r) atomicAdd(&sh[b - base], 1u);
+  uint32_t lo, hi;
+  sort_slice_groups(pp, s, lo, hi);
+  const Digit8<D>* row = reinterpret_cast<const Digit8<D>*>(mags + (size_t)w * pp.stride);
+  const uint8_t* skip = reinterpret_cast<const uint8_t*>(planes + (size_t)w * 2 * (pp.stride >> 6));
+  auto count = [&](const Digit8<D>& d, uint32_t sk) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const uint32_t b = d.v[j];
+      if (!((sk >> j) & 1u) && (b >> kRangeLog) == r) atomicAdd(&sh[b - base], 1u);
     }
+  };
+  // two groups per thread and trip, both requested before either is counted: the loop is bound by the bytes in flight per CU
+  for (uint32_t g = lo + threadIdx.x; g < hi; g += 2 * blockDim.x) {
+    const uint32_t g2 = g + blockDim.x < hi ? g + blockDim.x : g;
+    const Digit8<D> d0 = row[g], d1 = row[g2];
+    const uint32_t s0 = skip[g], s1 = g2 != g ? skip[g2] : 0xffu;
+    count(d0, s0);
+    count(d1, s1);
   }
   __syncthreads();
   uint32_t* out = hist + ((size_t)w * pp.S + s) * pp.B + base;
   for (uint32_t b = threadIdx.x; b < nb; b += blockDim.x) out[b] = sh[b];
+}
+
+// One column of the histogram matrix -> its exclusive prefix (in place); returns the column's sum.  The counters are requested
+// eight rows at a time: a thread that loads, adds and stores row by row waits one memory round trip per row (120 of them at c = 17).
+GS_HD uint32_t colscan_column(uint32_t* __restrict__ col, size_t pitch, uint32_t nq) {
+  constexpr uint32_t kBatch = 8;
+  uint32_t run = 0;
+  for (uint32_t q0 = 0; q0 < nq; q0 += kBatch) {
+    uint32_t t[kBatch];
+#pragma unroll
+    for (uint32_t j = 0; j < kBatch; ++j) t[j] = q0 + j < nq ? col[(size_t)(q0 + j) * pitch] : 0u;
+#pragma unroll
+    for (uint32_t j = 0; j < kBatch; ++j) if (q0 + j < nq) { col[(size_t)(q0 + j) * pitch] = run; run += t[j]; }
+  }
+  return run;
 }
 
 // hist[q][b], q = w*S + s  ->  exclusive prefix over q (in place); totals[b] = sum over q.
@@ -130,11 +213,7 @@ __global__ void __launch_bounds__(256) k_colscan(uint32_t* __restrict__ hist, Pl
   wave_priority<GS_PRIO_PLAN>();
   const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= pp.B) return;
-  uint32_t* col = hist + b;
-  const uint32_t nq = (uint32_t)pp.W * pp.S;
-  uint32_t run = 0;
-  for (uint32_t q = 0; q < nq; ++q) { const uint32_t t = col[(size_t)q * pp.B]; col[(size_t)q * pp.B] = run; run += t; }
-  totals[b] = run;
+  totals[b] = colscan_column(hist + b, pp.B, (uint32_t)pp.W * pp.S);
 }
 
 // The table-free route keeps the windows apart: hist[q][b], q = w*S + s  ->  exclusive prefix over the SLICES of window w only;
@@ -144,38 +223,49 @@ __global__ void __launch_bounds__(256) k_colscan_windows(uint32_t* __restrict__ 
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (uint32_t)pp.W * pp.B) return;
   const uint32_t w = i / pp.B, b = i % pp.B;
-  uint32_t* col = hist + (size_t)w * pp.S * pp.B + b;
-  uint32_t run = 0;
-  for (uint32_t q = 0; q < pp.S; ++q) { const uint32_t t = col[(size_t)q * pp.B]; col[(size_t)q * pp.B] = run; run += t; }
-  totals[i] = run;
+  totals[i] = colscan_column(hist + (size_t)w * pp.S * pp.B + b, pp.B, pp.S);
 }
 
 // ---- plan, step 4: counting-sort scatter; the cursors of the workgroup's bucket range live in LDS -------------------
-// entry = sign (bit 31) | window (bits 30..26) | term index (bits 25..0)
-__global__ void __launch_bounds__(kSortBlock) k_scatter(const digit_t* __restrict__ digits, PlanParams pp, const uint32_t* __restrict__ hist,
-                                                         const uint32_t* __restrict__ offsets, uint32_t* __restrict__ entries,
-                                                         const uint32_t* __restrict__ term_index, uint32_t index_bias) {
+// entry = sign (bit 31) | window (bits 30..26) | term index (bits 25..0); the same workgroup map as k_hist
+template <class D>
+__global__ void __launch_bounds__(kSortBlock) k_scatter(const D* __restrict__ mags, const uint64_t* __restrict__ planes, PlanParams pp,
+                                                         const uint32_t* __restrict__ hist, const uint32_t* __restrict__ offsets,
+                                                         uint32_t* __restrict__ entries, const uint32_t* __restrict__ term_index, uint32_t index_bias) {
   wave_priority<GS_PRIO_PLAN>();
   extern __shared__ uint32_t sh[];
-  const uint32_t w = blockIdx.x, s = blockIdx.y, r = blockIdx.z;
+  uint32_t w, s, r;
+  if (!sort_block_of(blockIdx.x, pp, w, s, r)) return;
   const uint32_t nb = min(pp.B, kRangeBuckets), base = r << kRangeLog;
   const uint32_t* pre = hist + ((size_t)w * pp.S + s) * pp.B + base;
   const uint32_t* off = offsets + (pp.tf ? (size_t)w * pp.B : (size_t)0);      // table-free: window w's own bucket set
   for (uint32_t b = threadIdx.x; b < nb; b += blockDim.x) sh[b] = off[base + b] + pre[b];
   __syncthreads();
-  const uint32_t lo = s * pp.slice, hi = min(pp.n, lo + pp.slice);
-  const digit_t* row = digits + (size_t)w * pp.stride;
-  const int32_t zero = (int32_t)pp.B - 1;
-  for (uint32_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
-    const int32_t d = (int32_t)row[i] - zero;
-    if (d != 0) {
-      const uint32_t b = (uint32_t)(d < 0 ? -d : d) - 1u;
-      if ((b >> kRangeLog) == r) {
+  uint32_t lo, hi;
+  sort_slice_groups(pp, s, lo, hi);
+  const Digit8<D>* row = reinterpret_cast<const Digit8<D>*>(mags + (size_t)w * pp.stride);
+  const uint8_t* skip = reinterpret_cast<const uint8_t*>(planes + (size_t)w * 2 * (pp.stride >> 6));
+  const uint8_t* neg = skip + ((size_t)(pp.stride >> 6) << 3);
+  const uint32_t tag = w << kWindowShift;
+  auto place = [&](uint32_t g, const Digit8<D>& d, uint32_t sk, uint32_t ng) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const uint32_t b = d.v[j];
+      if (!((sk >> j) & 1u) && (b >> kRangeLog) == r) {
         const uint32_t pos = atomicAdd(&sh[b - base], 1u);
+        const uint32_t i = g * 8u + (uint32_t)j;                                // (< n: padding terms are marked skip)
         const uint32_t id = term_index ? term_index[i] - index_bias : i;       // (k_digits: the plan's compact term i)
-        entries[pos] = id | (w << kWindowShift) | (d < 0 ? kSignBit : 0u);
+        entries[pos] = id | tag | (((ng >> j) & 1u) ? kSignBit : 0u);
       }
     }
+  };
+  for (uint32_t g = lo + threadIdx.x; g < hi; g += 2 * blockDim.x) {
+    const uint32_t g2 = g + blockDim.x < hi ? g + blockDim.x : g;
+    const Digit8<D> d0 = row[g], d1 = row[g2];
+    const uint32_t s0 = skip[g], s1 = g2 != g ? skip[g2] : 0xffu;
+    const uint32_t n0 = neg[g], n1 = neg[g2];
+    place(g, d0, s0, n0);
+    place(g2, d1, s1, n1);
   }
 }
 
