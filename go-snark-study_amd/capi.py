@@ -85,6 +85,13 @@ _SIGS = {
     "gs_r1cs_upload_zkey": [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(Handle)],
     "gs_groth16_pk_create_domain": [Handle, Handle, Handle, Handle, Handle, u64p, u64p, u64p, u64p, u64p,
                                     ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(Handle)],
+    "gs_g1_lagrange": [Handle, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(Handle)],
+    "gs_g2_lagrange": [Handle, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(Handle)],
+    "gs_r1cs_colsum_g1": [Handle, Handle, Handle, Handle, ctypes.POINTER(Handle)],
+    "gs_r1cs_colsum_g2": [Handle, Handle, Handle, Handle, ctypes.POINTER(Handle)],
+    "gs_g1_scale": [Handle, u64p, ctypes.POINTER(Handle)],
+    "gs_g1_download_affine_mont": [Handle, ctypes.c_void_p, ctypes.c_size_t],
+    "gs_g2_download_affine_mont": [Handle, ctypes.c_void_p, ctypes.c_size_t],
     "gs_groth16_pk_create": [Handle, Handle, Handle, Handle, Handle, u64p, u64p, u64p, u64p, u64p,
                              u64p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(Handle)],
     "gs_groth16_prove": [Handle, u64p, ctypes.c_size_t, u64p, ctypes.c_size_t, u64p, u64p, u64p, intp],
@@ -497,6 +504,56 @@ def g1_upload_affine_mont(buf):
 
 def g2_upload_affine_mont(buf):
     return _upload_affine_mont("gs_g2_upload_affine_mont", buf, 128)
+
+
+def _download_affine_mont(name, handle, point_bytes, out, n):
+    n = len(handle) if n is None else int(n)
+    if out is None:
+        out = np.zeros(n * point_bytes, dtype=np.uint8)
+    a = out.reshape(-1).view(np.uint8) if isinstance(out, np.ndarray) else None
+    if a is None or not a.flags.c_contiguous or not a.flags.writeable or a.size != n * point_bytes:
+        raise ValueError("%s: the output must be a writable contiguous uint8 array of %d bytes" % (name, n * point_bytes))
+    call(name, raw(handle), ctypes.c_void_p(a.ctypes.data if a.size else None), n)
+    return out
+
+
+def g1_download_affine_mont(handle, out=None, n=None):
+    """gs_g1_download_affine_mont: the first n points (default: all) of a G1 base array as the n x 64 bytes a .zkey holds, into `out` (a
+    writable uint8 array, e.g. a section of a memory-mapped output file) or a new array."""
+    return _download_affine_mont("gs_g1_download_affine_mont", handle, 64, out, n)
+
+
+def g2_download_affine_mont(handle, out=None, n=None):
+    return _download_affine_mont("gs_g2_download_affine_mont", handle, 128, out, n)
+
+
+def g1_lagrange(powers, log2_n, off=0, odd_half=False):
+    """gs_g1_lagrange: the inverse transform of 2^log2_n points of `powers` from index `off`, in the group -> a base-array handle
+    (odd_half: the odd entries of the transform of twice the size, from 2^(log2_n + 1) - 1 or 2^(log2_n + 1) points)."""
+    cell = HandleCell()
+    call("gs_g1_lagrange", raw(powers), int(off), int(log2_n), int(bool(odd_half)), cell.ref)
+    return cell.result()
+
+
+def g2_lagrange(powers, log2_n, off=0):
+    cell = HandleCell()
+    call("gs_g2_lagrange", raw(powers), int(off), int(log2_n), cell.ref)
+    return cell.result()
+
+
+def r1cs_colsum(r1cs, basis_a=None, basis_b=None, basis_c=None, g2=False):
+    """gs_r1cs_colsum_g1 / _g2: out[s] = sum_j a_js Ba[j] + b_js Bb[j] + c_js Bc[j] over the rows j of a resident R1CS, for every
+    variable s; None leaves a matrix out -> a base-array handle of nvars points."""
+    cell = HandleCell()
+    call("gs_r1cs_colsum_g2" if g2 else "gs_r1cs_colsum_g1", raw(r1cs), raw(basis_a), raw(basis_b), raw(basis_c), cell.ref)
+    return cell.result()
+
+
+def g1_scale(bases, k):
+    """gs_g1_scale: out[i] = k * P[i] -> a base-array handle."""
+    cell = HandleCell()
+    call("gs_g1_scale", raw(bases), ptr64(ints_to_u64([int(k) % R])), cell.ref)
+    return cell.result()
 
 
 def scalars_upload(s_u64):

@@ -28,6 +28,7 @@ evaluation basis, so the key is coset-only (gs_groth16_pk_create_domain) and pro
 ReadWtns below) is written down from snarkjs's source; NO FILE WRITTEN BY snarkjs ITSELF HAS BEEN READ YET -- the files this module has
 seen are the ones its own WriteZkey / WriteWtns produce.  Should a real file disagree, the parser is what changes: the library takes
 sections, not files."""
+import shutil
 import struct
 
 import numpy as np
@@ -511,3 +512,312 @@ def ConvertProvingKey(pkj, vk_json, path):
     key, _ = UploadProvingKey(pkj)
     DeriveEvalBasis(key, pkj.domainBits)
     WriteZkey(path, pkj, vk, groth16.ExportPkArray(key, "PowersTauDeltaEval"))
+
+
+# ---- circuit.r1cs / a powers-of-tau transcript -> circuit.zkey -------------------------------------------------------------------
+# The container is the one of .zkey / .wtns (_read_sections).  Layouts as published by iden3 (r1cs binary format, snarkjs ptau files); as
+# for .zkey, NO FILE WRITTEN BY circom / snarkjs ITSELF HAS BEEN READ YET: ReadR1cs and ReadPtau are the only places that know them.
+#   .r1cs  "r1cs" v1    1: u32 n8 (32), r, u32 nWires, u32 nPubOut, u32 nPubIn, u32 nPrvIn, u64 nLabels, u32 nConstraints
+#                       2: per constraint the linear combinations A, B, C: u32 nTerms, nTerms x (u32 wire, 32 bytes, standard form)
+#                       3: wire -> label map (ignored)      4, 5: custom gates (must be empty)
+#   .ptau  "ptau" v1    1: u32 n8 (32), q, u32 power, u32 ceremonyPower
+#                       2: tauG1, 2^(power+1) - 1 G1     3: tauG2, 2^power G2     4: alphaTauG1, 2^power G1     5: betaTauG1, 2^power G1
+#                       6: betaG2, one G2                7: contributions, 12 - 15: prepared Lagrange bases (all ignored: computed here)
+# Points are in the .zkey encoding.
+_R1CS_NAMES = {1: "1 (header)", 2: "2 (constraints)", 3: "3 (wire map)", 4: "4 (custom gates list)", 5: "5 (custom gates application)"}
+_PTAU_NAMES = {1: "1 (header)", 2: "2 (tauG1)", 3: "3 (tauG2)", 4: "4 (alphaTauG1)", 5: "5 (betaTauG1)", 6: "6 (betaG2)"}
+G1_GEN, G2_GEN = (1, 2, 1), ((10857046999023057135944570762232829481370756359578518086990519993285655852781,
+                              11559732032986387107991004021392285783925812861821192530917403151452391805634),
+                             (8495653923123431417604973247489272438418190587263600148770280649306958101930,
+                              4082367875863433681332203403145435568316851327593401208105741076214120093531), (1, 0))
+
+
+class R1cs:
+    """A parsed circuit.r1cs: the counts of its header and the three matrices as CSR triples (row_ptr uint32 [nConstraints + 1], col uint32
+    [nnz], val uint64 [nnz, 4], as they stand in the file: unsorted, repeated wires stay separate terms, values are not reduced)."""
+
+    def __init__(self, nWires, nPubOut, nPubIn, nPrvIn, nLabels, nConstraints, a, b, c):
+        self.nWires, self.nPubOut, self.nPubIn, self.nPrvIn, self.nLabels, self.nConstraints = nWires, nPubOut, nPubIn, nPrvIn, nLabels, nConstraints
+        self.nVars, self.nPublic = nWires, nPubOut + nPubIn
+        self.a, self.b, self.c = a, b, c
+
+
+def ReadR1cs(path):
+    """circuit.r1cs -> R1cs.  Every malformation is a ValueError that names the section."""
+    N = _R1CS_NAMES
+    data, sec = _read_sections(path, b"r1cs", 1, N, (1, 2))
+    for sid in (4, 5):
+        if sid in sec and sec[sid][1]:
+            raise ValueError("%s: section %s is not empty: circuits with custom gates are not supported by Groth16" % (path, N[sid]))
+    off, length = sec[1]
+    if length < 4:
+        raise ValueError("%s: section %s is too short" % (path, N[1]))
+    n8 = struct.unpack("<I", bytes(data[off:off + 4]))[0]
+    if n8 != 32:
+        raise ValueError("%s: section %s: n8 = %d, BN128 needs 32" % (path, N[1], n8))
+    _expect_len(path, N, 1, sec, 4 + 32 + 16 + 8 + 4)
+    if int.from_bytes(bytes(data[off + 4:off + 36]), "little") != R:
+        raise ValueError("%s: section %s: the prime is not BN128's r" % (path, N[1]))
+    nwires, npubout, npubin, nprvin, nlabels, ncons = struct.unpack("<IIIIQI", bytes(data[off + 36:off + 64]))
+    if 1 + npubout + npubin + nprvin > nwires:
+        raise ValueError("%s: section %s: 1 + nPubOut + nPubIn + nPrvIn = %d exceeds nWires = %d" % (path, N[1], 1 + npubout + npubin + nprvin, nwires))
+    off, length = sec[2]
+    bad_len = ValueError("%s: section %s has %d bytes, which its %d constraints do not fill exactly" % (path, N[2], length, ncons))
+    if length % 4:
+        raise bad_len
+    words = data[off:off + length].view("<u4")
+    # the count word of every linear combination: one step per combination (its position depends on the counts before it) ...
+    nlc = 3 * ncons
+    pos, cnt = np.zeros(nlc, dtype=np.int64), np.zeros(nlc, dtype=np.int64)
+    p, nw = 0, words.size
+    for j in range(nlc):
+        if p >= nw:
+            raise bad_len
+        pos[j], cnt[j] = p, words[p]
+        p += 1 + 9 * int(words[p])
+    if p != nw:
+        raise bad_len
+    # ... and every term at once: word index of term t of combination j = pos[j] + 1 + 9 t
+    first = np.cumsum(cnt) - cnt
+    at = np.repeat(pos + 1 - 9 * first, cnt) + 9 * np.arange(int(cnt.sum()), dtype=np.int64)
+    wires = np.asarray(words[at], dtype=np.uint32)
+    if wires.size and int(wires.max()) >= nwires:
+        raise ValueError("%s: section %s: wire %d, the circuit has %d" % (path, N[2], int(wires.max()), nwires))
+    vals = np.ascontiguousarray(np.asarray(words)[at[:, None] + np.arange(1, 9)], dtype="<u4").view("<u8").reshape(-1, 4)
+    which = np.repeat(np.arange(nlc, dtype=np.int64) % 3, cnt)
+    csr = []
+    for k in range(3):
+        rp = np.concatenate([[0], np.cumsum(cnt[k::3])]).astype(np.uint32)
+        csr.append((rp, wires[which == k], vals[which == k]))
+    return R1cs(nwires, npubout, npubin, nprvin, nlabels, ncons, csr[0], csr[1], csr[2])
+
+
+def WriteR1cs(path, nWires, nPubOut, nPubIn, nPrvIn, constraints, extra_sections=()):
+    """constraints: (A, B, C) per constraint, each a list of (wire, value) pairs (values as they are given, below 2^256) -> circuit.r1cs.
+    For fixtures and tests."""
+    body = []
+    for lcs in constraints:
+        for lc in lcs:
+            body.append(struct.pack("<I", len(lc)) + b"".join(struct.pack("<I", int(w)) + int(v).to_bytes(32, "little") for w, v in lc))
+    body = b"".join(body)
+    head = struct.pack("<I", 32) + R.to_bytes(32, "little") + struct.pack("<IIIIQI", nWires, nPubOut, nPubIn, nPrvIn, nWires, len(constraints))
+    secs = [(1, head), (2, body), (3, np.arange(nWires, dtype="<u8").tobytes())] + list(extra_sections)
+    with open(path, "wb") as f:
+        f.write(b"r1cs" + struct.pack("<II", 1, len(secs)))
+        for sid, payload in secs:
+            f.write(struct.pack("<IQ", sid, len(payload)) + payload)
+
+
+class Ptau:
+    """A parsed powers-of-tau file: power, ceremonyPower and the point sections as read-only uint8 views of the memory-mapped file."""
+
+    def __init__(self, power, ceremonyPower, tauG1, tauG2, alphaTauG1, betaTauG1, betaG2):
+        self.power, self.ceremonyPower = power, ceremonyPower
+        self.tauG1, self.tauG2, self.alphaTauG1, self.betaTauG1, self.betaG2 = tauG1, tauG2, alphaTauG1, betaTauG1, betaG2
+
+
+def ReadPtau(path):
+    """A .ptau file -> Ptau.  Every malformation is a ValueError that names the section."""
+    N = _PTAU_NAMES
+    data, sec = _read_sections(path, b"ptau", 1, N, (1, 2, 3, 4, 5, 6))
+    off, length = sec[1]
+    if length < 4:
+        raise ValueError("%s: section %s is too short" % (path, N[1]))
+    n8 = struct.unpack("<I", bytes(data[off:off + 4]))[0]
+    if n8 != 32:
+        raise ValueError("%s: section %s: n8 = %d, BN128 needs 32" % (path, N[1], n8))
+    _expect_len(path, N, 1, sec, 4 + 32 + 8)
+    if int.from_bytes(bytes(data[off + 4:off + 36]), "little") != Q:
+        raise ValueError("%s: section %s: the prime is not BN128's q" % (path, N[1]))
+    power, ceremony = struct.unpack("<II", bytes(data[off + 36:off + 44]))
+    if power > 28 or ceremony < power:
+        raise ValueError("%s: section %s: power = %d (ceremonyPower = %d) is not in 0 .. 28" % (path, N[1], power, ceremony))
+    for sid, count, size in ((2, (2 << power) - 1, G1_BYTES), (3, 1 << power, G2_BYTES), (4, 1 << power, G1_BYTES), (5, 1 << power, G1_BYTES),
+                             (6, 1, G2_BYTES)):
+        _expect_len(path, N, sid, sec, count * size)
+    view = lambda sid: data[sec[sid][0]:sec[sid][0] + sec[sid][1]]      # noqa: E731
+    return Ptau(power, ceremony, view(2), view(3), view(4), view(5), view(6))
+
+
+def WritePtau(path, power, tau, alpha, beta, extra_sections=()):
+    """The transcript of the toxic scalars tau, alpha, beta -> a .ptau file of 2^power (fixtures and tests; the points come from the
+    device's fixed-base multiplication, so this needs one)."""
+    n = 1 << power
+    pw = [1]
+    for _ in range(2 * n - 2):
+        pw.append(pw[-1] * tau % R)
+    g1 = lambda s: capi.g1_download_affine_mont(capi.g1_fixed_base(capi.ints_to_u64(s))).tobytes()      # noqa: E731
+    g2 = lambda s: capi.g2_download_affine_mont(capi.g2_fixed_base(capi.ints_to_u64(s))).tobytes()      # noqa: E731
+    head = struct.pack("<I", 32) + Q.to_bytes(32, "little") + struct.pack("<II", power, power)
+    secs = [(1, head), (2, g1(pw)), (3, g2(pw[:n])), (4, g1([alpha * t % R for t in pw[:n]])), (5, g1([beta * t % R for t in pw[:n]])),
+            (6, g2([beta % R]))] + list(extra_sections)
+    with open(path, "wb") as f:
+        f.write(b"ptau" + struct.pack("<II", 1, len(secs)))
+        for sid, payload in secs:
+            f.write(struct.pack("<IQ", sid, len(payload)) + payload)
+
+
+def _coef_values(vals):
+    """[n, 4] uint64 standard-form values -> [n, 32] uint8 of v * 2^512 mod r: one big-integer product per DISTINCT value (the values
+    below 2^64 and the wider ones are told apart first: the first are sorted as machine words)."""
+    v = np.ascontiguousarray(vals, dtype="<u8").reshape(-1, 4)
+    out = np.zeros((v.shape[0], 32), dtype=np.uint8)
+    small = ~v[:, 1:].any(axis=1)
+    for mask, keys in ((small, v[small, 0]), (~small, np.ascontiguousarray(v[~small]).view("V32").reshape(-1))):
+        if keys.size:
+            uniq, inverse = np.unique(keys, return_inverse=True)
+            table = b"".join((int.from_bytes(u.tobytes(), "little") * _COEF_SHIFT % R).to_bytes(32, "little") for u in uniq)
+            out[mask] = np.frombuffer(table, dtype=np.uint8).reshape(-1, 32)[inverse.reshape(-1)]
+    return out
+
+
+_COEF_DTYPE = np.dtype([("matrix", "<u4"), ("row", "<u4"), ("signal", "<u4"), ("value", np.uint8, (32,))])
+
+
+def _setup_records(r1cs):
+    """Section 4 of the key of a circuit: the A and B terms of every constraint in file order (A's before B's per constraint), then the
+    rows nConstraints + s = (signal s, 1) of A for s = 0 .. nPublic -> a [nCoefs] array of 44-byte records."""
+    counts = [np.diff(m[0].astype(np.int64)) for m in (r1cs.a, r1cs.b)]
+    rows = [np.repeat(np.arange(r1cs.nConstraints, dtype=np.int64), c) for c in counts]
+    na, nb, npub = rows[0].size, rows[1].size, r1cs.nPublic + 1
+    order = np.argsort(np.concatenate([2 * rows[0], 2 * rows[1] + 1]), kind="stable")
+    rec = np.zeros(na + nb + npub, dtype=_COEF_DTYPE)
+    assert rec.dtype.itemsize == COEF_BYTES
+    head = rec[:na + nb]
+    head["matrix"] = np.concatenate([np.zeros(na, dtype=np.uint32), np.ones(nb, dtype=np.uint32)])[order]
+    head["row"] = np.concatenate(rows)[order]
+    head["signal"] = np.concatenate([r1cs.a[1], r1cs.b[1]])[order]
+    head["value"] = _coef_values(np.concatenate([r1cs.a[2].reshape(-1, 4), r1cs.b[2].reshape(-1, 4)]))[order]
+    tail = rec[na + nb:]
+    tail["row"] = r1cs.nConstraints + np.arange(npub)
+    tail["signal"] = np.arange(npub)
+    tail["value"] = np.frombuffer(_COEF_SHIFT.to_bytes(32, "little"), dtype=np.uint8)
+    return rec
+
+
+def _setup_domain_bits(r1cs):
+    return max(1, (r1cs.nConstraints + r1cs.nPublic).bit_length())      # ceil(log2(nConstraints + nPublic + 1)), at least 1
+
+
+def _setup_system(r1cs, k):
+    """The circuit's constraints with the rows nConstraints + s = (signal s, 1) appended to A, as a domain R1CS over 2^k."""
+    npub = r1cs.nPublic + 1
+    rp_a = np.concatenate([r1cs.a[0].astype(np.int64), int(r1cs.a[0][-1]) + np.arange(1, npub + 1)]).astype(np.uint32)
+    col_a = np.concatenate([r1cs.a[1], np.arange(npub, dtype=np.uint32)])
+    one = np.zeros((npub, 4), dtype=np.uint64)
+    one[:, 0] = 1
+    val_a = np.concatenate([r1cs.a[2].reshape(-1, 4), one])
+    pad = lambda m: (np.concatenate([m[0], np.full(npub, m[0][-1], dtype=np.uint32)]), m[1], m[2])      # noqa: E731
+    return DeviceDomainR1CS(k, (rp_a, col_a, val_a), pad(r1cs.b), pad(r1cs.c), r1cs.nVars)
+
+
+def SetupFromPtau(r1cs_path, ptau_path, zkey_path, timing=None):
+    """What `snarkjs groth16 setup` does, on the device: circuit.r1cs + a powers-of-tau file -> circuit.zkey with delta = 1 (apply
+    ContributeDelta before using the key: with delta = 1 proofs can be forged).  The Lagrange bases of the domain are inverse transforms of
+    the transcript's sections in the group (gs_g1_lagrange / gs_g2_lagrange; the prepared sections 12 - 15 of a transcript are not read),
+    A, B1, B2, C and IC column sums of the circuit's matrices over them (gs_r1cs_colsum_g1 / _g2), H the odd half of the transform of
+    twice the size.  The arrays leave the device straight into the memory-mapped output file.
+    -> (groth16.DevicePk, DeviceZkeyR1CS, groth16.Vk) of the key just written, built from the resident arrays.
+    `timing`: a dict that receives the device milliseconds of the phases (transforms, column sums), the wall milliseconds of the
+    downloads and file writing, and the largest gs_memory_query library_bytes seen between two device calls."""
+    import time
+    r1cs, ptau = ReadR1cs(r1cs_path), ReadPtau(ptau_path)
+    k = _setup_domain_bits(r1cs)
+    m, nvars, npub = 1 << k, r1cs.nVars, r1cs.nPublic + 1
+    if ptau.power < k:
+        raise ValueError("%s: section %s: power = %d, but %d constraints and %d public signals need a domain of 2^%d points"
+                         % (ptau_path, _PTAU_NAMES[1], ptau.power, r1cs.nConstraints, r1cs.nPublic, k))
+    if npub > nvars:
+        raise ValueError("%s: section %s: nPublic + 1 = %d exceeds nWires = %d" % (r1cs_path, _R1CS_NAMES[1], npub, nvars))
+    capi.init()
+    ms = {"transforms_ms": 0.0, "colsums_ms": 0.0, "write_ms": 0.0, "library_bytes_max": 0}
+
+    def timed(phase, fn, *args, **kw):
+        out = fn(*args, **kw)
+        ms[phase] += capi.last_timing()["total_ms"]
+        ms["library_bytes_max"] = max(ms["library_bytes_max"], capi.memory_query()["library_bytes"])
+        return out
+
+    system = _setup_system(r1cs, k)
+    tau1 = capi.g1_upload_affine_mont(ptau.tauG1[:min(2 * m, (2 << ptau.power) - 1) * G1_BYTES])
+    L = timed("transforms_ms", capi.g1_lagrange, tau1, k)
+    H = timed("transforms_ms", capi.g1_lagrange, tau1, k, odd_half=True)
+    tau1 = None
+    L2 = timed("transforms_ms", capi.g2_lagrange, capi.g2_upload_affine_mont(ptau.tauG2[:m * G2_BYTES]), k)
+    La = timed("transforms_ms", capi.g1_lagrange, capi.g1_upload_affine_mont(ptau.alphaTauG1[:m * G1_BYTES]), k)
+    Lb = timed("transforms_ms", capi.g1_lagrange, capi.g1_upload_affine_mont(ptau.betaTauG1[:m * G1_BYTES]), k)
+    A = timed("colsums_ms", capi.r1cs_colsum, system, L, None, None)
+    B1 = timed("colsums_ms", capi.r1cs_colsum, system, None, L, None)
+    B2 = timed("colsums_ms", capi.r1cs_colsum, system, None, L2, None, g2=True)
+    K = timed("colsums_ms", capi.r1cs_colsum, system, Lb, La, L)
+    L = L2 = La = Lb = system = None
+    # the file: header and records from the host, the arrays from the device into their sections
+    t0 = time.perf_counter()
+    rec = _setup_records(r1cs)
+    alpha1, beta1, beta2 = bytes(ptau.alphaTauG1[:G1_BYTES]), bytes(ptau.betaTauG1[:G1_BYTES]), bytes(ptau.betaG2)
+    head = struct.pack("<I", 32) + Q.to_bytes(32, "little") + struct.pack("<I", 32) + R.to_bytes(32, "little") + struct.pack("<III", nvars, r1cs.nPublic, m)
+    head += alpha1 + beta1 + beta2 + G2ToZkey(G2_GEN) + G1ToZkey(G1_GEN) + G2ToZkey(G2_GEN)
+    sizes = {1: 4, 2: len(head), 3: npub * G1_BYTES, 4: 4 + rec.size * COEF_BYTES, 5: nvars * G1_BYTES, 6: nvars * G1_BYTES, 7: nvars * G2_BYTES,
+             8: (nvars - npub) * G1_BYTES, 9: m * G1_BYTES}
+    offs, pos = {}, 12
+    for sid in range(1, 10):
+        offs[sid] = pos + 12
+        pos += 12 + sizes[sid]
+    with open(zkey_path, "wb") as f:
+        f.truncate(pos)
+    out = np.memmap(zkey_path, dtype=np.uint8, mode="r+")
+    put = lambda at, b: out.__setitem__(slice(at, at + len(b)), np.frombuffer(b, dtype=np.uint8))      # noqa: E731
+    put(0, b"zkey" + struct.pack("<II", 1, 9))
+    for sid in range(1, 10):
+        put(offs[sid] - 12, struct.pack("<IQ", sid, sizes[sid]))
+    put(offs[1], struct.pack("<I", 1))
+    put(offs[2], head)
+    put(offs[4], struct.pack("<I", rec.size))
+    section = lambda sid, skip=0: out[offs[sid] + skip:offs[sid] + sizes[sid]]      # noqa: E731
+    section(4, 4)[:] = rec.view(np.uint8).reshape(-1)
+    capi.g1_download_affine_mont(A, section(5))
+    capi.g1_download_affine_mont(B1, section(6))
+    capi.g2_download_affine_mont(B2, section(7))
+    capi.g1_download_affine_mont(H, section(9))
+    capi.g1_download_affine_mont(K, section(3), n=npub)
+    kbytes = capi.g1_download_affine_mont(K)                       # C = K without the public signals; the resident C has infinities there
+    section(8)[:] = kbytes[npub * G1_BYTES:]
+    out.flush()
+    ms["write_ms"] = (time.perf_counter() - t0) * 1e3
+    kbytes[:npub * G1_BYTES] = 0
+    ic = [G1FromZkey(row) for row in np.asarray(section(3)).reshape(-1, G1_BYTES)]
+    a1, b1p, b2p = G1FromZkey(alpha1), G1FromZkey(beta1), G2FromZkey(beta2)
+    key = groth16.device_pk_domain_from_handles(A, B1, B2, capi.g1_upload_affine_mont(kbytes), H, a1, b1p, G1_GEN, b2p, G2_GEN, k, nvars, r1cs.nPublic)
+    prod = DeviceZkeyR1CS(k, nvars, rec.view(np.uint8).reshape(-1))
+    del out
+    if timing is not None:
+        timing.update(ms, log2_domain=k, nVars=nvars, nCoefs=int(rec.size))
+    return key, prod, groth16.Vk(IC=ic, G1_Alpha=a1, G2_Beta=b2p, G2_Gamma=G2_GEN, G2_Delta=G2_GEN)
+
+
+def ContributeDelta(zkey_in, zkey_out, delta):
+    """One phase-2 contribution with the secret `delta`: C and H are multiplied by 1 / delta (gs_g1_scale), delta1 and delta2 by delta, and
+    everything else -- every other section, section 10 if the file has one, unknown sections -- is copied byte for byte.
+    NO CONTRIBUTION TRANSCRIPT IS WRITTEN: `snarkjs zkey verify` checks the chain of contributions recorded in section 10, and producing that
+    record (the challenge hashes and the proof of knowledge of delta) is out of scope here; the key proves and verifies, it does not pass
+    `zkey verify`."""
+    delta = int(delta) % R
+    if delta == 0:
+        raise ValueError("delta must not be 0 mod r")
+    ReadZkey(zkey_in)                                                  # validates the layout
+    data, sec = _read_sections(zkey_in, b"zkey", 1, _ZKEY_NAMES, (2, 8, 9))
+    capi.init()
+    shutil.copyfile(zkey_in, zkey_out)
+    out = np.memmap(zkey_out, dtype=np.uint8, mode="r+")
+    inv = pow(delta, -1, R)
+    for sid in (8, 9):
+        off, length = sec[sid]
+        if length:
+            capi.g1_download_affine_mont(capi.g1_scale(capi.g1_upload_affine_mont(data[off:off + length]), inv), out[off:off + length])
+    d1 = sec[2][0] + sec[2][1] - G2_BYTES - G1_BYTES                  # delta1 | delta2 end the header
+    capi.g1_download_affine_mont(capi.g1_scale(capi.g1_upload_affine_mont(data[d1:d1 + G1_BYTES]), delta), out[d1:d1 + G1_BYTES])
+    d2 = capi.g2_upload_affine_mont(data[d1 + G1_BYTES:d1 + G1_BYTES + G2_BYTES])
+    p = capi.msm(d2, capi.ints_to_u64([delta]), g2=True)
+    out[d1 + G1_BYTES:d1 + G1_BYTES + G2_BYTES] = np.frombuffer(G2ToZkey(G2_INF if p is None else (p[0], p[1], (1, 0))), dtype=np.uint8)
+    out.flush()
+    del out

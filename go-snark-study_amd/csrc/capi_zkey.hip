@@ -10,6 +10,7 @@
 #include "msm.h"
 #include "point_io.h"
 #include "runtime.h"
+#include "scan.h"
 #include "zkey_convert.h"
 
 using namespace gs;
@@ -41,7 +42,6 @@ int upload_affine_mont_bases(Ctx& c, const char* fn, Kind kind, const void* byte
 // The order inside a row is whatever the atomics give: the row's sum is a sum in a field.  Repeated (matrix, row, signal) records stay
 // separate entries and add up in the product.
 constexpr int kRecWords = 11;
-constexpr uint32_t kScanPerThread = 8, kScanTile = 256 * kScanPerThread;
 
 __global__ void __launch_bounds__(256) k_zkey_count(const uint32_t* __restrict__ rec, uint32_t ncoefs, uint32_t m, uint32_t nvars, uint32_t* __restrict__ counts,
                                                      uint32_t* __restrict__ bad) {
@@ -55,59 +55,6 @@ __global__ void __launch_bounds__(256) k_zkey_count(const uint32_t* __restrict__
     return;
   }
   atomicAdd(&counts[(size_t)mat * m + row], 1u);
-}
-// x[0..n) -> its exclusive prefix sums inside every tile of kScanTile, tile_sum[t] = the tile's total
-__global__ void __launch_bounds__(256) k_scan_tiles(uint32_t* __restrict__ x, uint32_t n, uint32_t* __restrict__ tile_sum) {
-  __shared__ uint32_t sh[256];
-  const size_t base = (size_t)blockIdx.x * kScanTile + (size_t)threadIdx.x * kScanPerThread;
-  uint32_t v[kScanPerThread], sum = 0;
-#pragma unroll
-  for (uint32_t j = 0; j < kScanPerThread; ++j) { v[j] = base + j < n ? x[base + j] : 0u; sum += v[j]; }
-  sh[threadIdx.x] = sum;
-  __syncthreads();
-  uint32_t incl = sum;
-  for (uint32_t off = 1; off < 256; off <<= 1) {
-    const uint32_t o = threadIdx.x >= off ? sh[threadIdx.x - off] : 0u;
-    __syncthreads();
-    incl += o;
-    sh[threadIdx.x] = incl;
-    __syncthreads();
-  }
-  uint32_t run = incl - sum;
-#pragma unroll
-  for (uint32_t j = 0; j < kScanPerThread; ++j) {
-    if (base + j < n) x[base + j] = run;
-    run += v[j];
-  }
-  if (threadIdx.x == 255) tile_sum[blockIdx.x] = incl;
-}
-// exclusive prefix sums of the tile totals, in place (one workgroup)
-__global__ void __launch_bounds__(1024) k_scan_tile_sums(uint32_t* __restrict__ tile_sum, uint32_t ntiles) {
-  __shared__ uint32_t sh[1024];
-  const uint32_t per = (ntiles + 1023u) / 1024u, b0 = threadIdx.x * per;
-  uint32_t sum = 0;
-  for (uint32_t j = 0; j < per; ++j) if (b0 + j < ntiles) sum += tile_sum[b0 + j];
-  sh[threadIdx.x] = sum;
-  __syncthreads();
-  uint32_t incl = sum;
-  for (uint32_t off = 1; off < 1024; off <<= 1) {
-    const uint32_t o = threadIdx.x >= off ? sh[threadIdx.x - off] : 0u;
-    __syncthreads();
-    incl += o;
-    sh[threadIdx.x] = incl;
-    __syncthreads();
-  }
-  uint32_t run = incl - sum;
-  for (uint32_t j = 0; j < per; ++j)
-    if (b0 + j < ntiles) {
-      const uint32_t t = tile_sum[b0 + j];
-      tile_sum[b0 + j] = run;
-      run += t;
-    }
-}
-__global__ void __launch_bounds__(256) k_scan_add(uint32_t* __restrict__ x, uint32_t n, const uint32_t* __restrict__ tile_prefix) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) x[i] += tile_prefix[i / kScanTile];
 }
 // offs = the scanned counters (2m + 1): the row pointers of A are offs[0..m], those of B offs[m..2m] less the entries of A
 __global__ void __launch_bounds__(256) k_zkey_rowptr(const uint32_t* __restrict__ offs, uint32_t m, uint32_t* __restrict__ rp_a, uint32_t* __restrict__ rp_b) {
@@ -159,7 +106,7 @@ int gs_r1cs_upload_zkey(size_t log2_domain, size_t nvars, const void* coefs, siz
     if (nvars == 0 || nvars >= (1ull << 31)) return fail(GS_ERR_ARG, "%s: nvars = %zu, must be 1 .. 2^31 - 1", fn, nvars);
     if (ncoefs >= (1ull << 31)) return fail(GS_ERR_ARG, "%s: too many coefficient records", fn);
     const size_t m = (size_t)1 << log2_domain, ncnt = 2 * m + 1;
-    const uint32_t ntiles = (uint32_t)((ncnt + kScanTile - 1) / kScanTile);
+    const uint32_t ntiles = scan_tiles(ncnt);
     DevBuf rec(std::max<size_t>(ncoefs, 1) * kRecWords * 4), counts(ncnt * 4), tiles((size_t)ntiles * 4), flag(8);
     if (ncoefs) staged_h2d(c, rec.p, coefs, ncoefs * kRecWords * 4, c.stream);
     const uint32_t init[2] = {0u, 0xffffffffu};
@@ -167,9 +114,7 @@ int gs_r1cs_upload_zkey(size_t log2_domain, size_t nvars, const void* coefs, siz
     GS_HIP(hipMemsetAsync(counts.p, 0, ncnt * 4, c.stream));
     if (ncoefs) hipLaunchKernelGGL(k_zkey_count, grid1(ncoefs), dim3(256), 0, c.stream, rec.as<uint32_t>(), (uint32_t)ncoefs, (uint32_t)m, (uint32_t)nvars,
                                    counts.as<uint32_t>(), flag.as<uint32_t>());
-    hipLaunchKernelGGL(k_scan_tiles, dim3(ntiles), dim3(256), 0, c.stream, counts.as<uint32_t>(), (uint32_t)ncnt, tiles.as<uint32_t>());
-    hipLaunchKernelGGL(k_scan_tile_sums, dim3(1), dim3(1024), 0, c.stream, tiles.as<uint32_t>(), ntiles);
-    hipLaunchKernelGGL(k_scan_add, grid1(ncnt), dim3(256), 0, c.stream, counts.as<uint32_t>(), (uint32_t)ncnt, tiles.as<uint32_t>());
+    scan_exclusive_dev(c, counts.as<uint32_t>(), ncnt, tiles.as<uint32_t>());
     GS_HIP(hipGetLastError());
     uint32_t res[2] = {0, 0}, nnz_a = 0;
     GS_HIP(hipMemcpyAsync(res, flag.p, 8, hipMemcpyDeviceToHost, c.stream));

@@ -13,6 +13,7 @@
 #include <algorithm>
 
 #include "domain.h"
+#include "ec_stage.h"
 #include "evaltree.h"
 #include "point_io.h"
 #include "prove.h"
@@ -23,11 +24,6 @@ namespace {
 
 constexpr int kPw = PointIO<FqTag>::kXyzzWords;
 
-GS_HD void load_words(const uint32_t* __restrict__ p, uint32_t (&k)[8]) {
-#pragma unroll
-  for (int i = 0; i < 8; ++i) k[i] = p[i];
-}
-
 // pts[i] = T[i] for i < n, the point at infinity for n <= i < total
 __global__ void __launch_bounds__(256) k_ec_load(const uint32_t* __restrict__ affine, uint32_t n, uint32_t* __restrict__ pts, uint32_t total) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -35,53 +31,6 @@ __global__ void __launch_bounds__(256) k_ec_load(const uint32_t* __restrict__ af
   G1Xyzz p = xyzz_inf<FqTag>();
   if (i < n) p = xyzz_from_affine(PointIO<FqTag>::load_affine(affine + (size_t)i * 16));
   store_xyzz<FqTag>(pts + (size_t)i * kPw, p);
-}
-
-// One radix-2 stage over `total` = 2 * nbf points, butterflies of span `half` (a power of two), twiddle of butterfly j within its
-// block: tw[j * tstep] (8 standard-form words each; tw[0] = 1 is not multiplied).
-//   forward (decimation in frequency):  (a, b) -> (a + b, (a - b) w)       inverse (decimation in time):  (a, b) -> (a + w b, a - w b)
-template <bool kInverse>
-__global__ void __launch_bounds__(64) k_ec_stage(uint32_t* __restrict__ pts, uint32_t nbf, uint32_t half, uint32_t tstep, const uint32_t* __restrict__ tw) {
-  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= nbf) return;
-  const uint32_t j = t & (half - 1);
-  const size_t i0 = (size_t)(t - j) * 2 + j, i1 = i0 + half;
-  G1Xyzz a = load_xyzz<FqTag>(pts + i0 * kPw), b = load_xyzz<FqTag>(pts + i1 * kPw);
-  const uint32_t e = j * tstep;
-  uint32_t k[8];
-  if (e) load_words(tw + (size_t)e * 8, k);
-  if (kInverse) {
-    if (e && !is_inf(b)) b = xyzz_mul_words_w4(b, k);
-    G1Xyzz d = a;
-    xyzz_add(a, b);
-    xyzz_add(d, xyzz_neg(b));
-    store_xyzz<FqTag>(pts + i0 * kPw, a);
-    store_xyzz<FqTag>(pts + i1 * kPw, d);
-  } else {
-    G1Xyzz d = a;
-    xyzz_add(a, b);
-    xyzz_add(d, xyzz_neg(b));
-    if (e && !is_inf(d)) d = xyzz_mul_words_w4(d, k);
-    store_xyzz<FqTag>(pts + i0 * kPw, a);
-    store_xyzz<FqTag>(pts + i1 * kPw, d);
-  }
-}
-
-// pts[i] = spec[i] * pts[i]
-__global__ void __launch_bounds__(64) k_ec_scale(uint32_t* __restrict__ pts, const uint32_t* __restrict__ spec, uint32_t total) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= total) return;
-  G1Xyzz p = load_xyzz<FqTag>(pts + (size_t)i * kPw);
-  if (is_inf(p)) return;
-  uint32_t k[8];
-  load_words(spec + (size_t)i * 8, k);
-  store_xyzz<FqTag>(pts + (size_t)i * kPw, xyzz_mul_words_w4(p, k));
-}
-
-__global__ void __launch_bounds__(256) k_ec_to_affine(const uint32_t* __restrict__ pts, uint32_t n, uint32_t* __restrict__ affine) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  PointIO<FqTag>::store_affine(affine + (size_t)i * 16, xyzz_to_affine(load_xyzz<FqTag>(pts + (size_t)i * kPw)));
 }
 
 // ---- the evaluation-basis array by a transposed subproduct tree in the group (pk_derive_eval_impl) ---------------------------------
@@ -155,14 +104,6 @@ __global__ void __launch_bounds__(64) k_ec_leaves(const uint32_t* __restrict__ p
   PointIO<FqTag>::store_affine(affine + (size_t)i * 16, xyzz_to_affine(p));
 }
 
-// omega_N^(+-1) as standard-form words, N = 2^logn
-void root_words(int logn, bool inverse, uint64_t out[4]) {
-  Fe<ModR, 2> w;
-  for (int i = 0; i < NL; ++i) w.l[i] = inverse ? ModR::omega28_inv_mont(i) : ModR::omega28_mont(i);
-  for (int i = 0; i < ModR::kTwoAdicity - logn; ++i) w = sqr(w);
-  fr_words_from_mont(w, out);
-}
-
 int pk_derive_quot_impl(Ctx& c, const char* fn, Kind kind, gs_handle hpk) {
   ProverKey* pk = c.get<ProverKey>(hpk, kind);
   if (!pk) return fail(GS_ERR_ARG, "%s: bad proving-key handle", fn);
@@ -184,8 +125,8 @@ int pk_derive_quot_impl(Ctx& c, const char* fn, Kind kind, gs_handle hpk) {
   uint64_t inv_n[4], w[4], wi[4];
   fr_inv_words(nn, inv_n);
   scale_mont_by_std_dev(c, gp.as<uint32_t>(), inv_n, N, spec.as<uint32_t>());
-  root_words(logn, false, w);
-  root_words(logn, true, wi);
+  ec_root_words(logn, false, w);
+  ec_root_words(logn, true, wi);
   scaled_powers_dev(c, w, one, half_n, twf.as<uint32_t>());
   scaled_powers_dev(c, wi, one, half_n, twi.as<uint32_t>());
   // the group side
@@ -193,15 +134,15 @@ int pk_derive_quot_impl(Ctx& c, const char* fn, Kind kind, gs_handle hpk) {
   hipLaunchKernelGGL(k_ec_load, grid1(N), dim3(256), 0, c.stream, pk->h.pts.as<uint32_t>(), (uint32_t)n, pts.as<uint32_t>(), (uint32_t)N);
   const uint32_t nbf = (uint32_t)(N / 2);
   for (int s = 0; s < logn; ++s)                       // spans N/2, N/4, .., 1
-    hipLaunchKernelGGL((k_ec_stage<false>), grid1(nbf, 64), dim3(64), 0, c.stream, pts.as<uint32_t>(), nbf, (uint32_t)(N >> (s + 1)), 1u << s, twf.as<uint32_t>());
-  hipLaunchKernelGGL(k_ec_scale, grid1(N, 64), dim3(64), 0, c.stream, pts.as<uint32_t>(), spec.as<uint32_t>(), (uint32_t)N);
+    hipLaunchKernelGGL((k_ec_stage<FqTag, false>), grid1(nbf, 64), dim3(64), 0, c.stream, pts.as<uint32_t>(), nbf, (uint32_t)(N >> (s + 1)), 1u << s, twf.as<uint32_t>());
+  hipLaunchKernelGGL(k_ec_scale<FqTag>, grid1(N, 64), dim3(64), 0, c.stream, pts.as<uint32_t>(), spec.as<uint32_t>(), (uint32_t)N);
   for (int s = logn - 1; s >= 0; --s)                  // spans 1, 2, .., N/2
-    hipLaunchKernelGGL((k_ec_stage<true>), grid1(nbf, 64), dim3(64), 0, c.stream, pts.as<uint32_t>(), nbf, (uint32_t)(N >> (s + 1)), 1u << s, twi.as<uint32_t>());
+    hipLaunchKernelGGL((k_ec_stage<FqTag, true>), grid1(nbf, 64), dim3(64), 0, c.stream, pts.as<uint32_t>(), nbf, (uint32_t)(N >> (s + 1)), 1u << s, twi.as<uint32_t>());
   GS_HIP(hipGetLastError());
   pk->h_quot.table.invalidate();
   pk->n_q = 0;
   pk->h_quot.pts.alloc(n * 64);
-  hipLaunchKernelGGL(k_ec_to_affine, grid1(n), dim3(256), 0, c.stream, pts.as<uint32_t>(), (uint32_t)n, pk->h_quot.pts.as<uint32_t>());
+  hipLaunchKernelGGL(k_ec_to_affine<FqTag>, grid1(n), dim3(256), 0, c.stream, pts.as<uint32_t>(), (uint32_t)n, pk->h_quot.pts.as<uint32_t>());
   GS_HIP(hipGetLastError());
   GS_HIP(hipStreamSynchronize(c.stream));
   pk->n_q = n;
@@ -236,8 +177,8 @@ int pk_derive_eval_impl(Ctx& c, const char* fn, Kind kind, gs_handle hpk, size_t
   shifted_tree_spectra_dev(c, n, spec, weights);
   const uint64_t one[4] = {1, 0, 0, 0};
   uint64_t w[4], wi[4];
-  root_words(L, false, w);
-  root_words(L, true, wi);
+  ec_root_words(L, false, w);
+  ec_root_words(L, true, wi);
   scaled_powers_dev(c, w, one, half_n, twf.as<uint32_t>());
   scaled_powers_dev(c, wi, one, half_n, twi.as<uint32_t>());
   // the group side
@@ -247,11 +188,11 @@ int pk_derive_eval_impl(Ctx& c, const char* fn, Kind kind, gs_handle hpk, size_t
   for (int level = L; level >= 1; --level) {
     const size_t blk = (size_t)1 << level;
     for (size_t half = blk / 2; half >= 1; half >>= 1)         // spans 2^(level-1) .. 1 within every slot
-      hipLaunchKernelGGL((k_ec_stage<false>), grid1(nbf, 64), dim3(64), 0, c.stream, cur.as<uint32_t>(), nbf, (uint32_t)half, (uint32_t)(total / (2 * half)), twf.as<uint32_t>());
+      hipLaunchKernelGGL((k_ec_stage<FqTag, false>), grid1(nbf, 64), dim3(64), 0, c.stream, cur.as<uint32_t>(), nbf, (uint32_t)half, (uint32_t)(total / (2 * half)), twf.as<uint32_t>());
     hipLaunchKernelGGL(k_ec_fork, grid1(total, 64), dim3(64), 0, c.stream, cur.as<uint32_t>(), spec[level - 1].as<uint32_t>(), prod.as<uint32_t>(), (uint32_t)n, level,
                        (uint32_t)total);
     for (size_t half = 1; half <= blk / 2; half <<= 1)         // spans 1 .. 2^(level-1), twice as many slots
-      hipLaunchKernelGGL((k_ec_stage<true>), grid1(2 * nbf, 64), dim3(64), 0, c.stream, prod.as<uint32_t>(), 2 * nbf, (uint32_t)half, (uint32_t)(total / (2 * half)),
+      hipLaunchKernelGGL((k_ec_stage<FqTag, true>), grid1(2 * nbf, 64), dim3(64), 0, c.stream, prod.as<uint32_t>(), 2 * nbf, (uint32_t)half, (uint32_t)(total / (2 * half)),
                          twi.as<uint32_t>());
     hipLaunchKernelGGL(k_ec_window, grid1(total), dim3(256), 0, c.stream, prod.as<uint32_t>(), cur.as<uint32_t>(), (uint32_t)n, level, (uint32_t)total);
   }
@@ -264,16 +205,6 @@ int pk_derive_eval_impl(Ctx& c, const char* fn, Kind kind, gs_handle hpk, size_t
   GS_HIP(hipStreamSynchronize(c.stream));
   pk->n_eval = n; pk->n_e = n; pk->eval_domain_log2 = 0;
   return GS_OK;
-}
-
-// pts[p] = T[bitrev(p)] for bitrev(p) < n, the point at infinity otherwise (p < 2^k): the permuting load of the derivation below
-__global__ void __launch_bounds__(256) k_ec_load_bitrev(const uint32_t* __restrict__ affine, uint32_t n, uint32_t* __restrict__ pts, int k) {
-  const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= (1u << k)) return;
-  const uint32_t i = dom_bitrev(k, p);
-  G1Xyzz v = xyzz_inf<FqTag>();
-  if (i < n) v = xyzz_from_affine(PointIO<FqTag>::load_affine(affine + (size_t)i * 16));
-  store_xyzz<FqTag>(pts + (size_t)p * kPw, v);
 }
 
 // The coset evaluation-basis array of a key over the power-of-two domain 2^k (domain.h), from its h array T alone:
@@ -296,19 +227,19 @@ int pk_derive_eval_domain_impl(Ctx& c, gs_handle hpk, size_t log2_domain) {
   DevBuf scal(m * 32), twi(half_m * 32), pts(m * kPw * 4);
   const uint64_t one[4] = {1, 0, 0, 0};
   uint64_t wi[4];
-  root_words(k, true, wi);
+  ec_root_words(k, true, wi);
   domain_derive_scalars_dev(c, k, scal.as<uint32_t>());
   scaled_powers_dev(c, wi, one, half_m, twi.as<uint32_t>());
-  hipLaunchKernelGGL(k_ec_load_bitrev, grid1(m), dim3(256), 0, c.stream, pk->h.pts.as<uint32_t>(), (uint32_t)std::min(pk->len_h, m), pts.as<uint32_t>(), k);
-  hipLaunchKernelGGL(k_ec_scale, grid1(m, 64), dim3(64), 0, c.stream, pts.as<uint32_t>(), scal.as<uint32_t>(), (uint32_t)m);
+  hipLaunchKernelGGL(k_ec_load_bitrev<FqTag>, grid1(m), dim3(256), 0, c.stream, pk->h.pts.as<uint32_t>(), (uint32_t)std::min(pk->len_h, m), pts.as<uint32_t>(), k);
+  hipLaunchKernelGGL(k_ec_scale<FqTag>, grid1(m, 64), dim3(64), 0, c.stream, pts.as<uint32_t>(), scal.as<uint32_t>(), (uint32_t)m);
   const uint32_t nbf = (uint32_t)half_m;
   for (int s = k - 1; s >= 0; --s)                     // spans 1, 2, .., m/2
-    hipLaunchKernelGGL((k_ec_stage<true>), grid1(nbf, 64), dim3(64), 0, c.stream, pts.as<uint32_t>(), nbf, (uint32_t)(m >> (s + 1)), 1u << s, twi.as<uint32_t>());
+    hipLaunchKernelGGL((k_ec_stage<FqTag, true>), grid1(nbf, 64), dim3(64), 0, c.stream, pts.as<uint32_t>(), nbf, (uint32_t)(m >> (s + 1)), 1u << s, twi.as<uint32_t>());
   GS_HIP(hipGetLastError());
   pk->h_eval.table.invalidate();
   pk->n_eval = 0; pk->e_lo = 0; pk->n_e = 0;
   pk->h_eval.pts.alloc(m * 64);
-  hipLaunchKernelGGL(k_ec_to_affine, grid1(m), dim3(256), 0, c.stream, pts.as<uint32_t>(), (uint32_t)m, pk->h_eval.pts.as<uint32_t>());
+  hipLaunchKernelGGL(k_ec_to_affine<FqTag>, grid1(m), dim3(256), 0, c.stream, pts.as<uint32_t>(), (uint32_t)m, pk->h_eval.pts.as<uint32_t>());
   GS_HIP(hipGetLastError());
   GS_HIP(hipStreamSynchronize(c.stream));
   pk->n_eval = m; pk->n_e = m; pk->eval_domain_log2 = k;

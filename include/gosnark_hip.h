@@ -248,6 +248,41 @@ int gs_groth16_pk_create_domain(gs_handle g1_at, gs_handle g1_bacgamma, gs_handl
                                 const uint64_t g2_beta[24], const uint64_t g2_delta[24], size_t log2_domain, size_t nvars, size_t npublic,
                                 gs_handle* out);
 
+/* ---- setup from a transcript: circuit.r1cs + a powers-of-tau file -> the arrays of a circuit.zkey ---------------------------------- */
+/* gs_groth16_setup takes the toxic scalars; whoever holds a real powers-of-tau transcript holds POINTS (tau^i G, alpha tau^i G, ..) and
+ * not tau, so the two halves of `snarkjs groth16 setup` are carried out in the group.  All arithmetic is exact, every addition is the
+ * complete one (a transcript or a basis may hold infinities, equal and opposite points), all results are ordinary base-array handles of
+ * affine points.  Blocking; GS_ERR_ARG for a bad handle or a value out of range, GS_ERR_SHAPE for arrays that do not fit each other.
+ *
+ * gs_g1_lagrange / gs_g2_lagrange: one inverse transform of n = 2^log2_n points P[off ..] in the group, w = 5^((r-1)/n), v = 5^((r-1)/(2n)):
+ *     odd_half = 0:  out[j] = (1/n)  sum_{i<n}  w^(-ij)      P[off+i]       0 <= log2_n <= 27, needs n points from off
+ *     odd_half = 1:  out[j] = (1/2n) sum_{i<2n} v^(-(2j+1)i) P[off+i]       1 <= log2_n <= 27, needs 2n - 1 or 2n points from off
+ *                                                                           (a missing P[off+2n-1] is the point at infinity)
+ * n points out, natural order.  With P[i] = tau^i G the first is the Lagrange basis L_j(tau) G of the domain of the n-th roots of unity
+ * (row j of a domain R1CS sits at w^j); the second -- the odd entries of the transform of size 2n, computed as ONE transform of size n
+ * over P[i] - P[i+n] -- is the coset evaluation basis of section 9 of a .zkey for delta = 1.  m + (m/2) log2 m scalar multiplications
+ * each (G1: 4-bit windows; G2: the same window, its 16-point table in private memory).  gs_g2_lagrange is the odd_half = 0 form.
+ *
+ * gs_r1cs_colsum_g1 / _g2: out[s] = sum_j a_js Ba[j] + b_js Bb[j] + c_js Bc[j] for every variable s < nvars of a resident R1CS
+ * (gs_r1cs_upload, gs_r1cs_upload_domain, gs_r1cs_upload_zkey): the column sums of the sparse matrices over basis points.  A basis handle
+ * of 0 leaves its matrix out; a basis holds at least as many points as the system has rows; a product system (no C matrix) with
+ * basis_c != 0 is GS_ERR_SHAPE.  The matrix rules are those of gs_r1cs_upload: unsorted indices, repeated (row, column) entries add, any
+ * 256-bit value counts mod r.  A coefficient of 1 or r - 1 costs one addition; any other v is multiplied through
+ * min(bitlen(v mod r), bitlen(r - v mod r)) bits; columns of any length are summed by a segmented reduction in levels of 16 terms, so no
+ * column is one thread's loop.  At most 2^28 - 1 terms per call.  nvars points out.
+ *
+ * gs_g1_scale: out[i] = k P[i] for any 256-bit k (a phase-2 contribution multiplies C and H by 1 / delta).
+ * gs_g1_download_affine_mont / gs_g2_download_affine_mont: the first n points of a base array in the encoding gs_g*_upload_affine_mont
+ * reads (the bytes of a .zkey section); `bytes` may be a writable memory map of the output file.
+ * go-snark-study_amd/circom.py (SetupFromPtau, ContributeDelta) drives them from circuit.r1cs and a .ptau file. */
+int gs_g1_lagrange(gs_handle powers, size_t off, size_t log2_n, int odd_half, gs_handle* out);
+int gs_g2_lagrange(gs_handle powers, size_t off, size_t log2_n, gs_handle* out);
+int gs_r1cs_colsum_g1(gs_handle r1cs, gs_handle basis_a, gs_handle basis_b, gs_handle basis_c, gs_handle* out);
+int gs_r1cs_colsum_g2(gs_handle r1cs, gs_handle basis_a, gs_handle basis_b, gs_handle basis_c, gs_handle* out);
+int gs_g1_scale(gs_handle bases, const uint64_t k[4], gs_handle* out);
+int gs_g1_download_affine_mont(gs_handle bases, void* bytes /* n x 64 */, size_t n);
+int gs_g2_download_affine_mont(gs_handle bases, void* bytes /* n x 128 */, size_t n);
+
 /* ---- Groth16 prover (groth16/groth16.go) --------------------------------------------------- */
 /* Device-resident proving key: groth16.Pk (groth16.go:15-32).  At, BACGamma (G1), BACDelta:
  * m points; G2 BACGamma: m points; PowersTauDelta: len(Z) points; single points as Jacobian
