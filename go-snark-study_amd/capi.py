@@ -37,6 +37,26 @@ class Memory(ctypes.Structure):
                                                "workspace_bytes", "objects", "evictions")]
 
 
+CHECK_MAX = 8
+KEY_CHECKS = ("coefs A", "coefs B", "A", "B1", "B2", "IC", "C", "H")
+PTAU_CHECKS = ("g1", "g2", "tau", "tauG1", "tauG2", "alphaTauG1", "betaTauG1", "betaG2")
+
+
+class CheckResult(ctypes.Structure):
+    _fields_ = ([(n, ctypes.c_int32) for n in ("ok", "lhs_g2", "rhs_g2", "lhs_inf", "rhs_inf", "reserved")]
+                + [("lhs", ctypes.c_uint64 * 16), ("rhs", ctypes.c_uint64 * 16)])
+
+
+class CheckReport(ctypes.Structure):
+    _fields_ = [("nchecks", ctypes.c_uint32), ("failed", ctypes.c_uint32), ("check", CheckResult * CHECK_MAX)]
+
+
+class KeyCheckInput(ctypes.Structure):
+    _fields_ = ([(n, Handle) for n in ("a", "b1", "b2", "ic", "c", "h", "key_system", "circuit_system", "tau_g1", "tau_g2", "alpha_tau_g1",
+                                       "beta_tau_g1")]
+                + [("delta2", ctypes.c_uint64 * 24), ("challenge", ctypes.c_uint64 * 4), ("log2_domain", ctypes.c_uint64), ("npublic", ctypes.c_uint64)])
+
+
 def lib_path():
     # GS_LIB: development aid for A/B runs of two builds inside one GPU session
     return os.environ.get("GS_LIB") or os.path.join(_HERE, "libgosnark_hip.so")
@@ -92,6 +112,9 @@ _SIGS = {
     "gs_g1_scale": [Handle, u64p, ctypes.POINTER(Handle)],
     "gs_g1_download_affine_mont": [Handle, ctypes.c_void_p, ctypes.c_size_t],
     "gs_g2_download_affine_mont": [Handle, ctypes.c_void_p, ctypes.c_size_t],
+    "gs_groth16_key_check": [ctypes.POINTER(KeyCheckInput), ctypes.POINTER(CheckReport)],
+    "gs_ptau_check": [Handle, Handle, Handle, Handle, u64p, ctypes.c_size_t, u64p, ctypes.POINTER(CheckReport)],
+    "gs_check_abi_sizes": [ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)],
     "gs_groth16_pk_create": [Handle, Handle, Handle, Handle, Handle, u64p, u64p, u64p, u64p, u64p,
                              u64p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(Handle)],
     "gs_groth16_prove": [Handle, u64p, ctypes.c_size_t, u64p, ctypes.c_size_t, u64p, u64p, u64p, intp],
@@ -235,6 +258,11 @@ def load_library():
         if tb.value != ctypes.sizeof(Timing) or mb.value != ctypes.sizeof(Memory):
             raise GosnarkHipError(-1, "%s writes gs_timing / gs_memory of %d / %d bytes, this binding expects %d / %d: rebuild the library"
                                   % (path, tb.value, mb.value, ctypes.sizeof(Timing), ctypes.sizeof(Memory)))
+        ib, rb = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        lib.gs_check_abi_sizes(ctypes.byref(ib), ctypes.byref(rb))
+        if ib.value != ctypes.sizeof(KeyCheckInput) or rb.value != ctypes.sizeof(CheckReport):
+            raise GosnarkHipError(-1, "%s takes gs_key_check_input / gs_check_report of %d / %d bytes, this binding expects %d / %d: rebuild the library"
+                                  % (path, ib.value, rb.value, ctypes.sizeof(KeyCheckInput), ctypes.sizeof(CheckReport)))
         _LIB = lib
         return lib
 
@@ -554,6 +582,42 @@ def g1_scale(bases, k):
     cell = HandleCell()
     call("gs_g1_scale", raw(bases), ptr64(ints_to_u64([int(k) % R])), cell.ref)
     return cell.result()
+
+
+def _check_report(rep, names):
+    """gs_check_report -> [(name, ok, lhs, rhs)] with the points as affine int tuples (None = infinity); the coefs checks carry the number
+    of differing rows in place of a left point."""
+    out = []
+    for i in range(rep.nchecks):
+        r = rep.check[i]
+        side = lambda w, inf, g2: _affine_result(np.array(w[:16 if g2 else 8], dtype=np.uint64), [inf], bool(g2))      # noqa: E731
+        if names[i].startswith("coefs"):
+            out.append((names[i], bool(r.ok), int(r.lhs[0]), None))
+        else:
+            out.append((names[i], bool(r.ok), side(r.lhs, r.lhs_inf, r.lhs_g2), side(r.rhs, r.rhs_inf, r.rhs_g2)))
+    return out
+
+
+def groth16_key_check(a, b1, b2, ic, c, h, key_system, circuit_system, tau_g1, tau_g2, alpha_tau_g1, beta_tau_g1, delta2, log2_domain, npublic,
+                      challenge):
+    """gs_groth16_key_check: the key's resident arrays and section-4 system against the circuit's system and the transcript's arrays, for
+    the challenge s -> [(check name, ok, lhs, rhs)] in the order of KEY_CHECKS.  delta2: a Jacobian int triple."""
+    inp = KeyCheckInput(*[raw(x) for x in (a, b1, b2, ic, c, h, key_system, circuit_system, tau_g1, tau_g2, alpha_tau_g1, beta_tau_g1)])
+    inp.delta2[:] = [int(v) for v in g2_points_to_u64([delta2]).reshape(-1)]
+    inp.challenge[:] = [int(v) for v in ints_to_u64([int(challenge) % (1 << 256)]).reshape(-1)]
+    inp.log2_domain, inp.npublic = int(log2_domain), int(npublic)
+    rep = CheckReport()
+    call("gs_groth16_key_check", ctypes.byref(inp), ctypes.byref(rep))
+    return _check_report(rep, KEY_CHECKS)
+
+
+def ptau_check(tau_g1, tau_g2, alpha_tau_g1, beta_tau_g1, beta_g2, log2_n, challenge):
+    """gs_ptau_check: the first 2^log2_n powers of a resident transcript against themselves -> [(check name, ok, lhs, rhs)] in the order
+    of PTAU_CHECKS.  beta_g2: a Jacobian int triple."""
+    rep = CheckReport()
+    call("gs_ptau_check", raw(tau_g1), raw(tau_g2), raw(alpha_tau_g1), raw(beta_tau_g1), ptr64(g2_points_to_u64([beta_g2]).reshape(-1)), int(log2_n),
+         ptr64(ints_to_u64([int(challenge) % (1 << 256)]).reshape(-1)), ctypes.byref(rep))
+    return _check_report(rep, PTAU_CHECKS)
 
 
 def scalars_upload(s_u64):

@@ -800,7 +800,7 @@ def ContributeDelta(zkey_in, zkey_out, delta):
     everything else -- every other section, section 10 if the file has one, unknown sections -- is copied byte for byte.
     NO CONTRIBUTION TRANSCRIPT IS WRITTEN: `snarkjs zkey verify` checks the chain of contributions recorded in section 10, and producing that
     record (the challenge hashes and the proof of knowledge of delta) is out of scope here; the key proves and verifies, it does not pass
-    `zkey verify`."""
+    `zkey verify`.  VerifyZkey below is the check this module offers in its place: the key against its circuit and transcript."""
     delta = int(delta) % R
     if delta == 0:
         raise ValueError("delta must not be 0 mod r")
@@ -821,3 +821,101 @@ def ContributeDelta(zkey_in, zkey_out, delta):
     out[d1 + G1_BYTES:d1 + G1_BYTES + G2_BYTES] = np.frombuffer(G2ToZkey(G2_INF if p is None else (p[0], p[1], (1, 0))), dtype=np.uint8)
     out.flush()
     del out
+
+
+# ---- checking a key and a transcript ---------------------------------------------------------------------------------------------
+class CheckReport:
+    """The outcome of VerifyZkey / VerifyPtau: truthy only when every check passed.  `checks`: [(name, ok, lhs, rhs)] in the order they
+    were made, the two points of a check as affine int tuples (None = infinity; None, None for the host-side checks; the coefs checks
+    carry the number of differing rows as lhs); `failed`: the names of the checks that did not pass; `points[name]` = (lhs, rhs)."""
+
+    def __init__(self, checks, seed):
+        self.checks, self.seed = list(checks), seed
+        self.failed = [name for name, ok, _, _ in self.checks if not ok]
+        self.points = {name: (lhs, rhs) for name, _, lhs, rhs in self.checks}
+
+    def __bool__(self):
+        return not self.failed
+
+    def __repr__(self):
+        return "%s(%s)" % (type(self).__name__, "all %d checks passed" % len(self.checks) if self else "FAILED: " + ", ".join(self.failed))
+
+
+class ZkeyReport(CheckReport):
+    pass
+
+
+class PtauReport(CheckReport):
+    pass
+
+
+def _challenge(seed):
+    """A challenge in 1 .. r - 1: from `seed` (tests: reproducible) or from the operating system's randomness."""
+    if seed is None:
+        import secrets
+        return 1 + secrets.randbelow(R - 1)
+    import random
+    return random.Random(seed).randrange(1, R)
+
+
+def VerifyZkey(r1cs_path, ptau_path, zkey_path, seed=None, timing=None):
+    """Is the key at `zkey_path` the Groth16 key of the circuit at `r1cs_path` over the transcript at `ptau_path`, with C and H scaled by
+    the delta of its header?  -> ZkeyReport.  Host side: the counts of the three files against each other (a mismatch is a ValueError that
+    names file and section, raised before the device is touched), then the checks `header` (alfa1 / beta1 / beta2 against the transcript,
+    gamma2 = the generator) and `delta` (delta1 finite, e(delta1, G2) = e(G1, delta2)).  Device side (gs_groth16_key_check): coefs A,
+    coefs B, A, B1, B2, IC, C, H -- random linear combinations of every section against combinations of transcript points whose scalars
+    come from the circuit, for a challenge drawn after the files are opened (`seed`: a fixed one, for tests).  A wrong key passes with
+    probability at most max(nVars, 2 domainSize) / r.  What this proves: the key's relation to THIS circuit and THIS transcript.  What it
+    does not: who contributed to either (no contribution chain is read or checked), or that the transcript is sound -- see VerifyPtau.
+    `timing`: a dict that receives the device milliseconds of the check (gs_last_timing) and the wall milliseconds of the whole call."""
+    import time
+    t0 = time.perf_counter()
+    r1cs, ptau, z = ReadR1cs(r1cs_path), ReadPtau(ptau_path), ReadZkey(zkey_path)
+    k = _setup_domain_bits(r1cs)
+    m = 1 << k
+    for name, have, want in (("nVars", z.nVars, r1cs.nVars), ("nPublic", z.nPublic, r1cs.nPublic), ("domainSize", z.domainSize, m)):
+        if have != want:
+            raise ValueError("%s: section %s: %s = %d, but the circuit %s (section %s) needs %d"
+                             % (zkey_path, _ZKEY_NAMES[2], name, have, r1cs_path, _R1CS_NAMES[1], want))
+    if ptau.power < k:
+        raise ValueError("%s: section %s: power = %d, but the key's domain of 2^%d points needs a transcript of at least that power"
+                         % (ptau_path, _PTAU_NAMES[1], ptau.power, k))
+    s = _challenge(seed)
+    header = (z.alfa1 == G1FromZkey(ptau.alphaTauG1[:G1_BYTES]) and z.beta1 == G1FromZkey(ptau.betaTauG1[:G1_BYTES])
+              and _g2(z.beta2) == _g2(G2FromZkey(ptau.betaG2)) and _g2(z.gamma2) == G2_GEN)
+    from . import bn128
+    neg = lambda p: (p[0], (Q - p[1]) % Q, p[2])      # noqa: E731
+    delta = z.delta1[2] % Q != 0 and _g2(z.delta2)[2] != (0, 0) and bn128.PairingCheck([z.delta1, neg(G1_GEN)], [G2_GEN, _g2(z.delta2)])
+    checks = [("header", bool(header), None, None), ("delta", bool(delta), None, None)]
+    capi.init()
+    up1, up2 = capi.g1_upload_affine_mont, capi.g2_upload_affine_mont
+    tau1 = up1(ptau.tauG1[:min(2 * m, (2 << ptau.power) - 1) * G1_BYTES])
+    checks += capi.groth16_key_check(up1(z.A), up1(z.B1), up2(z.B2), up1(z.IC), up1(z.C), up1(z.H), DeviceZkeyR1CS(k, z.nVars, z.coefs),
+                                     _setup_system(r1cs, k), tau1, up2(ptau.tauG2[:m * G2_BYTES]), up1(ptau.alphaTauG1[:m * G1_BYTES]),
+                                     up1(ptau.betaTauG1[:m * G1_BYTES]), _g2(z.delta2), k, z.nPublic, s)
+    if timing is not None:
+        timing.update(capi.last_timing(), wall_ms=(time.perf_counter() - t0) * 1e3, log2_domain=k, nVars=z.nVars)
+    return ZkeyReport(checks, s)
+
+
+def VerifyPtau(ptau_path, power=None, seed=None, timing=None):
+    """Is the transcript at `ptau_path` consistent with itself over its first 2^power powers (default: all it holds)?  -> PtauReport of
+    gs_ptau_check's checks: tauG1[0] and tauG2[0] are the generators, both sections are the powers of ONE tau, alphaTauG1 and betaTauG1 are
+    geometric with that ratio, betaG2 carries betaTauG1[0]'s scalar.  What this does not prove: who contributed -- the contribution chain of
+    a ceremony (challenge hashes, proofs of knowledge) is out of scope."""
+    import time
+    t0 = time.perf_counter()
+    ptau = ReadPtau(ptau_path)
+    power = ptau.power if power is None else int(power)
+    if not 1 <= power <= ptau.power:
+        raise ValueError("%s: section %s: power = %d, so 2^%d powers cannot be checked (1 <= power <= %d)"
+                         % (ptau_path, _PTAU_NAMES[1], ptau.power, power, ptau.power))
+    s = _challenge(seed)
+    n = 1 << power
+    capi.init()
+    up1 = capi.g1_upload_affine_mont
+    checks = capi.ptau_check(up1(ptau.tauG1[:(2 * n - 1) * G1_BYTES]), capi.g2_upload_affine_mont(ptau.tauG2[:n * G2_BYTES]),
+                             up1(ptau.alphaTauG1[:n * G1_BYTES]), up1(ptau.betaTauG1[:n * G1_BYTES]), _g2(G2FromZkey(ptau.betaG2)), power, s)
+    if timing is not None:
+        timing.update(capi.last_timing(), wall_ms=(time.perf_counter() - t0) * 1e3, power=power)
+    return PtauReport(checks, s)

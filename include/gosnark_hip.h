@@ -283,6 +283,93 @@ int gs_g1_scale(gs_handle bases, const uint64_t k[4], gs_handle* out);
 int gs_g1_download_affine_mont(gs_handle bases, void* bytes /* n x 64 */, size_t n);
 int gs_g2_download_affine_mont(gs_handle bases, void* bytes /* n x 128 */, size_t n);
 
+/* ---- checking a key and a transcript: is this .zkey the key of THIS circuit over THIS transcript? ------------------------------- */
+/* Every array of a Groth16 key is a linear image of the transcript's points, so a random linear combination of a section equals a
+ * combination of transcript points whose scalars come out of the circuit alone: the prover's own pipeline with a challenge vector in the
+ * witness's place (sparse rows times a vector, values -> coefficients, MSM).  Only scalars go through a transform; the group work is
+ * about a dozen table-free MSMs and two pairing products, against the five transforms in the group of a second setup.
+ *
+ * Notation: m = 2^log2_domain; M' = (A', B', C') the circuit's system with the rows nConstraints + s = (signal s, 1), s <= npublic,
+ * appended to A' (what the setup sums over); rho_i = s^(i+1), i < nvars, and sigma_j = s^(j+1), j < m, for the challenge s (made on
+ * the device); rho^pub = rho with the entries i > npublic zeroed, rho^prv = rho - rho^pub; p_X(x) = the m coefficients of the
+ * interpolant of X' x on the domain (row j at w^j, w = 5^((r-1)/m)).  Every check has a left point from the key and a right point
+ * from circuit and transcript:
+ *
+ *   0 coefs A   A_key rho                         A' rho                             the value vectors are equal, A_key / B_key = the
+ *   1 coefs B   B_key rho                         B' rho                             key's own section 4 (lhs[0] = rows that differ)
+ *   2 A         MSM(A, rho)                       MSM(tauG1[0..m), p_A(rho))         equal points
+ *   3 B1        MSM(B1, rho)                      MSM(tauG1[0..m), p_B(rho))         equal points
+ *   4 B2        MSM(B2, rho)                      MSM(tauG2[0..m), p_B(rho))         equal points (G2)
+ *   5 IC        MSM(IC, rho[0..npublic])          K(rho^pub)                         equal points
+ *   6 C         MSM(C, rho[npublic+1..])          K(rho^prv)                         e(lhs, delta2) = e(rhs, G2)
+ *   7 H         MSM(H, sigma)                     MSM(tauG1[0..m), c) - MSM(tauG1[m..m+cnt), c[0..cnt))     e(lhs, delta2) = e(rhs, G2)
+ *
+ * with K(x) = MSM(betaTauG1, p_A(x)) + MSM(alphaTauG1, p_B(x)) + MSM(tauG1, p_C(x)), and for H: c_t = (1/2) v^(-t) q_t, q = the
+ * coefficients of the interpolant of sigma, v = 5^((r-1)/(2m)); cnt = m when the transcript holds 2m or more tauG1 points and m - 1
+ * otherwise.  That is gs_g1_lagrange's odd_half form read as a transposed map: H_j = (1/2m) sum_{i<2m} v^(-(2j+1)i) tau^i G / delta,
+ * so the coefficient of tau^i G in sum_j sigma_j H_j delta is (1/2) v^(-i) q_(i mod m), and v^m = -1 gives c_(t+m) = -c_t; a missing
+ * tauG1[2m-1] is the point at infinity, as there -- a key set up from a transcript of exactly 2m - 1 points and one set up from a longer
+ * transcript differ in H, and each passes against its own transcript only.
+ *
+ * SOUNDNESS is Schwartz-Zippel over the challenge: both sides of every check are polynomials in s of degree at most max(nvars, 2m), so a
+ * wrong key passes for at most max(nvars, 2m) values of s out of r ~ 2^254.  The caller draws s AFTER the key, the circuit and the
+ * transcript are fixed (go-snark-study_amd/circom.py: VerifyZkey).  WHAT THIS PROVES: the key's arrays are the ones a setup of this circuit over this
+ * transcript yields, scaled by the delta of its header.  WHAT IT DOES NOT: who contributed to the transcript or to delta -- the
+ * contribution chain of a ceremony (challenge hashes, proofs of knowledge) is out of scope; and the header points themselves (alpha1,
+ * beta1, beta2, gamma2, delta1 against delta2) are a few host comparisons and one pairing product that the caller makes (VerifyZkey).
+ *
+ * Handles: a, b1, b2 (nvars points), ic (npublic + 1), c (nvars - npublic - 1: section 8 as it lies in the file), h (m): the key's
+ * arrays from gs_g1_upload_affine_mont / gs_g2_upload_affine_mont; key_system: gs_r1cs_upload_zkey of the key's section 4;
+ * circuit_system: gs_r1cs_upload_domain of M'; tau_g1 (at least 2m - 1 points), tau_g2, alpha_tau_g1, beta_tau_g1 (at least m).
+ * delta2: a Jacobian triple, standard form; it must be a point of the order-r subgroup (the rule of gs_pairing_check), else C and H fail.
+ * Every MSM of the check is summed TABLE-FREE whatever the table policy -- each array is used once -- and after the call none of the
+ * handles owns a window table (one it had is released); the call leaves no device memory behind except caches gs_trim frees.
+ * Blocking; gs_last_timing has the device time (plan_ms, accumulate_ms, reduce_ms of the MSMs, poly_ms = the scalar side).
+ * GS_ERR_SHAPE when the handles do not fit each other, GS_ERR_ARG for a bad handle or s = 0 mod r.
+ *
+ * gs_ptau_check: the same machinery on the transcript itself, for its first N = 2^log2_n powers (2N - 1 of tauG1), rho_i = s^(i+1):
+ *   0 g1          tauG1[0]                        G1                                 equal points
+ *   1 g2          tauG2[0]                        G2                                 equal points
+ *   2 tau         tauG1[1]                        tauG2[1]                           e(lhs, G2) = e(G1, rhs)
+ *   3 tauG1       sum_{i<2N-2} rho_i tauG1[i]     sum rho_i tauG1[i+1]               e(lhs, tauG2[1]) = e(rhs, G2)
+ *   4 tauG2       sum_{i<N-1} rho_i tauG2[i]      sum rho_i tauG2[i+1]               e(tauG1[1], lhs) = e(G1, rhs)
+ *   5 alphaTauG1  sum_{i<N-1} rho_i alphaTauG1[i] sum rho_i alphaTauG1[i+1]          e(lhs, tauG2[1]) = e(rhs, G2)
+ *   6 betaTauG1   the same over betaTauG1
+ *   7 betaG2      betaTauG1[0]                    betaG2                             e(lhs, G2) = e(G1, rhs)
+ * Together: tauG1[i] = tau^i G1, tauG2[i] = tau^i G2 for ONE tau, alphaTauG1 and betaTauG1 are geometric with that ratio, and betaG2 has
+ * betaTauG1[0]'s scalar.  The shifted sums are one MSM plan over two offsets of the resident array.  Soundness as above with degree 2N.
+ *
+ * Results: a point is affine, standard form, G1 in words 0..7 (x | y), G2 in words 0..15 (x.c0 | x.c1 | y.c0 | y.c1), zero at infinity.
+ * gs_check_report is written through the caller's pointer: gs_check_abi_sizes tells a binding of another revision before it passes a
+ * short buffer. */
+#define GS_CHECK_MAX 8
+enum { GS_KEY_COEFS_A = 0, GS_KEY_COEFS_B, GS_KEY_A, GS_KEY_B1, GS_KEY_B2, GS_KEY_IC, GS_KEY_C, GS_KEY_H };
+enum { GS_PTAU_G1 = 0, GS_PTAU_G2, GS_PTAU_TAU, GS_PTAU_TAU_G1, GS_PTAU_TAU_G2, GS_PTAU_ALPHA_TAU_G1, GS_PTAU_BETA_TAU_G1, GS_PTAU_BETA_G2 };
+typedef struct {
+  int32_t ok;                       /* 1 = the check passed */
+  int32_t lhs_g2, rhs_g2;           /* which group each point lives in */
+  int32_t lhs_inf, rhs_inf;
+  int32_t reserved;
+  uint64_t lhs[16], rhs[16];
+} gs_check_result;
+typedef struct {
+  uint32_t nchecks;                 /* entries of `check` in use */
+  uint32_t failed;                  /* bit i set: check i failed */
+  gs_check_result check[GS_CHECK_MAX];
+} gs_check_report;
+typedef struct {
+  gs_handle a, b1, b2, ic, c, h;                        /* the key's arrays (sections 5, 6, 7, 3, 8, 9) */
+  gs_handle key_system, circuit_system;
+  gs_handle tau_g1, tau_g2, alpha_tau_g1, beta_tau_g1;  /* the transcript (sections 2 .. 5) */
+  uint64_t delta2[24];
+  uint64_t challenge[4];                                /* s, any 256-bit value, not 0 mod r */
+  uint64_t log2_domain, npublic;
+} gs_key_check_input;
+int gs_groth16_key_check(const gs_key_check_input* in, gs_check_report* out);
+int gs_ptau_check(gs_handle tau_g1, gs_handle tau_g2, gs_handle alpha_tau_g1, gs_handle beta_tau_g1, const uint64_t beta_g2[24], size_t log2_n,
+                  const uint64_t challenge[4], gs_check_report* out);
+int gs_check_abi_sizes(size_t* input_bytes, size_t* report_bytes);
+
 /* ---- Groth16 prover (groth16/groth16.go) --------------------------------------------------- */
 /* Device-resident proving key: groth16.Pk (groth16.go:15-32).  At, BACGamma (G1), BACDelta:
  * m points; G2 BACGamma: m points; PowersTauDelta: len(Z) points; single points as Jacobian

@@ -2,64 +2,25 @@
 
     python tools/time_setup_ptau.py 16 profiles/setup_ptau_timing.txt      (appends; one process per size)
 
-The circuit has fan-in 2 per linear combination, 90 % of the coefficients in {1, r - 1}, 5 % below 2^16, 5 % of 251 bits, and signal 0 in
-every row of A; it is written as circuit.r1cs with vectorised numpy, the transcript from toxic values with circom.WritePtau.  Reported: the
+The circuit is tools/synth_circuit.py's (fan-in 2 per linear combination, 90 % of the coefficients in {1, r - 1}, 5 % below 2^16, 5 % of
+251 bits, signal 0 in every row of A), the transcript is written from toxic values with circom.WritePtau.  Reported: the
 five transforms and the four column sums by HIP events around each call's device work (SetupFromPtau's timing=), the records, downloads
 and file writing by the wall clock, and gs_memory_query's library_bytes sampled between device calls.
 GS_TIMING_DRY=1: the host half only (write and parse the circuit, build the records of section 4)."""
 import os
-import struct
 import sys
 import time
-
-import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import gosnark_amd  # noqa: F401,E402
 from gosnark_amd import capi, circom  # noqa: E402
+from synth_circuit import write_r1cs  # noqa: E402
 
-R = circom.R
 k, out_path = int(sys.argv[1]), sys.argv[2]
 work = os.environ.get("TMPDIR", "/tmp")
-rng = np.random.default_rng(k)
-npub, nc = 1, (1 << k) - 2 - 7
-nw = 1 + npub + 1 + nc
 t0 = time.perf_counter()
-# circuit.r1cs, vectorised: A = c0 * w0 + c1 * w[x], B = two terms, C = 1 * w[new]
-def coefs(n):
-    u = rng.random(n)
-    v = np.zeros((n, 4), dtype="<u8")
-    rm1 = np.frombuffer((R - 1).to_bytes(32, "little"), dtype="<u8")
-    v[u < 0.45, 0] = 1
-    v[(u >= 0.45) & (u < 0.9)] = rm1
-    small = (u >= 0.9) & (u < 0.95)
-    v[small, 0] = rng.integers(2, 1 << 16, size=int(small.sum()), dtype=np.uint64)
-    wide = u >= 0.95
-    w = rng.integers(0, 1 << 62, size=(int(wide.sum()), 4), dtype=np.uint64)
-    w[:, 3] &= (1 << 59) - 1
-    v[wide] = w
-    return v
-term = np.dtype([("wire", "<u4"), ("value", "<u8", (4,))])
-cons = np.dtype([("na", "<u4"), ("a", term, (2,)), ("nb", "<u4"), ("b", term, (2,)), ("nc", "<u4"), ("c", term, (1,))])
-assert cons.itemsize == 192
-body = np.zeros(nc, dtype=cons)
-body["na"], body["nb"], body["nc"] = 2, 2, 1
-new = 2 + npub + np.arange(nc, dtype=np.uint32)
-body["a"]["wire"][:, 0] = 0
-body["a"]["wire"][:, 1] = rng.integers(0, new, dtype=np.uint32)
-body["b"]["wire"][:, 0] = rng.integers(0, new, dtype=np.uint32)
-body["b"]["wire"][:, 1] = rng.integers(0, new, dtype=np.uint32)
-body["c"]["wire"][:, 0] = new
-body["a"]["value"] = coefs(2 * nc).reshape(nc, 2, 4)
-body["b"]["value"] = coefs(2 * nc).reshape(nc, 2, 4)
-body["c"]["value"][:, 0, 0] = 1
 r1cs, ptau, zkey = (os.path.join(work, "timing_%d.%s" % (k, e)) for e in ("r1cs", "ptau", "zkey"))
-head = struct.pack("<I", 32) + R.to_bytes(32, "little") + struct.pack("<IIIIQI", nw, 0, npub, 1, nw, nc)
-with open(r1cs, "wb") as f:
-    f.write(b"r1cs" + struct.pack("<II", 1, 2))
-    f.write(struct.pack("<IQ", 1, len(head)) + head)
-    f.write(struct.pack("<IQ", 2, body.nbytes))
-    body.tofile(f)
+npub, nc, nw = write_r1cs(k, r1cs)
 t1 = time.perf_counter()
 if os.environ.get("GS_TIMING_DRY"):                      # host half only: parse the file, build the records
     r = circom.ReadR1cs(r1cs)
