@@ -112,6 +112,8 @@ _SIGS = {
     "gs_g1_scale": [Handle, u64p, ctypes.POINTER(Handle)],
     "gs_g1_download_affine_mont": [Handle, ctypes.c_void_p, ctypes.c_size_t],
     "gs_g2_download_affine_mont": [Handle, ctypes.c_void_p, ctypes.c_size_t],
+    "gs_g1_scale_powers": [Handle, ctypes.c_size_t, ctypes.c_size_t, u64p, u64p, ctypes.POINTER(Handle)],
+    "gs_g2_scale_powers": [Handle, ctypes.c_size_t, ctypes.c_size_t, u64p, u64p, ctypes.POINTER(Handle)],
     "gs_groth16_key_check": [ctypes.POINTER(KeyCheckInput), ctypes.POINTER(CheckReport)],
     "gs_ptau_check": [Handle, Handle, Handle, Handle, u64p, ctypes.c_size_t, u64p, ctypes.POINTER(CheckReport)],
     "gs_check_abi_sizes": [ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)],
@@ -582,6 +584,22 @@ def g1_scale(bases, k):
     cell = HandleCell()
     call("gs_g1_scale", raw(bases), ptr64(ints_to_u64([int(k) % R])), cell.ref)
     return cell.result()
+
+
+def _scale_powers(name, bases, off, n, c, t):
+    cell = HandleCell()
+    ct = ints_to_u64([int(c) % (1 << 256), int(t) % (1 << 256)])       # any 256-bit value: the library reduces mod r
+    call(name, raw(bases), int(off), int(n), ptr64(ct[0]), ptr64(ct[1]), cell.ref)
+    return cell.result()
+
+
+def g1_scale_powers(bases, off, n, c, t):
+    """gs_g1_scale_powers: out[i] = (c * t^i mod r) * P[off + i], i < n -> a base-array handle (t^0 = 1 also for t = 0)."""
+    return _scale_powers("gs_g1_scale_powers", bases, off, n, c, t)
+
+
+def g2_scale_powers(bases, off, n, c, t):
+    return _scale_powers("gs_g2_scale_powers", bases, off, n, c, t)
 
 
 def _check_report(rep, names):

@@ -657,6 +657,119 @@ def WritePtau(path, power, tau, alpha, beta, extra_sections=()):
             f.write(struct.pack("<IQ", sid, len(payload)) + payload)
 
 
+def NewPtau(path, power):
+    """The transcript of tau = alpha = beta = 1 -> a .ptau file of 2^power: every point is its generator, sections 1 - 6.  The starting
+    point of a chain of ContributePtau calls; host code only, written in pieces (power 28 is a 137 GB file, not 137 GB of memory)."""
+    power = int(power)
+    if not 0 <= power <= 28:
+        raise ValueError("%s: power = %d is not in 0 .. 28" % (path, power))
+    n = 1 << power
+    g1, g2 = G1ToZkey(G1_GEN), G2ToZkey(G2_GEN)
+    head = struct.pack("<I", 32) + Q.to_bytes(32, "little") + struct.pack("<II", power, power)
+    piece = 1 << 16                                                 # points per write
+    with open(path, "wb") as f:
+        f.write(b"ptau" + struct.pack("<II", 1, 6))
+        f.write(struct.pack("<IQ", 1, len(head)) + head)
+        for sid, point, count in ((2, g1, 2 * n - 1), (3, g2, n), (4, g1, n), (5, g1, n), (6, g2, 1)):
+            f.write(struct.pack("<IQ", sid, count * len(point)))
+            block = point * min(count, piece)
+            for _ in range(count // piece):
+                f.write(block)
+            f.write(point * (count % piece))
+
+
+_PTAU_PREPARED = (12, 13, 14, 15)      # the prepared Lagrange bases of a transcript: stale after a contribution, and computed here anyway
+
+
+def _ptau_section_list(data):
+    """Every section of an already validated .ptau memory map, in file order: [(id, offset, length)]."""
+    nsec = struct.unpack("<I", bytes(data[8:12]))[0]
+    out, pos = [], 12
+    for _ in range(nsec):
+        sid, length = struct.unpack("<IQ", bytes(data[pos:pos + 12]))
+        out.append((sid, pos + 12, length))
+        pos += 12 + length
+    return out
+
+
+def ContributePtau(ptau_in, ptau_out, tau, alpha, beta, slab_log2=22, timing=None):
+    """One phase-1 contribution with the secrets tau, alpha, beta, on the points (nobody needs to know the transcript's own tau):
+        tauG1[i] *= tau^i    tauG2[i] *= tau^i    alphaTauG1[i] *= alpha tau^i    betaTauG1[i] *= beta tau^i    betaG2 *= beta
+    Every section streams through the device in slabs of at most 2^slab_log2 points -- memory-mapped input -> gs_g*_upload_affine_mont ->
+    gs_g*_scale_powers -> gs_g*_download_affine_mont into the memory-mapped output -- the slab that starts at index s with the factor
+    c tau^s, and a slab's handles are freed before the next is uploaded: the device holds the input and the output of one slab (beside
+    the upload's staging copy and the series of that slab), whatever the power.  The header is copied (ceremonyPower included); section 7 and every unknown section are copied as found; the prepared
+    Lagrange bases, sections 12 - 15, are DROPPED: they would be stale, and SetupFromPtau computes the bases itself.
+    NO CONTRIBUTION RECORD IS WRITTEN: no proof of knowledge of the secrets, no challenge hash, nothing appended to section 7 -- the same
+    statement ContributeDelta makes for a key.  The result is a transcript for SetupFromPtau / VerifyPtau of this module; `snarkjs
+    powersoftau verify` checks the chain of records and will not accept it.
+    `timing`: a dict that receives the wall milliseconds of parsing, uploads, downloads and file writing, the device milliseconds of the
+    multiplications (gs_last_timing), the wall milliseconds of the whole call and the largest gs_memory_query library_bytes seen between
+    two device calls."""
+    import os
+    import time
+    t0 = time.perf_counter()
+    tau, alpha, beta = int(tau) % R, int(alpha) % R, int(beta) % R
+    for name, v in (("tau", tau), ("alpha", alpha), ("beta", beta)):
+        if v == 0:
+            raise ValueError("%s must not be 0 mod r" % name)
+    slab_log2 = int(slab_log2)
+    if not 0 <= slab_log2 <= 28:
+        raise ValueError("slab_log2 = %d is not in 0 .. 28" % slab_log2)
+    ptau = ReadPtau(ptau_in)
+    if os.path.exists(ptau_out) and os.path.samefile(ptau_in, ptau_out):
+        raise ValueError("%s: the output must not be the input file (the input is read while the output is written)" % ptau_out)
+    data = np.memmap(ptau_in, dtype=np.uint8, mode="r")
+    keep = [s for s in _ptau_section_list(data) if s[0] not in _PTAU_PREPARED]
+    ms = {"parse_ms": (time.perf_counter() - t0) * 1e3, "upload_ms": 0.0, "device_ms": 0.0, "download_ms": 0.0, "write_ms": 0.0,
+          "library_bytes_max": 0, "slabs": 0}
+    capi.init()
+    t1 = time.perf_counter()
+    with open(ptau_out, "wb") as f:
+        f.truncate(12 + sum(12 + length for _, _, length in keep))
+    out = np.memmap(ptau_out, dtype=np.uint8, mode="r+")
+    put = lambda at, b: out.__setitem__(slice(at, at + len(b)), np.frombuffer(b, dtype=np.uint8))      # noqa: E731
+    put(0, b"ptau" + struct.pack("<II", 1, len(keep)))
+    ms["write_ms"] += (time.perf_counter() - t1) * 1e3
+    # section id -> (point bytes, upload, scale, download, the factor of point 0, the ratio)
+    g1 = (G1_BYTES, capi.g1_upload_affine_mont, capi.g1_scale_powers, capi.g1_download_affine_mont)
+    g2 = (G2_BYTES, capi.g2_upload_affine_mont, capi.g2_scale_powers, capi.g2_download_affine_mont)
+    plan = {2: g1 + (1, tau), 3: g2 + (1, tau), 4: g1 + (alpha, tau), 5: g1 + (beta, tau), 6: g2 + (beta, 1)}
+    slab, pos = 1 << slab_log2, 12
+    for sid, off, length in keep:
+        put(pos, struct.pack("<IQ", sid, length))
+        pos += 12
+        if sid not in plan:
+            t1 = time.perf_counter()
+            out[pos:pos + length] = data[off:off + length]
+            ms["write_ms"] += (time.perf_counter() - t1) * 1e3
+            pos += length
+            continue
+        size, up, scale, down, c, t = plan[sid]
+        for s in range(0, length // size, slab):
+            cnt = min(slab, length // size - s)
+            t1 = time.perf_counter()
+            src = up(data[off + s * size:off + (s + cnt) * size])
+            t2 = time.perf_counter()
+            dst = scale(src, 0, cnt, c * pow(t, s, R) % R, t)
+            ms["device_ms"] += capi.last_timing()["total_ms"]
+            ms["library_bytes_max"] = max(ms["library_bytes_max"], capi.memory_query()["library_bytes"])
+            src.free()
+            t3 = time.perf_counter()
+            down(dst, out[pos + s * size:pos + (s + cnt) * size])
+            dst.free()
+            ms["upload_ms"] += (t2 - t1) * 1e3
+            ms["download_ms"] += (time.perf_counter() - t3) * 1e3
+            ms["slabs"] += 1
+        pos += length
+    t1 = time.perf_counter()
+    out.flush()
+    del out
+    ms["write_ms"] += (time.perf_counter() - t1) * 1e3
+    if timing is not None:
+        timing.update(ms, wall_ms=(time.perf_counter() - t0) * 1e3, power=ptau.power)
+
+
 def _coef_values(vals):
     """[n, 4] uint64 standard-form values -> [n, 32] uint8 of v * 2^512 mod r: one big-integer product per DISTINCT value (the values
     below 2^64 and the wider ones are told apart first: the first are sorted as machine words)."""

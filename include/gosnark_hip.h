@@ -283,6 +283,22 @@ int gs_g1_scale(gs_handle bases, const uint64_t k[4], gs_handle* out);
 int gs_g1_download_affine_mont(gs_handle bases, void* bytes /* n x 64 */, size_t n);
 int gs_g2_download_affine_mont(gs_handle bases, void* bytes /* n x 128 */, size_t n);
 
+/* ---- contributing to a transcript: one phase-1 (powers-of-tau) contribution on the points ---------------------------------------- */
+/* A contribution multiplies a new secret into a transcript whose tau nobody knows: tauG1[i] *= tau^i, tauG2[i] *= tau^i,
+ * alphaTauG1[i] *= alpha tau^i, betaTauG1[i] *= beta tau^i, betaG2 *= beta -- an array of points by a geometric series of scalars.
+ *
+ * gs_g1_scale_powers / gs_g2_scale_powers: out = a new base array of n points, out[i] = (c t^i mod r) P[off + i].  c and t are any
+ * 256-bit values and count mod r; t^0 = 1 also for t = 0 (out[0] = c P[off], every later point is infinity); t = 1 is a uniform scale
+ * (the G2 twin gs_g1_scale lacks); n = 0 gives an empty array; off + n beyond the array is GS_ERR_SHAPE, a bad handle or a null pointer
+ * GS_ERR_ARG.  The series is built on the device, so the n scalars never exist on the host; one kernel launch reads the affine points,
+ * multiplies each through 4-bit windows (256 doublings and at most 64 + 14 general additions, the 16-point table in private memory)
+ * and writes affine points (one field inversion per point).  Every addition is the complete one: the input may
+ * hold infinities, equal and opposite points, and every scalar including 0 is legal.  A caller that streams a long section in slabs
+ * passes c t^s for the slab that starts at index s.  Blocking; gs_last_timing().total_ms = device time.
+ * go-snark-study_amd/circom.py (ContributePtau) drives them over a .ptau file; go/gosnarkhip/ptau.go and tests/c/ptau_contribute.c are the same sequence. */
+int gs_g1_scale_powers(gs_handle bases, size_t off, size_t n, const uint64_t c[4], const uint64_t t[4], gs_handle* out);
+int gs_g2_scale_powers(gs_handle bases, size_t off, size_t n, const uint64_t c[4], const uint64_t t[4], gs_handle* out);
+
 /* ---- checking a key and a transcript: is this .zkey the key of THIS circuit over THIS transcript? ------------------------------- */
 /* Every array of a Groth16 key is a linear image of the transcript's points, so a random linear combination of a section equals a
  * combination of transcript points whose scalars come out of the circuit alone: the prover's own pipeline with a challenge vector in the
