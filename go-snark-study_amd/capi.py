@@ -117,6 +117,10 @@ _SIGS = {
     "gs_groth16_key_check": [ctypes.POINTER(KeyCheckInput), ctypes.POINTER(CheckReport)],
     "gs_ptau_check": [Handle, Handle, Handle, Handle, u64p, ctypes.c_size_t, u64p, ctypes.POINTER(CheckReport)],
     "gs_check_abi_sizes": [ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)],
+    "gs_g1_lagrange_levels": [Handle, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(Handle)],
+    "gs_g2_lagrange_levels": [Handle, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(Handle)],
+    "gs_g1_lagrange_levels_check": [Handle, Handle, ctypes.c_size_t, u64p, ctypes.POINTER(CheckResult)],
+    "gs_g2_lagrange_levels_check": [Handle, Handle, ctypes.c_size_t, u64p, ctypes.POINTER(CheckResult)],
     "gs_groth16_pk_create": [Handle, Handle, Handle, Handle, Handle, u64p, u64p, u64p, u64p, u64p,
                              u64p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(Handle)],
     "gs_groth16_prove": [Handle, u64p, ctypes.c_size_t, u64p, ctypes.c_size_t, u64p, u64p, u64p, intp],
@@ -636,6 +640,40 @@ def ptau_check(tau_g1, tau_g2, alpha_tau_g1, beta_tau_g1, beta_g2, log2_n, chall
     call("gs_ptau_check", raw(tau_g1), raw(tau_g2), raw(alpha_tau_g1), raw(beta_tau_g1), ptr64(g2_points_to_u64([beta_g2]).reshape(-1)), int(log2_n),
          ptr64(ints_to_u64([int(challenge) % (1 << 256)]).reshape(-1)), ctypes.byref(rep))
     return _check_report(rep, PTAU_CHECKS)
+
+
+def _lagrange_levels(name, powers, lo, hi):
+    cell = HandleCell()
+    call(name, raw(powers), int(lo), int(hi), cell.ref)
+    return cell.result()
+
+
+def g1_lagrange_levels(powers, lo, hi):
+    """gs_g1_lagrange_levels: the Lagrange bases of the domains 2^lo .. 2^hi over the first points of `powers`, every level's stage of one
+    span in one launch -> a base-array handle of 2^(hi+1) - 2^lo points, level p at index 2^p - 2^lo (an array of exactly 2^hi - 1
+    points: the missing last point of level hi is the point at infinity)."""
+    return _lagrange_levels("gs_g1_lagrange_levels", powers, lo, hi)
+
+
+def g2_lagrange_levels(powers, lo, hi):
+    return _lagrange_levels("gs_g2_lagrange_levels", powers, lo, hi)
+
+
+def _lagrange_levels_check(name, check_name, powers, levels, hi, challenge):
+    rep = CheckReport()
+    rep.nchecks = 1
+    call(name, raw(powers), raw(levels), int(hi), ptr64(ints_to_u64([int(challenge) % (1 << 256)]).reshape(-1)), ctypes.byref(rep.check[0]))
+    return _check_report(rep, (check_name,))[0]
+
+
+def g1_lagrange_levels_check(powers, levels, hi, challenge, name="levels"):
+    """gs_g1_lagrange_levels_check: are the first 2^(hi+1) - 1 points of `levels` the levels 0 .. hi of `powers`?  Two sums and a scalar
+    transform, for the challenge s -> (name, ok, lhs, rhs), the points as affine int tuples (None = infinity)."""
+    return _lagrange_levels_check("gs_g1_lagrange_levels_check", name, powers, levels, hi, challenge)
+
+
+def g2_lagrange_levels_check(powers, levels, hi, challenge, name="levels"):
+    return _lagrange_levels_check("gs_g2_lagrange_levels_check", name, powers, levels, hi, challenge)
 
 
 def scalars_upload(s_u64):

@@ -522,10 +522,19 @@ def ConvertProvingKey(pkj, vk_json, path):
 #                       3: wire -> label map (ignored)      4, 5: custom gates (must be empty)
 #   .ptau  "ptau" v1    1: u32 n8 (32), q, u32 power, u32 ceremonyPower
 #                       2: tauG1, 2^(power+1) - 1 G1     3: tauG2, 2^power G2     4: alphaTauG1, 2^power G1     5: betaTauG1, 2^power G1
-#                       6: betaG2, one G2                7: contributions, 12 - 15: prepared Lagrange bases (all ignored: computed here)
+#                       6: betaG2, one G2                7: contributions, 12 - 15: prepared Lagrange bases (ReadPtau ignores them)
+#                       12: tauG1 Lagrange, levels 0 .. power+1, 2^(power+2) - 1 G1     13: tauG2 Lagrange, levels 0 .. power, 2^(power+1) - 1 G2
+#                       14: alphaTauG1 Lagrange, 15: betaTauG1 Lagrange, levels 0 .. power, 2^(power+1) - 1 G1 each
+#                       level p = the Lagrange basis of the domain 2^p over the section's first 2^p points, at point offset 2^p - 1; level
+#                       power+1 of section 12 is the transform of the 2^(power+1) - 1 tauG1 points and one point at infinity.  This is the
+#                       layout `snarkjs powersoftau prepare phase2` writes as far as its source is understood here: like the rest, it has
+#                       not been checked against a file snarkjs wrote (ReadPtauPrepared is the only place that knows it).
 # Points are in the .zkey encoding.
 _R1CS_NAMES = {1: "1 (header)", 2: "2 (constraints)", 3: "3 (wire map)", 4: "4 (custom gates list)", 5: "5 (custom gates application)"}
 _PTAU_NAMES = {1: "1 (header)", 2: "2 (tauG1)", 3: "3 (tauG2)", 4: "4 (alphaTauG1)", 5: "5 (betaTauG1)", 6: "6 (betaG2)"}
+# ReadPtauPrepared's table: ReadPtau keeps the one above and with it its indifference to whatever sits in sections 12 - 15
+_PTAU_PREPARED_NAMES = {**_PTAU_NAMES, 12: "12 (tauG1 Lagrange)", 13: "13 (tauG2 Lagrange)", 14: "14 (alphaTauG1 Lagrange)",
+                        15: "15 (betaTauG1 Lagrange)"}
 G1_GEN, G2_GEN = (1, 2, 1), ((10857046999023057135944570762232829481370756359578518086990519993285655852781,
                               11559732032986387107991004021392285783925812861821192530917403151452391805634),
                              (8495653923123431417604973247489272438418190587263600148770280649306958101930,
@@ -770,6 +779,120 @@ def ContributePtau(ptau_in, ptau_out, tau, alpha, beta, slab_log2=22, timing=Non
         timing.update(ms, wall_ms=(time.perf_counter() - t0) * 1e3, power=ptau.power)
 
 
+# prepared section -> (the section it is the Lagrange form of, its top level beyond `power`, point bytes)
+_PTAU_LEVELS = {12: (2, 1, G1_BYTES), 13: (3, 0, G2_BYTES), 14: (4, 0, G1_BYTES), 15: (5, 0, G1_BYTES)}
+
+
+class PtauPrepared(Ptau):
+    """Ptau plus the prepared sections: `lagrange[sid]` (sid = 12 .. 15) is the read-only uint8 view of a section, level(sid, p) the view
+    of its level p -- the Lagrange basis of the domain 2^p, 2^p points at point offset 2^p - 1."""
+
+    def __init__(self, ptau, lagrange):
+        Ptau.__init__(self, ptau.power, ptau.ceremonyPower, ptau.tauG1, ptau.tauG2, ptau.alphaTauG1, ptau.betaTauG1, ptau.betaG2)
+        self.lagrange = dict(lagrange)
+
+    def top_level(self, sid):
+        return self.power + _PTAU_LEVELS[sid][1]
+
+    def level(self, sid, p):
+        size = _PTAU_LEVELS[sid][2]
+        if not 0 <= p <= self.top_level(sid):
+            raise ValueError("section %s holds the levels 0 .. %d, level %d was asked for" % (_PTAU_PREPARED_NAMES[sid], self.top_level(sid), p))
+        return self.lagrange[sid][((1 << p) - 1) * size:((2 << p) - 1) * size]
+
+
+def ReadPtauPrepared(path):
+    """A prepared .ptau file -> PtauPrepared: what ReadPtau returns plus the sections 12 - 15 (layout: the comment above ReadR1cs; NOT yet
+    checked against a file written by snarkjs).  A missing prepared section or one of the wrong length is a ValueError that names it.
+    The points are NOT checked here: VerifyPtauPrepared does that."""
+    ptau = ReadPtau(path)
+    N = _PTAU_PREPARED_NAMES
+    data, sec = _read_sections(path, b"ptau", 1, N, _PTAU_PREPARED)
+    for sid in _PTAU_PREPARED:
+        _, extra, size = _PTAU_LEVELS[sid]
+        _expect_len(path, N, sid, sec, ((2 << (ptau.power + extra)) - 1) * size)
+    return PtauPrepared(ptau, {sid: data[sec[sid][0]:sec[sid][0] + sec[sid][1]] for sid in _PTAU_PREPARED})
+
+
+def PreparePtau(ptau_in, ptau_out, batch_log2=20, timing=None):
+    """What `snarkjs powersoftau prepare phase2` does, on the device: the Lagrange bases of every domain 2^0 .. 2^power (2^(power+1) for
+    tauG1) of the four array sections, appended as sections 12 - 15.  Every section of the input is copied in file order -- an existing
+    12 - 15 is dropped and recomputed -- then 12, 13, 14, 15 follow.  Per section: one upload, ONE gs_g*_lagrange_levels call for the
+    levels 0 .. min(top, batch_log2) (every level's stage of one span in one launch), one gs_g*_lagrange call per level above; each result
+    goes straight into its place in the memory-mapped output and its handle is freed before the next call.  Level power+1 of tauG1 is the
+    transform of its 2^(power+1) - 1 points and one point at infinity.  power <= 26 (level power+1 is a transform of 2^27 points at most).
+    NO CONTRIBUTION RECORD IS READ OR WRITTEN, as in ContributePtau; the result is for SetupFromPtau(prepared=True) / VerifyPtauPrepared.
+    `timing`: as ContributePtau's -- wall milliseconds of parsing, uploads, downloads and file writing, device milliseconds of the
+    transforms, the wall milliseconds of the whole call, the largest library_bytes seen, the number of device calls."""
+    import os
+    import time
+    t0 = time.perf_counter()
+    batch_log2 = int(batch_log2)
+    if not 0 <= batch_log2 <= 27:
+        raise ValueError("batch_log2 = %d is not in 0 .. 27" % batch_log2)
+    ptau = ReadPtau(ptau_in)
+    if ptau.power > 26:
+        raise ValueError("%s: section %s: power = %d, preparing needs power <= 26 (level power + 1 is one transform of at most 2^27 points)"
+                         % (ptau_in, _PTAU_NAMES[1], ptau.power))
+    if os.path.exists(ptau_out) and os.path.samefile(ptau_in, ptau_out):
+        raise ValueError("%s: the output must not be the input file (the input is read while the output is written)" % ptau_out)
+    data = np.memmap(ptau_in, dtype=np.uint8, mode="r")
+    keep = [s for s in _ptau_section_list(data) if s[0] not in _PTAU_PREPARED]
+    new = [(sid, ((2 << (ptau.power + _PTAU_LEVELS[sid][1])) - 1) * _PTAU_LEVELS[sid][2]) for sid in _PTAU_PREPARED]
+    ms = {"parse_ms": (time.perf_counter() - t0) * 1e3, "upload_ms": 0.0, "device_ms": 0.0, "download_ms": 0.0, "write_ms": 0.0,
+          "library_bytes_max": 0, "calls": 0}
+    capi.init()
+    t1 = time.perf_counter()
+    with open(ptau_out, "wb") as f:
+        f.truncate(12 + sum(12 + length for _, _, length in keep) + sum(12 + length for _, length in new))
+    out = np.memmap(ptau_out, dtype=np.uint8, mode="r+")
+    put = lambda at, b: out.__setitem__(slice(at, at + len(b)), np.frombuffer(b, dtype=np.uint8))      # noqa: E731
+    put(0, b"ptau" + struct.pack("<II", 1, len(keep) + len(new)))
+    pos = 12
+    for sid, off, length in keep:
+        put(pos, struct.pack("<IQ", sid, length))
+        out[pos + 12:pos + 12 + length] = data[off:off + length]
+        pos += 12 + length
+    ms["write_ms"] += (time.perf_counter() - t1) * 1e3
+    source = {2: ptau.tauG1, 3: ptau.tauG2, 4: ptau.alphaTauG1, 5: ptau.betaTauG1}
+    g1 = (capi.g1_upload_affine_mont, capi.g1_lagrange_levels, capi.g1_lagrange, capi.g1_download_affine_mont)
+    g2 = (capi.g2_upload_affine_mont, capi.g2_lagrange_levels, capi.g2_lagrange, capi.g2_download_affine_mont)
+    for sid, length in new:
+        put(pos, struct.pack("<IQ", sid, length))
+        pos += 12
+        src_id, extra, size = _PTAU_LEVELS[sid]
+        up, levels, single, down = g2 if size == G2_BYTES else g1
+        top, batch = ptau.power + extra, min(ptau.power + extra, batch_log2)
+        points = source[src_id]
+        if extra and batch < top:            # the single-level call of level power + 1 takes 2^(power+1) points: the last is the format's infinity
+            points = np.concatenate([points, np.zeros(size, dtype=np.uint8)])
+
+        def run(fn, at, count, *args):
+            dst = fn(src, *args)
+            ms["device_ms"] += capi.last_timing()["total_ms"]
+            ms["library_bytes_max"] = max(ms["library_bytes_max"], capi.memory_query()["library_bytes"])
+            t3 = time.perf_counter()
+            down(dst, out[pos + at * size:pos + (at + count) * size])
+            dst.free()
+            ms["download_ms"] += (time.perf_counter() - t3) * 1e3
+            ms["calls"] += 1
+
+        t1 = time.perf_counter()
+        src = up(points)
+        ms["upload_ms"] += (time.perf_counter() - t1) * 1e3
+        run(levels, 0, (2 << batch) - 1, 0, batch)
+        for p in range(batch + 1, top + 1):
+            run(single, (1 << p) - 1, 1 << p, p)
+        src.free()
+        pos += length
+    t1 = time.perf_counter()
+    out.flush()
+    del out
+    ms["write_ms"] += (time.perf_counter() - t1) * 1e3
+    if timing is not None:
+        timing.update(ms, wall_ms=(time.perf_counter() - t0) * 1e3, power=ptau.power)
+
+
 def _coef_values(vals):
     """[n, 4] uint64 standard-form values -> [n, 32] uint8 of v * 2^512 mod r: one big-integer product per DISTINCT value (the values
     below 2^64 and the wider ones are told apart first: the first are sorted as machine words)."""
@@ -824,17 +947,22 @@ def _setup_system(r1cs, k):
     return DeviceDomainR1CS(k, (rp_a, col_a, val_a), pad(r1cs.b), pad(r1cs.c), r1cs.nVars)
 
 
-def SetupFromPtau(r1cs_path, ptau_path, zkey_path, timing=None):
+def SetupFromPtau(r1cs_path, ptau_path, zkey_path, timing=None, prepared=False):
     """What `snarkjs groth16 setup` does, on the device: circuit.r1cs + a powers-of-tau file -> circuit.zkey with delta = 1 (apply
     ContributeDelta before using the key: with delta = 1 proofs can be forged).  The Lagrange bases of the domain are inverse transforms of
     the transcript's sections in the group (gs_g1_lagrange / gs_g2_lagrange; the prepared sections 12 - 15 of a transcript are not read),
     A, B1, B2, C and IC column sums of the circuit's matrices over them (gs_r1cs_colsum_g1 / _g2), H the odd half of the transform of
     twice the size.  The arrays leave the device straight into the memory-mapped output file.
+    prepared=True reads the bases from the transcript's prepared sections instead (ReadPtauPrepared; PreparePtau writes them): L, L2, La,
+    Lb are level k of sections 12, 13, 14, 15 and H the odd entries of level k + 1 of section 12, no transform runs and
+    timing["transforms_ms"] stays 0; a file without usable prepared sections is a ValueError before the device is touched.  The prepared
+    sections are TRUSTED INPUT: nothing here checks that they are the Lagrange form of sections 2 - 5 -- run VerifyPtauPrepared on the
+    transcript before the setup, or VerifyZkey on the key after it.
     -> (groth16.DevicePk, DeviceZkeyR1CS, groth16.Vk) of the key just written, built from the resident arrays.
     `timing`: a dict that receives the device milliseconds of the phases (transforms, column sums), the wall milliseconds of the
     downloads and file writing, and the largest gs_memory_query library_bytes seen between two device calls."""
     import time
-    r1cs, ptau = ReadR1cs(r1cs_path), ReadPtau(ptau_path)
+    r1cs, ptau = ReadR1cs(r1cs_path), (ReadPtauPrepared if prepared else ReadPtau)(ptau_path)
     k = _setup_domain_bits(r1cs)
     m, nvars, npub = 1 << k, r1cs.nVars, r1cs.nPublic + 1
     if ptau.power < k:
@@ -852,13 +980,19 @@ def SetupFromPtau(r1cs_path, ptau_path, zkey_path, timing=None):
         return out
 
     system = _setup_system(r1cs, k)
-    tau1 = capi.g1_upload_affine_mont(ptau.tauG1[:min(2 * m, (2 << ptau.power) - 1) * G1_BYTES])
-    L = timed("transforms_ms", capi.g1_lagrange, tau1, k)
-    H = timed("transforms_ms", capi.g1_lagrange, tau1, k, odd_half=True)
-    tau1 = None
-    L2 = timed("transforms_ms", capi.g2_lagrange, capi.g2_upload_affine_mont(ptau.tauG2[:m * G2_BYTES]), k)
-    La = timed("transforms_ms", capi.g1_lagrange, capi.g1_upload_affine_mont(ptau.alphaTauG1[:m * G1_BYTES]), k)
-    Lb = timed("transforms_ms", capi.g1_lagrange, capi.g1_upload_affine_mont(ptau.betaTauG1[:m * G1_BYTES]), k)
+    if prepared:
+        L = capi.g1_upload_affine_mont(ptau.level(12, k))
+        H = capi.g1_upload_affine_mont(np.ascontiguousarray(np.asarray(ptau.level(12, k + 1)).reshape(-1, G1_BYTES)[1::2]).reshape(-1))
+        L2 = capi.g2_upload_affine_mont(ptau.level(13, k))
+        La, Lb = capi.g1_upload_affine_mont(ptau.level(14, k)), capi.g1_upload_affine_mont(ptau.level(15, k))
+    else:
+        tau1 = capi.g1_upload_affine_mont(ptau.tauG1[:min(2 * m, (2 << ptau.power) - 1) * G1_BYTES])
+        L = timed("transforms_ms", capi.g1_lagrange, tau1, k)
+        H = timed("transforms_ms", capi.g1_lagrange, tau1, k, odd_half=True)
+        tau1 = None
+        L2 = timed("transforms_ms", capi.g2_lagrange, capi.g2_upload_affine_mont(ptau.tauG2[:m * G2_BYTES]), k)
+        La = timed("transforms_ms", capi.g1_lagrange, capi.g1_upload_affine_mont(ptau.alphaTauG1[:m * G1_BYTES]), k)
+        Lb = timed("transforms_ms", capi.g1_lagrange, capi.g1_upload_affine_mont(ptau.betaTauG1[:m * G1_BYTES]), k)
     A = timed("colsums_ms", capi.r1cs_colsum, system, L, None, None)
     B1 = timed("colsums_ms", capi.r1cs_colsum, system, None, L, None)
     B2 = timed("colsums_ms", capi.r1cs_colsum, system, None, L2, None, g2=True)
@@ -1031,4 +1165,44 @@ def VerifyPtau(ptau_path, power=None, seed=None, timing=None):
                              up1(ptau.alphaTauG1[:n * G1_BYTES]), up1(ptau.betaTauG1[:n * G1_BYTES]), _g2(G2FromZkey(ptau.betaG2)), power, s)
     if timing is not None:
         timing.update(capi.last_timing(), wall_ms=(time.perf_counter() - t0) * 1e3, power=power)
+    return PtauReport(checks, s)
+
+
+PTAU_PREPARED_CHECKS = ("tauG1 Lagrange", "tauG2 Lagrange", "alphaTauG1 Lagrange", "betaTauG1 Lagrange")
+
+
+def VerifyPtauPrepared(ptau_path, power=None, seed=None, timing=None):
+    """Are the prepared sections 12 - 15 of the transcript at `ptau_path` the Lagrange bases of its sections 2 - 5?  -> PtauReport of four
+    checks named after the sections (gs_g*_lagrange_levels_check: per section one random linear combination of all its levels against one
+    combination of the section's powers whose scalars come from scalar transforms; no transform runs in the group).  `power` (default: the
+    file's) limits the check to the levels 0 .. power, a prefix of each section -- 0 .. power + 1 for tauG1, whose level power + 1 is the
+    padded one (2^(power+1) - 1 points and an infinity) only at the file's own power.  At most power 24: one sum takes the 2^(power+2) - 1
+    points of tauG1's levels and a sum holds 2^26 - 1 terms.  A wrong section passes with probability at most 2^(power+2) / r (G2: for
+    differences in the order-r subgroup, see include/gosnark_hip.h).  What this does not prove: that sections 2 - 5 themselves are sound
+    -- see VerifyPtau.
+    `timing`: a dict that receives the device milliseconds of the four checks and the wall milliseconds of the whole call."""
+    import time
+    t0 = time.perf_counter()
+    ptau = ReadPtauPrepared(ptau_path)
+    power = ptau.power if power is None else int(power)
+    if not 0 <= power <= min(ptau.power, 24):
+        raise ValueError("%s: section %s: power = %d, so the levels 0 .. %d cannot be checked (0 <= power <= %d; 24 at most: tauG1's levels "
+                         "0 .. power + 1 are one sum of 2^(power+2) - 1 terms)" % (ptau_path, _PTAU_NAMES[1], ptau.power, power, min(ptau.power, 24)))
+    s = _challenge(seed)
+    capi.init()
+    source = {2: ptau.tauG1, 3: ptau.tauG2, 4: ptau.alphaTauG1, 5: ptau.betaTauG1}
+    checks, device_ms = [], 0.0
+    for sid, name in zip(_PTAU_PREPARED, PTAU_PREPARED_CHECKS):
+        src_id, extra, size = _PTAU_LEVELS[sid]
+        g2 = size == G2_BYTES
+        up = capi.g2_upload_affine_mont if g2 else capi.g1_upload_affine_mont
+        hi = power + extra
+        pw = up(source[src_id][:(1 << hi) * size])                     # tauG1 at the file's own power: 2^hi - 1 points, the padded level
+        lv = up(ptau.lagrange[sid][:((2 << hi) - 1) * size])
+        checks.append((capi.g2_lagrange_levels_check if g2 else capi.g1_lagrange_levels_check)(pw, lv, hi, s, name))
+        device_ms += capi.last_timing()["total_ms"]
+        pw.free()
+        lv.free()
+    if timing is not None:
+        timing.update(device_ms=device_ms, wall_ms=(time.perf_counter() - t0) * 1e3, power=power)
     return PtauReport(checks, s)

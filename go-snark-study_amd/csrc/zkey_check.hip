@@ -6,6 +6,7 @@
 // the twist c_t = (1/2) v^(-t) q_t of the H check, the vector compare; the weight is in kernels the library already had.
 //   gs_groth16_key_check   coefs A, coefs B, A, B1, B2, IC, C, H against circuit and transcript
 //   gs_ptau_check          the transcript's first 2^log2_n powers: one tau in both groups, geometric alpha / beta sections, betaG2
+//   gs_g1 / g2_lagrange_levels_check   a prepared section (the Lagrange bases of every power-of-two domain) against its powers
 // Every MSM is summed table-free whatever the table policy (each array is used once); the pairing comparisons run here, on the host
 // (pairing.h), so a C or Go caller gets the whole answer from one call.
 #include <algorithm>
@@ -411,9 +412,88 @@ int ptau_check_impl(Ctx& c, gs_handle h1, gs_handle h2, gs_handle ha, gs_handle 
   return GS_OK;
 }
 
+// ---- the prepared sections of a transcript ------------------------------------------------------------------------------------------
+// acc[i] += x[i] mod r, i < n (both standard form, any representative; the sum is < 2r)
+__global__ void __launch_bounds__(256) k_zc_accumulate(uint32_t* __restrict__ acc, const uint32_t* __restrict__ x, uint32_t n) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  zc_store(acc + (size_t)i * 8, canon(reduce2(add(zc_load(acc + (size_t)i * 8), zc_load(x + (size_t)i * 8)))));
+}
+
+constexpr int kLevelsCheckMaxLog2 = 25;      // 2^(hi+1) - 1 terms in one sum, and a sum takes at most 2^26 - 1 (kIndexMask)
+
+// levels[2^p - 1 + j] = (1/2^p) sum_i w_p^(-ij) powers[i] for every p <= hi, as ONE equation of two sums: the coefficient of powers[i] in
+// sum_p sum_j rho_(2^p-1+j) levels[2^p-1+j] is sum_p (1/2^p) sum_j rho_(2^p-1+j) w_p^(-ij) -- coefficient i of the interpolant of
+// rho's slice for level p on that level's domain (domain_coeffs_dev: its 1/m is the 2^(-p)).
+template <class T>
+int levels_check_impl(Ctx& c, const char* fn, gs_handle hpow, gs_handle hlev, size_t hi_, const uint64_t challenge[4], gs_check_result& res) {
+  constexpr Kind kind = T::kWords == 8 ? Kind::G1Bases : Kind::G2Bases;
+  Bases* P = c.get<Bases>(hpow, kind);
+  Bases* L = c.get<Bases>(hlev, kind);
+  if (!P || !L) return fail(GS_ERR_ARG, "%s: bad base-array handle (powers, levels: both of this call's group)", fn);
+  uint64_t s[4];
+  if (!challenge_words(challenge, s)) return fail(GS_ERR_ARG, "%s: the challenge is 0 mod r", fn);
+  if (hi_ > (size_t)kLevelsCheckMaxLog2)
+    return fail(GS_ERR_ARG, "%s: hi = %zu, must be 0 .. %d (a sum takes at most 2^26 - 1 terms, the levels 0 .. hi are 2^(hi+1) - 1)", fn, hi_, kLevelsCheckMaxLog2);
+  const int hi = (int)hi_;
+  const size_t top = (size_t)1 << hi, nlev = 2 * top - 1;
+  if (L->n < nlev) return fail(GS_ERR_SHAPE, "%s: levels holds %zu points, the levels 0 .. %d are %zu", fn, L->n, hi, nlev);
+  if (P->n < top - 1)
+    return fail(GS_ERR_SHAPE, "%s: powers holds %zu points, level %d needs %zu (or %zu and a last point at infinity)", fn, P->n, hi, top, top - 1);
+  const size_t npow = std::min(P->n, top);
+  c.drain();
+  reset_timing(c);
+  drop_table(P);
+  drop_table(L);
+  PhaseTimer total(c.stream);
+  // rho lives from slot 1 of its buffer, so that level p's slice starts at slot 2^p: every transform runs on an aligned copy
+  DevBuf rho(2 * top * 32), coef(top * 32);
+  {
+    PhaseTimer tp(c.stream);
+    DevBuf vals(2 * top * 32), tmp(top * 32);
+    GS_HIP(hipMemsetAsync(rho.p, 0, 32, c.stream));
+    scaled_powers_dev(c, s, s, nlev, rho.as<uint32_t>() + 8);                              // s^(i+1)
+    GS_HIP(hipMemcpyAsync(vals.p, rho.p, 2 * top * 32, hipMemcpyDeviceToDevice, c.stream));
+    GS_HIP(hipMemsetAsync(coef.p, 0, top * 32, c.stream));
+    for (int p = hi; p >= 0; --p) {                    // the largest first: the engine's twiddle table is made once
+      const size_t m = (size_t)1 << p;
+      domain_coeffs_dev(c, vals.as<uint32_t>() + m * 8, p, 1, tmp.as<uint32_t>());
+      hipLaunchKernelGGL(k_zc_accumulate, grid1(m), dim3(256), 0, c.stream, coef.as<uint32_t>(), tmp.as<uint32_t>(), (uint32_t)m);
+    }
+    GS_HIP(hipGetLastError());
+    tp.stop();
+    GS_HIP(hipStreamSynchronize(c.stream));            // the scratch buffers go here
+    c.timing.poly_ms += tp.ms();
+  }
+  Xyzz<T> lhs, rhs = xyzz_inf<T>();
+  const int g1 = T::kWords == 8 ? 1 : 0;
+  { SharedPlan p(c, rho.as<uint32_t>() + 8, nlev, g1, 1 - g1); lhs = p.sum<T>({{L, 0}})[0]; }
+  if (npow) { SharedPlan p(c, coef.as<uint32_t>(), npow, g1, 1 - g1); rhs = p.sum<T>({{P, 0}})[0]; }
+  total.stop();
+  GS_HIP(hipStreamSynchronize(c.stream));
+  c.timing.total_ms = total.ms();
+  res = gs_check_result{};
+  set_points(res, lhs, rhs);
+  res.ok = same_point(res);
+  return GS_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int gs_g1_lagrange_levels_check(gs_handle powers, gs_handle levels, size_t hi, const uint64_t challenge[4], gs_check_result* out) {
+  return guarded([&](Ctx& c) -> int {
+    if (!out || !challenge) return fail(GS_ERR_ARG, "gs_g1_lagrange_levels_check: null argument");
+    return levels_check_impl<FqTag>(c, "gs_g1_lagrange_levels_check", powers, levels, hi, challenge, *out);
+  }, true, false, powers);
+}
+int gs_g2_lagrange_levels_check(gs_handle powers, gs_handle levels, size_t hi, const uint64_t challenge[4], gs_check_result* out) {
+  return guarded([&](Ctx& c) -> int {
+    if (!out || !challenge) return fail(GS_ERR_ARG, "gs_g2_lagrange_levels_check: null argument");
+    return levels_check_impl<Fq2Tag>(c, "gs_g2_lagrange_levels_check", powers, levels, hi, challenge, *out);
+  }, true, false, powers);
+}
 
 int gs_groth16_key_check(const gs_key_check_input* in, gs_check_report* out) {
   return guarded([&](Ctx& c) -> int {

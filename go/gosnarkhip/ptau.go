@@ -75,3 +75,92 @@ func ContributePtauArrays(in PtauArrays, n1, n int, tau, alpha, beta []uint64) (
 	}
 	return &out, nil
 }
+
+// LagrangeLevelsG1 gives the Lagrange bases of the domains 2^lo .. 2^hi over the first points of a resident section
+// (gs_g1_lagrange_levels): 2^(hi+1) - 2^lo points, level p -- LagrangeG1(powers, 0, p, false) of the first 2^p points -- at index
+// 2^p - 2^lo.  One launch carries the stage of one span for every level.  An array of exactly 2^hi - 1 points: the missing last point
+// of level hi is the point at infinity (tauG1's level power + 1).
+func LagrangeLevelsG1(powers Handle, lo, hi int) (Handle, error) {
+	var h C.gs_handle
+	err := call(func() C.int { return C.gs_g1_lagrange_levels(C.gs_handle(powers), C.size_t(lo), C.size_t(hi), &h) })
+	return Handle(h), err
+}
+
+// LagrangeLevelsG2 is LagrangeLevelsG1 for G2 points (gs_g2_lagrange_levels).
+func LagrangeLevelsG2(powers Handle, lo, hi int) (Handle, error) {
+	var h C.gs_handle
+	err := call(func() C.int { return C.gs_g2_lagrange_levels(C.gs_handle(powers), C.size_t(lo), C.size_t(hi), &h) })
+	return Handle(h), err
+}
+
+func resultFromC(c *C.gs_check_result) *CheckResult {
+	r := &CheckResult{OK: c.ok != 0, LhsG2: c.lhs_g2 != 0, RhsG2: c.rhs_g2 != 0, LhsInf: c.lhs_inf != 0, RhsInf: c.rhs_inf != 0}
+	for j := 0; j < 16; j++ {
+		r.Lhs[j], r.Rhs[j] = uint64(c.lhs[j]), uint64(c.rhs[j])
+	}
+	return r
+}
+
+// CheckLagrangeLevelsG1 asks whether the first 2^(hi+1) - 1 points of levels are the levels 0 .. hi of powers
+// (gs_g1_lagrange_levels_check): one sum over each array and scalar transforms, nothing is transformed in the group.  The challenge is
+// four limbs, not 0 mod r, drawn after both arrays are fixed.  hi <= 25.
+func CheckLagrangeLevelsG1(powers, levels Handle, hi int, challenge []uint64) (*CheckResult, error) {
+	if len(challenge) != 4 {
+		return nil, errors.New("gosnark-hip: the challenge is four limbs")
+	}
+	var res C.gs_check_result
+	err := call(func() C.int {
+		return C.gs_g1_lagrange_levels_check(C.gs_handle(powers), C.gs_handle(levels), C.size_t(hi), ptr(challenge), &res)
+	})
+	runtime.KeepAlive(challenge)
+	if err != nil {
+		return nil, err
+	}
+	return resultFromC(&res), nil
+}
+
+// CheckLagrangeLevelsG2 is CheckLagrangeLevelsG1 for G2 points (gs_g2_lagrange_levels_check); include/gosnark_hip.h says what the
+// bound means in G2.
+func CheckLagrangeLevelsG2(powers, levels Handle, hi int, challenge []uint64) (*CheckResult, error) {
+	if len(challenge) != 4 {
+		return nil, errors.New("gosnark-hip: the challenge is four limbs")
+	}
+	var res C.gs_check_result
+	err := call(func() C.int {
+		return C.gs_g2_lagrange_levels_check(C.gs_handle(powers), C.gs_handle(levels), C.size_t(hi), ptr(challenge), &res)
+	})
+	runtime.KeepAlive(challenge)
+	if err != nil {
+		return nil, err
+	}
+	return resultFromC(&res), nil
+}
+
+// PreparePtauArrays gives the prepared sections 12 .. 15 of a transcript of 2^power from its resident sections: the levels
+// 0 .. power + 1 of tauG1 (2^(power+1) - 1 points in, the padded top level) and 0 .. power of tauG2, alphaTauG1, betaTauG1; the inputs
+// stay as they are.  4 x gs_g*_lagrange_levels.  Call sequence = tests/c/ptau_prepare.c.  power <= 26.
+func PreparePtauArrays(in PtauArrays, power int) (*PtauArrays, error) {
+	var out PtauArrays
+	var err error
+	fail := func(e error) (*PtauArrays, error) {
+		for _, h := range []Handle{out.TauG1, out.TauG2, out.AlphaTauG1, out.BetaTauG1} {
+			if h != 0 {
+				_ = Free(h)
+			}
+		}
+		return nil, e
+	}
+	if out.TauG1, err = LagrangeLevelsG1(in.TauG1, 0, power+1); err != nil {
+		return fail(err)
+	}
+	if out.TauG2, err = LagrangeLevelsG2(in.TauG2, 0, power); err != nil {
+		return fail(err)
+	}
+	if out.AlphaTauG1, err = LagrangeLevelsG1(in.AlphaTauG1, 0, power); err != nil {
+		return fail(err)
+	}
+	if out.BetaTauG1, err = LagrangeLevelsG1(in.BetaTauG1, 0, power); err != nil {
+		return fail(err)
+	}
+	return &out, nil
+}

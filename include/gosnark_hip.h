@@ -386,6 +386,41 @@ int gs_ptau_check(gs_handle tau_g1, gs_handle tau_g2, gs_handle alpha_tau_g1, gs
                   const uint64_t challenge[4], gs_check_report* out);
 int gs_check_abi_sizes(size_t* input_bytes, size_t* report_bytes);
 
+/* ---- preparing a transcript for phase 2: the Lagrange bases of every power-of-two domain ----------------------------------------- */
+/* `snarkjs powersoftau prepare phase2` appends to a transcript, per array section, the Lagrange basis of EVERY domain 2^0 .. 2^top: a
+ * setup then reads the level of its domain and runs no transform.  Level p of a section P is gs_g*_lagrange(P, 0, p, 0) of its first 2^p
+ * points: level[p][j] = (1/2^p) sum_{i<2^p} w_p^(-ij) P[i], w_p = 5^((r-1)/2^p), natural order.
+ *
+ * gs_g1_lagrange_levels / gs_g2_lagrange_levels: out = a new base array of 2^(hi+1) - 2^lo affine points, level p (lo <= p <= hi) at
+ * index 2^p - 2^lo.  The levels share one workspace and the decimation-in-time stage of span h has the same twiddles at every level, so
+ * ONE launch carries that stage for all levels with 2^p >= 2h: hi stage launches instead of sum (p + 1) -- below about 2^17 butterflies a
+ * stage does not fill the chip and costs one scalar multiplication's latency however small it is.  The array holds at least 2^hi points,
+ * or exactly 2^hi - 1: then the missing last point of level hi is the point at infinity (tauG1 has 2^(power+1) - 1 points and its top
+ * level is power + 1); fewer is GS_ERR_SHAPE.  lo > hi, hi > 27, a bad handle or a null `out` is GS_ERR_ARG.  All arithmetic is exact
+ * and every addition the complete one.  Blocking; gs_last_timing().total_ms = device time.
+ *
+ * gs_g1_lagrange_levels_check / gs_g2_lagrange_levels_check: are the first 2^(hi+1) - 1 points of `levels` the levels 0 .. hi of
+ * `powers` (at least 2^hi points, or 2^hi - 1 with the rule above)?  No transform runs in the group: with rho_i = s^(i+1) over the
+ * section index i,
+ *     lhs = MSM(levels, rho)          rhs = MSM(powers, c),   c_i = sum_p [i < 2^p] (coefficient i of the interpolant of rho's slice for
+ *                                                                   level p on the domain of w_p: the 2^(-p) is the interpolation's own)
+ * and the check is lhs = rhs as points (gs_ptau_check's machinery: only scalars go through a transform, both sums are table-free and
+ * the handles own no window table afterwards).  *out is ONE gs_check_result.  s = 0 mod r or a bad handle is GS_ERR_ARG, arrays too
+ * short GS_ERR_SHAPE; hi <= 25, since a sum takes at most 2^26 - 1 terms and the levels 0 .. hi are 2^(hi+1) - 1 (GS_ERR_ARG above).
+ * SOUNDNESS: lhs - rhs = sum_i s^(i+1) D_i for the differences D_i = levels[i] - (what level i should be), a polynomial in s of degree at
+ * most 2^(hi+1) with point coefficients.  In G1 every point has order r, so a wrong section passes for at most 2^(hi+1) values of s out
+ * of r ~ 2^254.  In G2 that bound holds for differences INSIDE the order-r subgroup only: the twist's cofactor is not prime, and a
+ * difference of small order t escapes whenever the combination of the powers of s it meets vanishes mod t -- for a single wrong point of
+ * order t, whenever t divides s^(i+1), i.e. with probability about 1 / (the product of t's prime factors): no 2^-230 event.  The levels of a checked transcript are sums
+ * of subgroup points and lie in the subgroup, so whoever needs this for a section of unknown origin tests subgroup membership of its
+ * points first (gs_ptau_check leaves the same case implicit for tauG2).
+ * go-snark-study_amd/circom.py (PreparePtau, VerifyPtauPrepared, SetupFromPtau(prepared=True)) drives them over a .ptau file; go/gosnarkhip/ptau.go
+ * and tests/c/ptau_prepare.c are the same sequence. */
+int gs_g1_lagrange_levels(gs_handle powers, size_t lo, size_t hi, gs_handle* out);
+int gs_g2_lagrange_levels(gs_handle powers, size_t lo, size_t hi, gs_handle* out);
+int gs_g1_lagrange_levels_check(gs_handle powers, gs_handle levels, size_t hi, const uint64_t challenge[4], gs_check_result* out);
+int gs_g2_lagrange_levels_check(gs_handle powers, gs_handle levels, size_t hi, const uint64_t challenge[4], gs_check_result* out);
+
 /* ---- Groth16 prover (groth16/groth16.go) --------------------------------------------------- */
 /* Device-resident proving key: groth16.Pk (groth16.go:15-32).  At, BACGamma (G1), BACDelta:
  * m points; G2 BACGamma: m points; PowersTauDelta: len(Z) points; single points as Jacobian
