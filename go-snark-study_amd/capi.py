@@ -121,6 +121,7 @@ _SIGS = {
     "gs_g2_lagrange_levels": [Handle, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(Handle)],
     "gs_g1_lagrange_levels_check": [Handle, Handle, ctypes.c_size_t, u64p, ctypes.POINTER(CheckResult)],
     "gs_g2_lagrange_levels_check": [Handle, Handle, ctypes.c_size_t, u64p, ctypes.POINTER(CheckResult)],
+    "gs_g2_subgroup_check": [Handle, ctypes.c_size_t, ctypes.c_size_t, u64p, u64p],
     "gs_groth16_pk_create": [Handle, Handle, Handle, Handle, Handle, u64p, u64p, u64p, u64p, u64p,
                              u64p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(Handle)],
     "gs_groth16_prove": [Handle, u64p, ctypes.c_size_t, u64p, ctypes.c_size_t, u64p, u64p, u64p, intp],
@@ -674,6 +675,17 @@ def g1_lagrange_levels_check(powers, levels, hi, challenge, name="levels"):
 
 def g2_lagrange_levels_check(powers, levels, hi, challenge, name="levels"):
     return _lagrange_levels_check("gs_g2_lagrange_levels_check", name, powers, levels, hi, challenge)
+
+
+def g2_subgroup_check(bases, off=0, n=None):
+    """gs_g2_subgroup_check: which of the points off .. off + n - 1 of a resident G2 array (default: all from off on) lie outside the
+    order-r subgroup?  -> (how many, the smallest index of one counted from the start of the array, or None when there is none).  The
+    uploads test the curve equation only; exact and per point, the point at infinity is a member."""
+    off = int(off)
+    n = max(len(bases) - off, 0) if n is None else int(n)
+    nbad, first = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    call("gs_g2_subgroup_check", raw(bases), off, n, ctypes.byref(nbad), ctypes.byref(first))
+    return int(nbad.value), (None if first.value == (1 << 64) - 1 else int(first.value))
 
 
 def scalars_upload(s_u64):

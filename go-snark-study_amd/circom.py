@@ -1074,7 +1074,9 @@ def ContributeDelta(zkey_in, zkey_out, delta):
 class CheckReport:
     """The outcome of VerifyZkey / VerifyPtau: truthy only when every check passed.  `checks`: [(name, ok, lhs, rhs)] in the order they
     were made, the two points of a check as affine int tuples (None = infinity; None, None for the host-side checks; the coefs checks
-    carry the number of differing rows as lhs); `failed`: the names of the checks that did not pass; `points[name]` = (lhs, rhs)."""
+    carry the number of differing rows as lhs, and the membership checks of membership=True the number of points outside the order-r
+    subgroup as lhs and the smallest index of one (None: there is none) as rhs); `failed`: the names of the checks that did not pass;
+    `points[name]` = (lhs, rhs)."""
 
     def __init__(self, checks, seed):
         self.checks, self.seed = list(checks), seed
@@ -1096,6 +1098,12 @@ class PtauReport(CheckReport):
     pass
 
 
+def _membership_check(name, points, off=0, n=None):
+    """(name, ok, nbad, first_bad) over a resident G2 array (gs_g2_subgroup_check), and the device milliseconds it took."""
+    nbad, first = capi.g2_subgroup_check(points, off, n)
+    return (name, nbad == 0, nbad, first), capi.last_timing()["total_ms"]
+
+
 def _challenge(seed):
     """A challenge in 1 .. r - 1: from `seed` (tests: reproducible) or from the operating system's randomness."""
     if seed is None:
@@ -1105,7 +1113,7 @@ def _challenge(seed):
     return random.Random(seed).randrange(1, R)
 
 
-def VerifyZkey(r1cs_path, ptau_path, zkey_path, seed=None, timing=None):
+def VerifyZkey(r1cs_path, ptau_path, zkey_path, seed=None, timing=None, membership=False):
     """Is the key at `zkey_path` the Groth16 key of the circuit at `r1cs_path` over the transcript at `ptau_path`, with C and H scaled by
     the delta of its header?  -> ZkeyReport.  Host side: the counts of the three files against each other (a mismatch is a ValueError that
     names file and section, raised before the device is touched), then the checks `header` (alfa1 / beta1 / beta2 against the transcript,
@@ -1114,7 +1122,13 @@ def VerifyZkey(r1cs_path, ptau_path, zkey_path, seed=None, timing=None):
     come from the circuit, for a challenge drawn after the files are opened (`seed`: a fixed one, for tests).  A wrong key passes with
     probability at most max(nVars, 2 domainSize) / r.  What this proves: the key's relation to THIS circuit and THIS transcript.  What it
     does not: who contributed to either (no contribution chain is read or checked), or that the transcript is sound -- see VerifyPtau.
-    `timing`: a dict that receives the device milliseconds of the check (gs_last_timing) and the wall milliseconds of the whole call."""
+    `timing`: a dict that receives the device milliseconds of the check (gs_last_timing) and the wall milliseconds of the whole call.
+    membership=True appends `tauG2 membership` (the domainSize transcript points used) and `B2 membership` (the key's nVars points): every
+    G2 point is tested for the order-r subgroup (gs_g2_subgroup_check, on the arrays already uploaded), (name, ok, points outside, smallest
+    index or None).  The uploads test the curve equation only and the twist's cofactor has the factor 10069, so the B2 check alone lets a
+    point off the subgroup by an element of that order through about once in 10069 challenges: files of unknown origin need
+    membership=True.  It is not the default because the default report is a fixed list that callers compare against, and files one wrote
+    oneself do not need it.  `timing` then also receives `membership_ms`."""
     import time
     t0 = time.perf_counter()
     r1cs, ptau, z = ReadR1cs(r1cs_path), ReadPtau(ptau_path), ReadZkey(zkey_path)
@@ -1137,19 +1151,31 @@ def VerifyZkey(r1cs_path, ptau_path, zkey_path, seed=None, timing=None):
     capi.init()
     up1, up2 = capi.g1_upload_affine_mont, capi.g2_upload_affine_mont
     tau1 = up1(ptau.tauG1[:min(2 * m, (2 << ptau.power) - 1) * G1_BYTES])
-    checks += capi.groth16_key_check(up1(z.A), up1(z.B1), up2(z.B2), up1(z.IC), up1(z.C), up1(z.H), DeviceZkeyR1CS(k, z.nVars, z.coefs),
-                                     _setup_system(r1cs, k), tau1, up2(ptau.tauG2[:m * G2_BYTES]), up1(ptau.alphaTauG1[:m * G1_BYTES]),
+    tau2, b2 = up2(ptau.tauG2[:m * G2_BYTES]), up2(z.B2)
+    checks += capi.groth16_key_check(up1(z.A), up1(z.B1), b2, up1(z.IC), up1(z.C), up1(z.H), DeviceZkeyR1CS(k, z.nVars, z.coefs),
+                                     _setup_system(r1cs, k), tau1, tau2, up1(ptau.alphaTauG1[:m * G1_BYTES]),
                                      up1(ptau.betaTauG1[:m * G1_BYTES]), _g2(z.delta2), k, z.nPublic, s)
+    device = capi.last_timing()
+    if membership:
+        (c1, ms1), (c2, ms2) = _membership_check("tauG2 membership", tau2), _membership_check("B2 membership", b2)
+        checks += [c1, c2]
+        device["membership_ms"] = ms1 + ms2
     if timing is not None:
-        timing.update(capi.last_timing(), wall_ms=(time.perf_counter() - t0) * 1e3, log2_domain=k, nVars=z.nVars)
+        timing.update(device, wall_ms=(time.perf_counter() - t0) * 1e3, log2_domain=k, nVars=z.nVars)
     return ZkeyReport(checks, s)
 
 
-def VerifyPtau(ptau_path, power=None, seed=None, timing=None):
+def VerifyPtau(ptau_path, power=None, seed=None, timing=None, membership=False):
     """Is the transcript at `ptau_path` consistent with itself over its first 2^power powers (default: all it holds)?  -> PtauReport of
     gs_ptau_check's checks: tauG1[0] and tauG2[0] are the generators, both sections are the powers of ONE tau, alphaTauG1 and betaTauG1 are
     geometric with that ratio, betaG2 carries betaTauG1[0]'s scalar.  What this does not prove: who contributed -- the contribution chain of
-    a ceremony (challenge hashes, proofs of knowledge) is out of scope."""
+    a ceremony (challenge hashes, proofs of knowledge) is out of scope.
+    membership=True appends `tauG2 membership`: each of the 2^power tauG2 points checked is tested for the order-r subgroup
+    (gs_g2_subgroup_check, on the array already uploaded), (name, ok, points outside, smallest index or None).  The uploads test the curve
+    equation only and the twist's cofactor has the factor 10069, so the tauG2 check alone lets tau^j G2 + S with S of that order through
+    about once in 10069 challenges: a file of unknown origin needs membership=True.  It is not the default because the default report is
+    a fixed list that callers compare against, and a transcript one wrote oneself does not need it.  `timing` then also receives
+    `membership_ms`, the device milliseconds of that test."""
     import time
     t0 = time.perf_counter()
     ptau = ReadPtau(ptau_path)
@@ -1161,17 +1187,22 @@ def VerifyPtau(ptau_path, power=None, seed=None, timing=None):
     n = 1 << power
     capi.init()
     up1 = capi.g1_upload_affine_mont
-    checks = capi.ptau_check(up1(ptau.tauG1[:(2 * n - 1) * G1_BYTES]), capi.g2_upload_affine_mont(ptau.tauG2[:n * G2_BYTES]),
+    tau2 = capi.g2_upload_affine_mont(ptau.tauG2[:n * G2_BYTES])
+    checks = capi.ptau_check(up1(ptau.tauG1[:(2 * n - 1) * G1_BYTES]), tau2,
                              up1(ptau.alphaTauG1[:n * G1_BYTES]), up1(ptau.betaTauG1[:n * G1_BYTES]), _g2(G2FromZkey(ptau.betaG2)), power, s)
+    device = capi.last_timing()
+    if membership:
+        check, device["membership_ms"] = _membership_check("tauG2 membership", tau2)
+        checks.append(check)
     if timing is not None:
-        timing.update(capi.last_timing(), wall_ms=(time.perf_counter() - t0) * 1e3, power=power)
+        timing.update(device, wall_ms=(time.perf_counter() - t0) * 1e3, power=power)
     return PtauReport(checks, s)
 
 
 PTAU_PREPARED_CHECKS = ("tauG1 Lagrange", "tauG2 Lagrange", "alphaTauG1 Lagrange", "betaTauG1 Lagrange")
 
 
-def VerifyPtauPrepared(ptau_path, power=None, seed=None, timing=None):
+def VerifyPtauPrepared(ptau_path, power=None, seed=None, timing=None, membership=False):
     """Are the prepared sections 12 - 15 of the transcript at `ptau_path` the Lagrange bases of its sections 2 - 5?  -> PtauReport of four
     checks named after the sections (gs_g*_lagrange_levels_check: per section one random linear combination of all its levels against one
     combination of the section's powers whose scalars come from scalar transforms; no transform runs in the group).  `power` (default: the
@@ -1180,7 +1211,11 @@ def VerifyPtauPrepared(ptau_path, power=None, seed=None, timing=None):
     points of tauG1's levels and a sum holds 2^26 - 1 terms.  A wrong section passes with probability at most 2^(power+2) / r (G2: for
     differences in the order-r subgroup, see include/gosnark_hip.h).  What this does not prove: that sections 2 - 5 themselves are sound
     -- see VerifyPtau.
-    `timing`: a dict that receives the device milliseconds of the four checks and the wall milliseconds of the whole call."""
+    `timing`: a dict that receives the device milliseconds of the four checks and the wall milliseconds of the whole call.
+    membership=True appends `tauG2 Lagrange membership`: each of the 2^(power+1) - 1 level points of section 13 checked is tested for the
+    order-r subgroup (gs_g2_subgroup_check, on the array already uploaded), (name, ok, points outside, smallest index or None) -- what
+    closes the G2 caveat above, and what a file of unknown origin needs.  It is not the default because the default report is a fixed list
+    that callers compare against, and a file one prepared oneself does not need it.  `timing` then also receives `membership_ms`."""
     import time
     t0 = time.perf_counter()
     ptau = ReadPtauPrepared(ptau_path)
@@ -1191,7 +1226,7 @@ def VerifyPtauPrepared(ptau_path, power=None, seed=None, timing=None):
     s = _challenge(seed)
     capi.init()
     source = {2: ptau.tauG1, 3: ptau.tauG2, 4: ptau.alphaTauG1, 5: ptau.betaTauG1}
-    checks, device_ms = [], 0.0
+    checks, device_ms, member = [], 0.0, None
     for sid, name in zip(_PTAU_PREPARED, PTAU_PREPARED_CHECKS):
         src_id, extra, size = _PTAU_LEVELS[sid]
         g2 = size == G2_BYTES
@@ -1201,8 +1236,14 @@ def VerifyPtauPrepared(ptau_path, power=None, seed=None, timing=None):
         lv = up(ptau.lagrange[sid][:((2 << hi) - 1) * size])
         checks.append((capi.g2_lagrange_levels_check if g2 else capi.g1_lagrange_levels_check)(pw, lv, hi, s, name))
         device_ms += capi.last_timing()["total_ms"]
+        if membership and g2:
+            member = _membership_check(name + " membership", lv)
         pw.free()
         lv.free()
+    if member is not None:
+        checks.append(member[0])
     if timing is not None:
         timing.update(device_ms=device_ms, wall_ms=(time.perf_counter() - t0) * 1e3, power=power)
+        if member is not None:
+            timing["membership_ms"] = member[1]
     return PtauReport(checks, s)

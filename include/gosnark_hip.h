@@ -411,15 +411,37 @@ int gs_check_abi_sizes(size_t* input_bytes, size_t* report_bytes);
  * most 2^(hi+1) with point coefficients.  In G1 every point has order r, so a wrong section passes for at most 2^(hi+1) values of s out
  * of r ~ 2^254.  In G2 that bound holds for differences INSIDE the order-r subgroup only: the twist's cofactor is not prime, and a
  * difference of small order t escapes whenever the combination of the powers of s it meets vanishes mod t -- for a single wrong point of
- * order t, whenever t divides s^(i+1), i.e. with probability about 1 / (the product of t's prime factors): no 2^-230 event.  The levels of a checked transcript are sums
- * of subgroup points and lie in the subgroup, so whoever needs this for a section of unknown origin tests subgroup membership of its
- * points first (gs_ptau_check leaves the same case implicit for tauG2).
+ * order t, whenever t divides s^(i+1), i.e. with probability about 1 / (the product of t's prime factors): no 2^-230 event -- see
+ * gs_g2_subgroup_check below, which closes that case.  The levels of a checked transcript are sums
+ * of subgroup points and lie in the subgroup, so whoever needs this for a section of unknown origin runs gs_g2_subgroup_check over its
+ * points first (gs_ptau_check has the same case for tauG2 and the key check for B2; circom.py: membership=True does it for all three).
  * go-snark-study_amd/circom.py (PreparePtau, VerifyPtauPrepared, SetupFromPtau(prepared=True)) drives them over a .ptau file; go/gosnarkhip/ptau.go
  * and tests/c/ptau_prepare.c are the same sequence. */
 int gs_g1_lagrange_levels(gs_handle powers, size_t lo, size_t hi, gs_handle* out);
 int gs_g2_lagrange_levels(gs_handle powers, size_t lo, size_t hi, gs_handle* out);
 int gs_g1_lagrange_levels_check(gs_handle powers, gs_handle levels, size_t hi, const uint64_t challenge[4], gs_check_result* out);
 int gs_g2_lagrange_levels_check(gs_handle powers, gs_handle levels, size_t hi, const uint64_t challenge[4], gs_check_result* out);
+
+/* ---- G2 subgroup membership of whole arrays -------------------------------------------------------------------------------------- */
+/* The twist E'(Fq2) has r (2q - r) points and the cofactor 2q - r = 10069 x (a 246-bit number with no factor below 3 x 10^6): a point that
+ * satisfies the curve equation -- all that the uploads test -- need not have order r.  The random linear combinations of gs_ptau_check,
+ * gs_g2_lagrange_levels_check and gs_groth16_key_check bound a wrong point's chance by 2^-230 only INSIDE the subgroup; a point
+ * tau^j G2 + S with S of order 10069 passes them about once in 10069 challenges.  No linear combination can do better: the map
+ * phi = psi - [6 x^2] that vanishes exactly on the subgroup sends S into a group whose order has the factor 10069, so a combination of
+ * images still vanishes once in about 10069 challenges.  The test has to be per point, and exact.
+ *
+ * gs_g2_subgroup_check: tests the points off .. off + n - 1 of a G2 base array (from gs_g2_upload, gs_g2_upload_affine_mont or any
+ * entry that returns one).  *nbad = how many lie outside the order-r subgroup; *first_bad = the smallest index of one, counted from
+ * the start of the ARRAY (not from off), UINT64_MAX when there is none.  The point at infinity is a member.  n = 0 is legal (0 and
+ * UINT64_MAX); off + n beyond the array is GS_ERR_SHAPE; a bad handle, a handle of another kind or a null out-pointer GS_ERR_ARG.
+ * One thread per point evaluates [x + 1] Q + psi([x] Q) + psi^2([x] Q) = psi^3([2x] Q) for the BN parameter x and the
+ * untwist-Frobenius-twist endomorphism psi: 62 doublings and 23 mixed additions along the fixed non-adjacent form of x (no lane of a
+ * wave diverges), three general additions, no inversion -- about a quarter of the field products of gs_g2_scale_powers over the same
+ * points.  Every addition is the complete one.  The call reads the affine array only: it builds no window table and leaves no device
+ * memory behind.  Blocking; gs_last_timing().total_ms = device time.  G1 needs no such call: its cofactor is 1.
+ * go-snark-study_amd/circom.py (VerifyPtau, VerifyPtauPrepared, VerifyZkey with membership=True) runs it on the arrays the other checks
+ * upload; go/gosnarkhip/g2_membership.go and tests/c/g2_membership.c are the plain call. */
+int gs_g2_subgroup_check(gs_handle points, size_t off, size_t n, uint64_t* nbad, uint64_t* first_bad);
 
 /* ---- Groth16 prover (groth16/groth16.go) --------------------------------------------------- */
 /* Device-resident proving key: groth16.Pk (groth16.go:15-32).  At, BACGamma (G1), BACDelta:

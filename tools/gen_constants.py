@@ -121,6 +121,32 @@ def pairing_constants():
     return {"kP": w64(Q, 4), "kX": [x], "kLoop": w64(6 * x + 2, 2), "kPm1Div6": w64((Q - 1) // 6, 4)}
 
 
+def g2_psi_constants():
+    """g2 = xi^((q-1)/3) and g3 = xi^((q-1)/2), xi = 9 + u, as pairs (c0, c1) of Fq2 = Fq[u]/(u^2 + 1), and the non-adjacent form of
+    the BN parameter x, least significant digit first."""
+    def mul(a, b):
+        return ((a[0] * b[0] - a[1] * b[1]) % Q, (a[0] * b[1] + a[1] * b[0]) % Q)
+
+    def power(a, e):
+        r = (1, 0)
+        while e:
+            if e & 1:
+                r = mul(r, a)
+            a = mul(a, a)
+            e >>= 1
+        return r
+    g2, g3 = power((9, 1), (Q - 1) // 3), power((9, 1), (Q - 1) // 2)
+    assert power(g2, 3) == power((9, 1), Q - 1) and mul(g3, g3) == power((9, 1), Q - 1)
+    x, naf = 4965661367192848881, []
+    while x:
+        d = (2 - (x & 3)) if x & 1 else 0
+        naf.append(d)
+        x = (x - d) >> 1
+    assert sum(d << i for i, d in enumerate(naf)) == 4965661367192848881 and naf[-1] == 1 and len(naf) <= 64
+    assert all(naf[i] == 0 or naf[i + 1] == 0 for i in range(len(naf) - 1))
+    return (g2, g3), naf
+
+
 def main():
     out = "// GENERATED by tools/gen_constants.py -- do not edit.\n"
     out += "// BN128 constants (reference: bn128/bn128.go:40-83) in 9 x 29-bit limbs, Montgomery R = 2^261.\n"
@@ -148,6 +174,15 @@ def main():
     assert ((tb0 * 9 - tb1) % Q, (tb0 + 9 * tb1) % Q) == (3, 0)
     assert (g2y[0] ** 2 - g2y[1] ** 2) % Q == (g2x[0] ** 3 - 3 * g2x[0] * g2x[1] ** 2 + tb0) % Q     # the generator is on the twist
     out += arr("b1", limbs(3 * MONT_R % Q)) + arr("b2c0", limbs(tb0 * MONT_R % Q)) + arr("b2c1", limbs(tb1 * MONT_R % Q))
+    # the untwist-Frobenius-twist endomorphism psi(x, y) = (conj(x) g2, conj(y) g3) of E' (csrc/g2_subgroup.h)
+    (p2, p3), xnaf = g2_psi_constants()
+    out += arr("psi2c0", limbs(p2[0] * MONT_R % Q)) + arr("psi2c1", limbs(p2[1] * MONT_R % Q))
+    out += arr("psi3c0", limbs(p3[0] * MONT_R % Q)) + arr("psi3c1", limbs(p3[1] * MONT_R % Q))
+    # the BN parameter x in non-adjacent form, digit i = bit i of kXNafPos minus bit i of kXNafNeg (the leading digit is +1)
+    pos = sum(1 << i for i, d in enumerate(xnaf) if d > 0)
+    neg = sum(1 << i for i, d in enumerate(xnaf) if d < 0)
+    out += "  static constexpr int kXNafDigits = %d;\n" % len(xnaf)
+    out += "  static constexpr unsigned long long kXNafPos = 0x%016xULL, kXNafNeg = 0x%016xULL;\n" % (pos, neg)
     out += "};\n\n}  // namespace gs\n"
     path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
                         "go-snark-study_amd", "csrc", "bn128_constants.h")
