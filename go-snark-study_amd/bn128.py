@@ -76,6 +76,16 @@ def Pairing(p1, p2):
     return tuple(tuple((v[6 * i + 2 * j], v[6 * i + 2 * j + 1]) for j in range(3)) for i in range(2))
 
 
+def PairingProduct(g1_handle, g2_handle, poff=0, qoff=0, n=None):
+    """prod_i e(P[poff + i], Q[qoff + i]) over two resident arrays (gs_pairing_product, on the device; default: as many pairs as both
+    arrays hold from their offsets) -> (the value in Pairing's nesting, whether it is one).  The Q must be in G2."""
+    if n is None:
+        n = max(min(len(g1_handle) - poff, len(g2_handle) - qoff), 0)
+    out, one = capi.pairing_product(g1_handle, poff, g2_handle, qoff, n)
+    v = capi.u64_to_ints(out)
+    return tuple(tuple((v[6 * i + 2 * j], v[6 * i + 2 * j + 1]) for j in range(3)) for i in range(2)), one
+
+
 def PairingCheck(g1_points, g2_points):
     """prod_i e(g1_i, g2_i) == 1 with one shared final exponentiation (gs_pairing_check)."""
     if len(g1_points) != len(g2_points):

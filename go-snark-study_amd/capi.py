@@ -224,6 +224,8 @@ _SIGS = {
     "gs_pairing_check": [u64p, u64p, ctypes.c_size_t, intp],
     "gs_groth16_verify": [u64p, u64p, u64p, u64p, u64p, ctypes.c_size_t, u64p, ctypes.c_size_t, u64p, u64p, u64p, intp],
     "gs_pinocchio_verify": [u64p, u64p, u64p, u64p, u64p, u64p, u64p, u64p, ctypes.c_size_t, u64p, ctypes.c_size_t, u64p, intp, intp],
+    "gs_pairing_product": [Handle, ctypes.c_size_t, Handle, ctypes.c_size_t, ctypes.c_size_t, u64p, intp],
+    "gs_groth16_verify_batch": [u64p, u64p, u64p, u64p, u64p, ctypes.c_size_t, u64p, ctypes.c_size_t, u64p, u64p, u64p, ctypes.c_size_t, u64p, intp],
 }
 EXPORTS = sorted(list(_SIGS) + ["gs_shutdown", "gs_last_error", "gs_version", "gs_comm_destroy"])
 
@@ -686,6 +688,14 @@ def g2_subgroup_check(bases, off=0, n=None):
     nbad, first = ctypes.c_uint64(0), ctypes.c_uint64(0)
     call("gs_g2_subgroup_check", raw(bases), off, n, ctypes.byref(nbad), ctypes.byref(first))
     return int(nbad.value), (None if first.value == (1 << 64) - 1 else int(first.value))
+
+
+def pairing_product(g1, poff, g2, qoff, n):
+    """gs_pairing_product: prod_i e(P[poff + i], Q[qoff + i]) over a resident G1 and a resident G2 array -> (the value as the 48 words
+    of gs_pairing's encoding, whether it is one).  The Q must be in G2: g2_subgroup_check on the same handle is the caller's job."""
+    out, one = np.zeros(48, dtype=np.uint64), ctypes.c_int(0)
+    call("gs_pairing_product", raw(g1), int(poff), raw(g2), int(qoff), int(n), ptr64(out), ctypes.byref(one))
+    return out, bool(one.value)
 
 
 def scalars_upload(s_u64):

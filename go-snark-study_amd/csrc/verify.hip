@@ -191,3 +191,181 @@ int gs_pinocchio_verify(const uint64_t vka[24], const uint64_t vkb[12], const ui
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ batch verification
+// gs_groth16_verify_batch (include/gosnark_hip.h): many proofs of one key in one randomised product check.  The per-proof work --
+// scaling A by the weights, the weighted sum of the C, the subgroup test of the B and the n Miller loops with their product -- runs on
+// the device through the library's own entry points; the host forms the npublic + 1 scalars of the public-input sum, runs the three
+// key pairs through the multi-Miller loop above and finishes with ONE final exponentiation.
+
+namespace gs {
+int miller_product(const char* fn, gs_handle g1, size_t poff, gs_handle g2, size_t qoff, size_t n, pairing::Fp12* out);   // pairing_device.hip
+}
+
+namespace {
+
+// Fr as 4 x 64-bit Montgomery words: the weights z_i = s^i and the sums over them (a few products per proof)
+struct Fr { uint64_t v[4]; };
+struct FrConsts { uint64_t n0; Fr r2, one; };
+inline bool fr_geq_r(const uint64_t* a) { return limbs_geq(a, kRorder); }
+inline Fr fr_add(const Fr& a, const Fr& b) {
+  Fr r;
+  u128 c = 0;
+  for (int i = 0; i < 4; ++i) {
+    c += (u128)a.v[i] + b.v[i];
+    r.v[i] = (uint64_t)c;
+    c >>= 64;
+  }
+  if (c || fr_geq_r(r.v)) limbs_sub(r.v, kRorder);
+  return r;
+}
+const FrConsts& frc() {
+  static const FrConsts c = [] {
+    FrConsts k;
+    uint64_t inv = 1;
+    for (int i = 0; i < 6; ++i) inv *= 2 - kRorder[0] * inv;
+    k.n0 = 0 - inv;
+    Fr t = {{1, 0, 0, 0}};
+    for (int i = 0; i < 256; ++i) t = fr_add(t, t);
+    k.one = t;
+    for (int i = 0; i < 256; ++i) t = fr_add(t, t);
+    k.r2 = t;
+    return k;
+  }();
+  return c;
+}
+// a b 2^-256 mod r (CIOS; a may be any 256-bit value, b < r)
+Fr fr_mul(const Fr& a, const Fr& b) {
+  const uint64_t n0 = frc().n0;
+  uint64_t t[6] = {0, 0, 0, 0, 0, 0};
+  for (int i = 0; i < 4; ++i) {
+    u128 c = 0;
+    for (int j = 0; j < 4; ++j) {
+      c += (u128)a.v[j] * b.v[i] + t[j];
+      t[j] = (uint64_t)c;
+      c >>= 64;
+    }
+    c += t[4];
+    t[4] = (uint64_t)c;
+    t[5] = (uint64_t)(c >> 64);
+    const uint64_t m = t[0] * n0;
+    c = (u128)m * kRorder[0] + t[0];
+    c >>= 64;
+    for (int j = 1; j < 4; ++j) {
+      c += (u128)m * kRorder[j] + t[j];
+      t[j - 1] = (uint64_t)c;
+      c >>= 64;
+    }
+    c += t[4];
+    t[3] = (uint64_t)c;
+    t[4] = t[5] + (uint64_t)(c >> 64);
+  }
+  Fr r = {{t[0], t[1], t[2], t[3]}};
+  if (t[4] || fr_geq_r(r.v)) limbs_sub(r.v, kRorder);
+  return r;
+}
+Fr fr_from_std(const uint64_t w[4]) {                 // any 256-bit value -> Montgomery residue mod r
+  Fr a = {{w[0], w[1], w[2], w[3]}};
+  return fr_mul(a, frc().r2);
+}
+void fr_to_std(const Fr& a, uint64_t w[4]) {
+  const Fr one = {{1, 0, 0, 0}};
+  const Fr r = fr_mul(a, one);
+  memcpy(w, r.v, 32);
+}
+bool fr_eq(const Fr& a, const Fr& b) { return memcmp(a.v, b.v, 32) == 0; }
+
+// temporary handles of one call: freed on every path
+struct HandleBag {
+  gs_handle hs[4] = {0, 0, 0, 0};
+  ~HandleBag() { for (gs_handle h : hs) if (h) (void)gs_free(h); }
+};
+
+}  // namespace
+
+extern "C" {
+
+int gs_groth16_verify_batch(const uint64_t vk_g1_alpha[12], const uint64_t vk_g2_beta[24], const uint64_t vk_g2_gamma[24],
+                            const uint64_t vk_g2_delta[24], const uint64_t* vk_ic, size_t nic, const uint64_t* public_signals, size_t npublic,
+                            const uint64_t* pi_a, const uint64_t* pi_b, const uint64_t* pi_c, size_t nproofs, const uint64_t challenge[4], int* ok) {
+  return host_guarded([&]() -> int {
+    const char* fn = "gs_groth16_verify_batch";
+    const size_t n = nproofs;
+    if (!vk_g1_alpha || !vk_g2_beta || !vk_g2_gamma || !vk_g2_delta || !vk_ic || !challenge || !ok || (n && (!pi_a || !pi_b || !pi_c)) ||
+        (n && npublic && !public_signals))
+      return fail(GS_ERR_ARG, "%s: null argument", fn);
+    if (nic < npublic + 1) return fail(GS_ERR_SHAPE, "%s: %zu public signals need %zu IC points, vk has %zu", fn, npublic, npublic + 1, nic);
+    if (g_strict.load() && nic != npublic + 1)
+      return fail(GS_ERR_SHAPE, "%s (strict): vk has %zu IC points, so exactly %zu public signals are required (got %zu)", fn, nic, nic - 1, npublic);
+    const Fr s = fr_from_std(challenge);
+    if (fr_eq(s, Fr{{0, 0, 0, 0}}) || fr_eq(s, frc().one))
+      return fail(GS_ERR_ARG, "%s: the challenge is 0 or 1 mod r: every weight would be the same (draw it at random, after the proofs are fixed)", fn);
+    if (!n) {
+      *ok = 1;
+      return GS_OK;
+    }
+    const auto reject = [&]() -> int { *ok = 0; return GS_OK; };        // *ok is written by the paths that return GS_OK, and only then
+    if (g_strict.load() && (!scalars_canonical(public_signals, n * npublic) || !coords_canonical(pi_a, 3 * n) || !coords_canonical(pi_b, 6 * n) ||
+                            !coords_canonical(pi_c, 3 * n)))
+      return reject();
+    // the weights z_i = s^i in standard form, their sum, and sum_i z_i pub_ij per public input
+    std::vector<uint64_t> z(4 * n);
+    std::vector<Fr> wsum(npublic + 1, Fr{{0, 0, 0, 0}});
+    Fr zi = frc().one;
+    for (size_t i = 0; i < n; ++i) {
+      fr_to_std(zi, z.data() + 4 * i);
+      wsum[0] = fr_add(wsum[0], zi);
+      for (size_t j = 0; j < npublic; ++j) wsum[j + 1] = fr_add(wsum[j + 1], fr_mul(fr_from_std(public_signals + 4 * (i * npublic + j)), zi));
+      zi = fr_mul(zi, s);
+    }
+    // the proofs' points; a point off its curve is a rejected batch, as it is a rejected proof for the single verifier
+    HandleBag bag;
+    gs_handle *ha = &bag.hs[0], *hb = &bag.hs[1], *hc = &bag.hs[2], *hna = &bag.hs[3];
+    int rc = gs_g1_upload(pi_a, n, ha);
+    if (rc == GS_ERR_ARG) return reject();
+    if (rc != GS_OK) return rc;
+    rc = gs_g2_upload(pi_b, n, hb);
+    if (rc == GS_ERR_ARG) return reject();
+    if (rc != GS_OK) return rc;
+    rc = gs_g1_upload(pi_c, n, hc);
+    if (rc == GS_ERR_ARG) return reject();
+    if (rc != GS_OK) return rc;
+    uint64_t nbad = 0, first_bad = 0;
+    if ((rc = gs_g2_subgroup_check(*hb, 0, n, &nbad, &first_bad)) != GS_OK) return rc;
+    if (nbad) return reject();
+    // -z_i A_i on the device, sum_i z_i C_i as one MSM
+    uint64_t rm1[4], sw[4];
+    memcpy(rm1, kRorder, 32);
+    rm1[0] -= 1;
+    fr_to_std(s, sw);
+    if ((rc = gs_g1_scale_powers(*ha, 0, n, rm1, sw, hna)) != GS_OK) return rc;
+    uint64_t csum[8];
+    int cinf = 0;
+    if ((rc = gs_msm_g1(*hc, z.data(), 0, n, csum, &cinf)) != GS_OK) return rc;
+    // the key's three pairs on the host: (sum z) alpha | beta,  sum_j wsum_j IC[j] | gamma,  sum z_i C_i | delta
+    uint64_t k[4];
+    fr_to_std(wsum[0], k);
+    const G1Aff alpha = g1j_affine(g1j_mul(g1j_from(g1_from_jacobian_std(vk_g1_alpha)), k));
+    G1Jac vkx = g1j_mul(g1j_from(g1_from_jacobian_std(vk_ic)), k);
+    for (size_t j = 0; j < npublic; ++j) {
+      fr_to_std(wsum[j + 1], k);
+      vkx = g1j_add(vkx, g1j_mul(g1j_from(g1_from_jacobian_std(vk_ic + 12 * (j + 1))), k));
+    }
+    const G1Aff csum_pt = cinf ? G1Aff{Fp{{0, 0, 0, 0}}, Fp{{0, 0, 0, 0}}, true} : G1Aff{fp_from_std(csum), fp_from_std(csum + 4), false};
+    const std::vector<G1Aff> ps{alpha, g1j_affine(vkx), csum_pt};
+    const std::vector<G2Aff> qs{g2_from_jacobian_std(vk_g2_beta), g2_from_jacobian_std(vk_g2_gamma), g2_from_jacobian_std(vk_g2_delta)};
+    for (const G1Aff& p : ps)
+      if (!g1_on_curve(p)) return reject();
+    for (const G2Aff& q : qs)
+      if (!g2_on_curve(q)) return reject();
+    Fp12 fkey;
+    if (!multi_miller_loop(ps, qs, fkey)) return reject();
+    // the n Miller values of e(-z_i A_i, B_i) and their product on the device
+    Fp12 f;
+    if ((rc = gs::miller_product(fn, *hna, 0, *hb, 0, n, &f)) != GS_OK) return rc;
+    *ok = f12_eq(final_exponentiation(f12_mul(f, fkey)), f12_one()) ? 1 : 0;
+    return GS_OK;
+  });
+}
+
+}  // extern "C"

@@ -399,3 +399,34 @@ def VerifyProof(vk, proof, publicSignals, debug=False):
     if debug:
         print("✓ groth16 verification passed" if ok.value else "❌ groth16 verification not passed")
     return bool(ok.value)
+
+
+def VerifyProofs(vk, proofs, publicSignalsList, seed=None):
+    """Many proofs of ONE verification key in one randomised check on the device (gs_groth16_verify_batch) -> bool: the answer of
+    all(VerifyProof(vk, p, s) ...), wrong with probability at most (len(proofs) - 1) / r, and only towards True.  The challenge is
+    drawn from the operating system's randomness unless `seed` is given (tests: reproducible; a predictable challenge voids the
+    bound).  False does not say which proof is bad: VerifyProof on each locates it.  Needs an initialised device."""
+    if len(proofs) != len(publicSignalsList):
+        raise ValueError("VerifyProofs: %d proofs, %d lists of public signals" % (len(proofs), len(publicSignalsList)))
+    npublic = len(publicSignalsList[0]) if publicSignalsList else 0
+    if any(len(s) != npublic for s in publicSignalsList):
+        raise ValueError("VerifyProofs: every proof of one key has the same number of public signals")
+    ic, nic, _, _ = _scheme.verify_inputs(vk, [0] * npublic)
+    if seed is None:
+        import secrets
+        challenge = 2 + secrets.randbelow(capi.R - 2)
+    else:
+        import random
+        challenge = random.Random(seed).randrange(2, capi.R)
+    g1 = capi.g1_points_to_u64([vk.G1_Alpha])
+    g2 = capi.g2_points_to_u64([vk.G2_Beta, vk.G2_Gamma, vk.G2_Delta])
+    flat = [int(x) % capi.R for s in publicSignalsList for x in s]
+    pub = capi.ints_to_u64(flat) if flat else np.zeros((1, 4), dtype=np.uint64)
+    a = capi.g1_points_to_u64([p.PiA for p in proofs]) if proofs else np.zeros((1, 12), dtype=np.uint64)
+    b = capi.g2_points_to_u64([p.PiB for p in proofs]) if proofs else np.zeros((1, 24), dtype=np.uint64)
+    c = capi.g1_points_to_u64([p.PiC for p in proofs]) if proofs else np.zeros((1, 12), dtype=np.uint64)
+    ok = ctypes.c_int(0)
+    capi.call("gs_groth16_verify_batch", capi.ptr64(g1[0]), capi.ptr64(g2[0]), capi.ptr64(g2[1]), capi.ptr64(g2[2]), ic, nic,
+              capi.ptr64(pub), npublic, capi.ptr64(a), capi.ptr64(b), capi.ptr64(c), len(proofs), capi.ptr64(capi.ints_to_u64([challenge])),
+              ctypes.byref(ok))
+    return bool(ok.value)

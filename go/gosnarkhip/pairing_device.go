@@ -1,0 +1,109 @@
+package gosnarkhip
+
+/*
+#include "gosnark_hip.h"
+*/
+import "C"
+
+import (
+	"errors"
+	"math/big"
+	"runtime"
+)
+
+// Pairing products on the device, and Groth16 proofs verified in batches.  One proof check is O(1) work and stays on the host
+// (Groth16Verify); thousands of proofs under one key are a Miller loop per proof, which the device runs one lane per pair.
+// include/gosnark_hip.h has the formulas, the precondition on the G2 points and the soundness bound of the batch check.
+
+// PairingProduct is prod_i e(P[poff+i], Q[qoff+i]) over a resident G1 and a resident G2 array (gs_pairing_product): the value in
+// Pairing's encoding (12 x 4 words) and whether it is one.  n = 0 gives one; a pair with an infinite member contributes one.  The Q
+// must be in G2 (G2SubgroupCheck on the same handle: the uploads test the curve equation only).  Call sequence = tests/c/verify_batch.c.
+func PairingProduct(g1 Handle, poff int, g2 Handle, qoff, n int) (value [48]uint64, isOne bool, err error) {
+	var one C.int
+	err = call(func() C.int {
+		return C.gs_pairing_product(C.gs_handle(g1), C.size_t(poff), C.gs_handle(g2), C.size_t(qoff), C.size_t(n), ptr(value[:]), &one)
+	})
+	return value, one == 1, err
+}
+
+// Groth16BatchProof is one proof of a batch with its public signals.
+type Groth16BatchProof struct {
+	PiA           [3]*big.Int
+	PiB           [3][2]*big.Int
+	PiC           [3]*big.Int
+	PublicSignals []*big.Int
+}
+
+// Groth16VerifyBatch checks many proofs of ONE verification key in one randomised product check (gs_groth16_verify_batch): true iff
+// every proof verifies, wrong with probability at most (len(proofs) - 1) / r over a challenge drawn uniformly after the proofs are
+// fixed, and only towards true.  The challenge is the caller's randomness (crypto/rand); 0 and 1 mod r are refused.  false does not
+// say which proof is bad: Groth16Verify on each locates it.  Needs Init.  Call sequence = tests/c/verify_batch.c.
+func Groth16VerifyBatch(vk Groth16VkParts, proofs []Groth16BatchProof, challenge *big.Int, order *big.Int) (bool, error) {
+	ic, err := G1Points(vk.IC)
+	if err != nil {
+		return false, err
+	}
+	g1, err := G1Points([][3]*big.Int{vk.G1Alpha})
+	if err != nil {
+		return false, err
+	}
+	g2, err := G2Points([][3][2]*big.Int{vk.G2Beta, vk.G2Gamma, vk.G2Delta})
+	if err != nil {
+		return false, err
+	}
+	npublic := 0
+	if len(proofs) > 0 {
+		npublic = len(proofs[0].PublicSignals)
+	}
+	as := make([][3]*big.Int, 0, len(proofs))
+	bs := make([][3][2]*big.Int, 0, len(proofs))
+	cs := make([][3]*big.Int, 0, len(proofs))
+	signals := make([]*big.Int, 0, len(proofs)*npublic)
+	for _, p := range proofs {
+		if len(p.PublicSignals) != npublic {
+			return false, errors.New("gosnarkhip: every proof of one key has the same number of public signals")
+		}
+		as, bs, cs = append(as, p.PiA), append(bs, p.PiB), append(cs, p.PiC)
+		signals = append(signals, p.PublicSignals...)
+	}
+	a, err := G1Points(as)
+	if err != nil {
+		return false, err
+	}
+	b, err := G2Points(bs)
+	if err != nil {
+		return false, err
+	}
+	c, err := G1Points(cs)
+	if err != nil {
+		return false, err
+	}
+	pub, err := Scalars(signals, order)
+	if err != nil {
+		return false, err
+	}
+	ch, err := Scalars([]*big.Int{challenge}, order)
+	if err != nil {
+		return false, err
+	}
+	if len(pub) == 0 {
+		pub = make([]uint64, 4)
+	}
+	if len(proofs) == 0 {
+		a, b, c = make([]uint64, 12), make([]uint64, 24), make([]uint64, 12)
+	}
+	var ok C.int
+	err = call(func() C.int {
+		return C.gs_groth16_verify_batch(ptr(g1[0:]), ptr(g2[0:]), ptr(g2[24:]), ptr(g2[48:]), ptr(ic), C.size_t(len(vk.IC)),
+			ptr(pub), C.size_t(npublic), ptr(a), ptr(b), ptr(c), C.size_t(len(proofs)), ptr(ch), &ok)
+	})
+	runtime.KeepAlive(ic)
+	runtime.KeepAlive(g1)
+	runtime.KeepAlive(g2)
+	runtime.KeepAlive(pub)
+	runtime.KeepAlive(a)
+	runtime.KeepAlive(b)
+	runtime.KeepAlive(c)
+	runtime.KeepAlive(ch)
+	return ok == 1, err
+}

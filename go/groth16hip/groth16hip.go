@@ -419,3 +419,21 @@ func VerifyProof(vk groth16.Vk, proof groth16.Proof, publicSignals []*big.Int, d
 	}
 	return true
 }
+
+// VerifyProofs checks many proofs of one verification key in one randomised check on the device (gosnarkhip.Groth16VerifyBatch):
+// the answer of VerifyProof on every one of them, wrong with probability at most (len(proofs) - 1) / r and only towards true.
+// challenge is the caller's randomness, drawn uniformly below r AFTER the proofs are fixed (crypto/rand).  false does not say which
+// proof is bad: VerifyProof on each locates it.  An error (no device, a challenge of 0 or 1) reads as false.
+func VerifyProofs(vk groth16.Vk, proofs []groth16.Proof, publicSignals [][]*big.Int, challenge *big.Int) bool {
+	if len(proofs) != len(publicSignals) {
+		return false
+	}
+	batch := make([]gosnarkhip.Groth16BatchProof, len(proofs))
+	for i, p := range proofs {
+		batch[i] = gosnarkhip.Groth16BatchProof{PiA: p.PiA, PiB: p.PiB, PiC: p.PiC, PublicSignals: publicSignals[i]}
+	}
+	ok, err := gosnarkhip.Groth16VerifyBatch(gosnarkhip.Groth16VkParts{
+		IC: vk.IC, G1Alpha: vk.G1.Alpha, G2Beta: vk.G2.Beta, G2Gamma: vk.G2.Gamma, G2Delta: vk.G2.Delta,
+	}, batch, challenge, groth16.Utils.FqR.Q)
+	return err == nil && ok
+}

@@ -852,6 +852,45 @@ int gs_pinocchio_verify(const uint64_t vka[24], const uint64_t vkb[12], const ui
                         const uint64_t* vk_ic /* nic x 12 */, size_t nic, const uint64_t* public_signals, size_t npublic,
                         const uint64_t* proof /* 108 words */, int* ok, int* failed_check);
 
+/* ---- pairing products on the device; Groth16 proofs verified in batches ------------------------------------------------------------ */
+/* One proof check is O(1) work and stays on the host (above).  Thousands of proofs under one key are not: a host core checks one
+ * proof in the time the device proves one and a half.  These two entry points need gs_init.
+ *
+ * gs_pairing_product: prod_{i<n} e(P[poff + i], Q[qoff + i]) for the points of a resident G1 and a resident G2 base array on the same
+ * logical device, in gs_pairing's encoding and equal bit for bit to the product of the host's values.  *is_one = 1 iff the value is 1.
+ * Either out-pointer may be NULL, not both.  n = 0 gives 1; a pair with an infinite member contributes 1.
+ * PRECONDITION: the Q are in G2, the subgroup of order r.  The uploads guarantee the curve equation only; membership is the caller's
+ * job -- gs_g2_subgroup_check on the same handle.  For a point of the twist outside the subgroup the call still returns, with a value
+ * that means nothing (it runs the same instruction sequence whatever the points are).
+ * One lane per pair runs the optimal ate Miller loop (inversion-free projective steps, the Fq12 accumulator in LDS), the values are
+ * multiplied across each one-wave workgroup and then 64 to 1 per pass until at most 4 are left; those cross to the host, which
+ * finishes the product and runs the ONE final exponentiation on the calling thread.
+ * A range beyond an array is GS_ERR_SHAPE; a bad handle, a handle of the wrong kind or two null out-pointers GS_ERR_ARG; no device
+ * GS_ERR_NOT_INIT.  Blocking; gs_last_timing().total_ms = device time.
+ * go/gosnarkhip/pairing_device.go (PairingProduct) and tests/c/verify_batch.c are the plain call. */
+int gs_pairing_product(gs_handle g1, size_t poff, gs_handle g2, size_t qoff, size_t n,
+                       uint64_t out_fq12[48] /* may be NULL */, int* is_one /* may be NULL, not both */);
+/* nproofs Groth16 proofs of ONE verification key in one randomised check: with s = challenge mod r and the weights z_i = s^i,
+ *   *ok = 1  iff  prod_i e(-z_i A_i, B_i) . e((sum_i z_i) Alpha, Beta) . e(sum_i z_i vkx_i, Gamma) . e(sum_i z_i C_i, Delta) = 1,
+ * vkx_i = IC[0] + sum_j publicSignals[i][j] IC[j+1].  The arguments are gs_groth16_verify's with one more dimension; the host checks are
+ * the same (null arguments GS_ERR_ARG, nic < npublic + 1 GS_ERR_SHAPE, and under gs_verify_set_strict(1) nic != npublic + 1 is
+ * GS_ERR_SHAPE and a non-canonical coordinate or signal in any proof gives *ok = 0).  A point off its curve gives *ok = 0, a B
+ * outside the order-r subgroup (gs_g2_subgroup_check over all of them) gives *ok = 0.  nproofs = 0 gives *ok = 1 without touching
+ * the device.
+ * SOUNDNESS: a batch that holds an invalid proof passes with probability at most (nproofs - 1) / r over a challenge drawn uniformly
+ * AFTER the proofs are fixed (the product is a polynomial of degree nproofs - 1 in s in the exponent).  The challenge is the
+ * caller's randomness: a constant or a value the prover can predict voids the bound, and s = 0 or 1 mod r is GS_ERR_ARG.  *ok = 0 does
+ * not say WHICH proof is bad: gs_groth16_verify finds it.
+ * The device scales the A_i (gs_g1_scale_powers), sums the C_i (gs_msm_g1, table-free), tests the B_i and runs the nproofs Miller
+ * loops with their product; the host forms the npublic + 1 scalars of the public-input sum, the three key pairs and the one final
+ * exponentiation.  Every temporary array is freed on every path.  Blocking.
+ * go-snark-study_amd/groth16.py (VerifyProofs), go/gosnarkhip/pairing_device.go (Groth16VerifyBatch) and tests/c/verify_batch.c. */
+int gs_groth16_verify_batch(const uint64_t vk_g1_alpha[12], const uint64_t vk_g2_beta[24], const uint64_t vk_g2_gamma[24],
+                            const uint64_t vk_g2_delta[24], const uint64_t* vk_ic, size_t nic,
+                            const uint64_t* public_signals /* nproofs x npublic x 4 */, size_t npublic,
+                            const uint64_t* pi_a /* nproofs x 12 */, const uint64_t* pi_b /* nproofs x 24 */,
+                            const uint64_t* pi_c /* nproofs x 12 */, size_t nproofs, const uint64_t challenge[4], int* ok);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
