@@ -86,6 +86,20 @@ def PairingProduct(g1_handle, g2_handle, poff=0, qoff=0, n=None):
     return tuple(tuple((v[6 * i + 2 * j], v[6 * i + 2 * j + 1]) for j in range(3)) for i in range(2)), one
 
 
+def PairingEach(g1_handle, g2_handle, poff=0, qoff=0, n=None):
+    """e(P[poff + i], Q[qoff + i]) for EVERY i over two resident arrays (gs_pairing_each: Miller loop and final exponentiation on the
+    device; default: as many pairs as both arrays hold from their offsets) -> (the list of values in Pairing's nesting, the list of
+    "is one" flags).  Every value equals Pairing's of that pair.  The Q must be in G2."""
+    if n is None:
+        n = max(min(len(g1_handle) - poff, len(g2_handle) - qoff), 0)
+    out, one = capi.pairing_each(g1_handle, poff, g2_handle, qoff, n)
+    vals = []
+    for row in out:
+        v = capi.u64_to_ints(row)
+        vals.append(tuple(tuple((v[6 * i + 2 * j], v[6 * i + 2 * j + 1]) for j in range(3)) for i in range(2)))
+    return vals, [bool(x) for x in one]
+
+
 def PairingCheck(g1_points, g2_points):
     """prod_i e(g1_i, g2_i) == 1 with one shared final exponentiation (gs_pairing_check)."""
     if len(g1_points) != len(g2_points):

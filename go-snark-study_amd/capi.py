@@ -225,6 +225,9 @@ _SIGS = {
     "gs_groth16_verify": [u64p, u64p, u64p, u64p, u64p, ctypes.c_size_t, u64p, ctypes.c_size_t, u64p, u64p, u64p, intp],
     "gs_pinocchio_verify": [u64p, u64p, u64p, u64p, u64p, u64p, u64p, u64p, ctypes.c_size_t, u64p, ctypes.c_size_t, u64p, intp, intp],
     "gs_pairing_product": [Handle, ctypes.c_size_t, Handle, ctypes.c_size_t, ctypes.c_size_t, u64p, intp],
+    "gs_groth16_verify_each": [u64p, u64p, u64p, u64p, u64p, ctypes.c_size_t, u64p, ctypes.c_size_t, u64p, u64p, u64p, ctypes.c_size_t, intp,
+                               ctypes.POINTER(ctypes.c_uint64)],
+    "gs_pairing_each": [Handle, ctypes.c_size_t, Handle, ctypes.c_size_t, ctypes.c_size_t, u64p, intp],
     "gs_groth16_verify_batch": [u64p, u64p, u64p, u64p, u64p, ctypes.c_size_t, u64p, ctypes.c_size_t, u64p, u64p, u64p, ctypes.c_size_t, u64p, intp],
 }
 EXPORTS = sorted(list(_SIGS) + ["gs_shutdown", "gs_last_error", "gs_version", "gs_comm_destroy"])
@@ -696,6 +699,17 @@ def pairing_product(g1, poff, g2, qoff, n):
     out, one = np.zeros(48, dtype=np.uint64), ctypes.c_int(0)
     call("gs_pairing_product", raw(g1), int(poff), raw(g2), int(qoff), int(n), ptr64(out), ctypes.byref(one))
     return out, bool(one.value)
+
+
+def pairing_each(g1, poff, g2, qoff, n):
+    """gs_pairing_each: e(P[poff + i], Q[qoff + i]) for every i < n over a resident G1 and a resident G2 array, final exponentiation
+    on the device -> (the values as an (n, 48) array of gs_pairing's encoding, a bool array: which are one).  Every value equals
+    gs_pairing's bit for bit.  The Q must be in G2: g2_subgroup_check on the same handle is the caller's job."""
+    n = int(n)
+    out, one = np.zeros((n, 48), dtype=np.uint64), np.zeros(max(n, 1), dtype=np.intc)
+    call("gs_pairing_each", raw(g1), int(poff), raw(g2), int(qoff), n, ptr64(out) if n else ptr64(np.zeros(48, dtype=np.uint64)),
+         one.ctypes.data_as(intp))
+    return out, one[:n] != 0
 
 
 def scalars_upload(s_u64):

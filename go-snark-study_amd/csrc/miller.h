@@ -127,4 +127,94 @@ GS_HD void miller_loop(S& f, const Affine<FqTag>& p_in, const Affine<Fq2Tag>& q_
   for (int i = 1; i < 6; ++i) f.set(i, select(skip, fq2_zero<2>(), f.get(i)));
 }
 
+// ---- a Groth16 proof: three pairs, ONE accumulator --------------------------------------------------------------------------------
+// f <- the Miller value of e(P1, Q1) e(P2, gamma) e(P3, delta): the three pairs share the 64 squarings of f.  gamma and delta are the
+// same in every lane, so their lines come PREPARED (pairing.h, prepare_g2_lines: the host's affine steps, (lambda, lambda x_T - y_T)
+// per step) and a lane only evaluates them at its P2 and P3: y_P - lambda x_P w + c w^3.  Only the pair with Q1 runs G2 arithmetic,
+// the projective steps of miller_loop.  The lines of the three pairs differ from the host's by factors in Fq2, which the final
+// exponentiation removes.  A pair whose P (or Q1) is infinite, or whose `skip` flag is set (an infinite gamma or delta), contributes
+// one: its line is replaced by the constant 1, a select, not a branch.  L is anything with
+//     Fq2e<2> lambda(int k) const   and   Fq2e<2> c(int k) const      (k = the step, the same for every lane of a wave)
+constexpr int kPreparedSteps = 64 + 36 + 2;           // tangents + the 36 set bits of kAteLoopLow + the two Frobenius chords
+static_assert(__builtin_popcountll(kAteLoopLow) == 36, "kPreparedSteps");
+
+GS_HD Line line_or_one(bool skip, const Line& l) {
+  return {select(skip, relax<2>(fq2_one()), l.a), select(skip, fq2_zero<2>(), l.b), select(skip, fq2_zero<2>(), l.c)};
+}
+template <class L>
+GS_HD Line prepared_line_at(const L& lines, int k, const Fe<ModQ, 2>& nxp, const Fe<ModQ, 1>& yp) {
+  Line l;
+  l.a = {relax<2>(yp), fe_zero<ModQ, 2>()};
+  l.b = fq2_mul_fq(lines.lambda(k), nxp);
+  l.c = lines.c(k);
+  return l;
+}
+
+template <class S, class L>
+GS_HD void miller_loop_groth16(S& f, const Affine<FqTag>& p1_in, const Affine<Fq2Tag>& q1_in, const Affine<FqTag>& p2, bool skip_gamma,
+                               const L& gamma, const Affine<FqTag>& p3, bool skip_delta, const L& delta) {
+  bool skip1 = is_inf(p1_in);
+  skip1 |= is_inf(q1_in);
+  const bool skip2 = skip_gamma | is_inf(p2), skip3 = skip_delta | is_inf(p3);
+  Affine<FqTag> p;
+  Affine<Fq2Tag> q;
+#pragma unroll
+  for (int i = 0; i < NL; ++i) {                                       // the substitute pair: the generators
+    p.x.l[i] = skip1 ? Gen::g1x(i) : p1_in.x.l[i];
+    p.y.l[i] = skip1 ? Gen::g1y(i) : p1_in.y.l[i];
+    q.x.c0.l[i] = skip1 ? Gen::g2x0(i) : q1_in.x.c0.l[i];
+    q.x.c1.l[i] = skip1 ? Gen::g2x1(i) : q1_in.x.c1.l[i];
+    q.y.c0.l[i] = skip1 ? Gen::g2y0(i) : q1_in.y.c0.l[i];
+    q.y.c1.l[i] = skip1 ? Gen::g2y1(i) : q1_in.y.c1.l[i];
+  }
+  const Fe<ModQ, 2> nxp = neg(p.x), nxp2 = neg(p2.x), nxp3 = neg(p3.x);
+  G2Proj t = {relax<2>(q.x), relax<2>(q.y), relax<2>(fq2_one())};
+  Affine<Fq2Tag> r = q;
+  f12_set_one(f);
+  int k = 0;
+#pragma unroll 1
+  for (int i = 63; i >= -2; --i) {
+#pragma unroll 1
+    for (int phase = 0; phase < 2; ++phase) {
+      Line l;
+      if (phase == 0) {
+        if (i < 0) continue;
+        f12_sqr(f);
+        l = miller_double(t, nxp, p.y);
+      } else {
+        if (i >= 0 && !((kAteLoopLow >> i) & 1ull)) continue;
+        if (i < 0) {
+          r = miller_psi(r);
+          if (i == -2) r.y = canon(neg(r.y));
+        }
+        l = miller_add(t, r, nxp, p.y);
+      }
+      l = line_or_one(skip1, l);
+      f12_mul_line(f, l.a, l.b, l.c);
+      l = line_or_one(skip2, prepared_line_at(gamma, k, nxp2, p2.y));
+      f12_mul_line(f, l.a, l.b, l.c);
+      l = line_or_one(skip3, prepared_line_at(delta, k, nxp3, p3.y));
+      f12_mul_line(f, l.a, l.b, l.c);
+      ++k;
+    }
+  }
+}
+
+// vkx = IC_0 + sum_j pub_j IC_{j+1} (verify.hip, accumulate_ic): a joint double-and-add over the npublic points, ONE doubling chain of
+// 256 steps and an addition per set bit per signal, complete formulas (ec.h), so any 256-bit scalar is taken as it is -- the group law
+// reduces it -- and an addition that meets a doubling or the inverse is right.  ic(j) gives the affine IC_j, bit(j, b) bit b of signal j.
+template <class IC, class BITS>
+GS_HD Affine<FqTag> groth16_vkx(const IC& ic, const BITS& bit, int npublic) {
+  Xyzz<FqTag> acc = xyzz_inf<FqTag>();
+#pragma unroll 1
+  for (int b = 255; b >= 0; --b) {
+    xyzz_dbl(acc);
+#pragma unroll 1
+    for (int j = 0; j < npublic; ++j)
+      if (bit(j, b)) xyzz_madd(acc, ic(j + 1));
+  }
+  xyzz_madd(acc, ic(0));
+  return xyzz_to_affine(acc);
+}
+
 }  // namespace gs

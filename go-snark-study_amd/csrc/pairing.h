@@ -594,5 +594,47 @@ inline bool multi_miller_loop(const std::vector<G1Aff>& ps, const std::vector<G2
   return true;
 }
 
+// "Prepared G2": the lines of the loop above for ONE finite Q, before they are evaluated at a P.  Step k (the order of the loop:
+// per bit the tangent, then the chord if the bit is set; then the chords to pi(Q) and -pi^2(Q)) is the pair (lambda, lambda x_T - y_T)
+// in standard form, 16 words: the line at P is y_P - lambda x_P w + (lambda x_T - y_T) w^3.  The steps do not depend on P, so a
+// verifier whose Q is the same in every pairing (gamma and delta of a Groth16 key) computes them once.  False on a degenerate step.
+static const int kPreparedSteps = 64 + 36 + 2;       // tangents + the 36 set bits of kLoop[0] + the two Frobenius chords
+inline bool prepare_g2_lines(const G2Aff& q, std::vector<uint64_t>& out) {
+  out.clear();
+  Fp2 tx = q.x, ty = q.y;
+  auto step = [&](const G2Aff* other) -> bool {
+    const Fp2 den = other ? f2_sub(other->x, tx) : f2_dbl(ty);
+    if (f2_is_zero(den)) return false;
+    const Fp2 di = f2_inv(den);
+    Fp2 lam, x3;
+    if (!other) {
+      const Fp2 xx = f2_sqr(tx);
+      lam = f2_mul(f2_add(f2_dbl(xx), xx), di);
+      x3 = f2_sub(f2_sqr(lam), f2_dbl(tx));
+    } else {
+      lam = f2_mul(f2_sub(other->y, ty), di);
+      x3 = f2_sub(f2_sub(f2_sqr(lam), tx), other->x);
+    }
+    const Fp2 c = f2_sub(f2_mul(lam, tx), ty);
+    uint64_t w[16];
+    fp_to_std(lam.c0, w); fp_to_std(lam.c1, w + 4); fp_to_std(c.c0, w + 8); fp_to_std(c.c1, w + 12);
+    out.insert(out.end(), w, w + 16);
+    const Fp2 y3 = f2_sub(f2_mul(lam, f2_sub(tx, x3)), ty);
+    tx = x3;
+    ty = y3;
+    return true;
+  };
+  for (int b = 63; b >= 0; --b) {
+    if (!step(nullptr)) return false;
+    if ((kLoop[0] >> b) & 1)
+      if (!step(&q)) return false;
+  }
+  const TowerConsts& t = twc();
+  const G2Aff q1{f2_mul(f2_conj(q.x), t.g1[2]), f2_mul(f2_conj(q.y), t.g1[3]), false};
+  const G2Aff q2n{f2_mul(q.x, t.g2[2]), f2_neg(f2_mul(q.y, t.g2[3])), false};
+  if (!step(&q1) || !step(&q2n)) return false;
+  return out.size() == (size_t)kPreparedSteps * 16;
+}
+
 }  // namespace pairing
 }  // namespace gs

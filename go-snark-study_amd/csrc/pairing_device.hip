@@ -7,8 +7,12 @@
 // An Fq12 accumulator is 108 limbs per lane -- k_g2_subgroup already fills the register file with a G2 point -- so it lives in LDS,
 // limb-major ([limb][lane]: a wave's access to one limb is 64 consecutive words, no bank conflict), 27 KB per one-wave workgroup.
 // The running G2 point, the pair and the line stay in registers.  Partials travel in gs_pairing's standard encoding (96 words).
+//
+// gs_pairing_each: e(P_i, Q_i) for EVERY i.  k_miller_each is the same loop without the product; k_final_exp runs the final
+// exponentiation of finalexp.h per lane ("one value per pair" below).
 #include <vector>
 
+#include "finalexp.h"
 #include "miller.h"
 #include "pairing.h"
 #include "point_io.h"
@@ -80,6 +84,238 @@ __global__ void __launch_bounds__(kPairBlock) k_f12_product(const uint32_t* __re
   wave_product_store(lds, out);
 }
 
+// ---- one value per pair: gs_pairing_each -------------------------------------------------------------------------------------
+// The final exponentiation (finalexp.h) keeps the working value in LDS like the Miller loop and its five temporaries in a global
+// workspace of the workgroup, each in the same limb-major [limb][lane] layout: a wave's access to one limb is 64 consecutive
+// words.  Slot 0 is also where k_miller_each leaves lane i's Miller value, so nothing passes through the standard encoding.
+constexpr size_t kSlotWords = (size_t)kF12Limbs * kPairBlock;
+constexpr size_t kWorkspaceWords = kFeSlots * kSlotWords;             // per workgroup
+
+struct GlbF12 {
+  uint32_t* __restrict__ base;
+  __device__ __forceinline__ Fq2e<2> get(int i) const {
+    Fq2e<2> r;
+#pragma unroll
+    for (int k = 0; k < NL; ++k) { r.c0.l[k] = base[(2 * NL * i + k) * kPairBlock]; r.c1.l[k] = base[(2 * NL * i + NL + k) * kPairBlock]; }
+    return r;
+  }
+  __device__ __forceinline__ void set(int i, const Fq2e<2>& v) {
+#pragma unroll
+    for (int k = 0; k < NL; ++k) { base[(2 * NL * i + k) * kPairBlock] = v.c0.l[k]; base[(2 * NL * i + NL + k) * kPairBlock] = v.c1.l[k]; }
+  }
+};
+struct GlbBank {
+  uint32_t* base;                                                      // the workgroup's workspace + lane
+  __device__ __forceinline__ GlbF12 slot(int i) const { return GlbF12{base + (size_t)i * kSlotWords}; }
+};
+
+// lane i's Miller value, kept: written to slot 0 of the workgroup's workspace (lanes past the end write one)
+__global__ void __launch_bounds__(kPairBlock) k_miller_each(const uint32_t* __restrict__ g1, const uint32_t* __restrict__ g2, uint32_t n,
+                                                            uint32_t* __restrict__ workspace) {
+  __shared__ uint32_t lds[kF12Limbs][kPairBlock];
+  const size_t i = (size_t)blockIdx.x * kPairBlock + threadIdx.x;
+  const size_t at = i < n ? i : 0;
+  Affine<FqTag> p = PointIO<FqTag>::load_affine(g1 + at * PointIO<FqTag>::kAffineWords);
+  const Affine<Fq2Tag> q = PointIO<Fq2Tag>::load_affine(g2 + at * PointIO<Fq2Tag>::kAffineWords);
+  if (i >= n) { p.x = fe_zero<ModQ, 1>(); p.y = fe_zero<ModQ, 1>(); }
+  LdsF12 f{&lds[0][threadIdx.x]};
+  miller_loop(f, p, q);
+  GlbF12 out{workspace + (size_t)blockIdx.x * kWorkspaceWords + threadIdx.x};
+  f12_copy(out, f);
+}
+
+// slot 0 of every lane -> its final exponentiation, in the standard encoding, and whether it is one
+__global__ void __launch_bounds__(kPairBlock) k_final_exp(uint32_t* __restrict__ workspace, uint32_t n, uint32_t* __restrict__ out_std,
+                                                          uint32_t* __restrict__ is_one) {
+  __shared__ uint32_t lds[kF12Limbs][kPairBlock];
+  const size_t i = (size_t)blockIdx.x * kPairBlock + threadIdx.x;
+  LdsF12 w{&lds[0][threadIdx.x]};
+  GlbBank bank{workspace + (size_t)blockIdx.x * kWorkspaceWords + threadIdx.x};
+  f12_copy(w, bank.slot(0));
+  final_exponentiation(w, bank);
+  if (i < n) {
+    f12_to_std(w, reinterpret_cast<uint64_t*>(out_std + i * kF12Words));
+    is_one[i] = f12_is_one(w) ? 1u : 0u;
+  }
+}
+
+int pairing_each_impl(Ctx& c, const char* fn, gs_handle h1, size_t poff, gs_handle h2, size_t qoff, size_t n, uint64_t* out_fq12, int* is_one) {
+  Bases* ps = c.get<Bases>(h1, Kind::G1Bases);
+  Bases* qs = c.get<Bases>(h2, Kind::G2Bases);
+  if (!ps) return fail(GS_ERR_ARG, "%s: bad G1 base-array handle", fn);
+  if (!qs) return fail(GS_ERR_ARG, "%s: bad G2 base-array handle", fn);
+  if (!out_fq12 && !is_one) return fail(GS_ERR_ARG, "%s: both out-pointers are null", fn);
+  if (poff > ps->n || ps->n - poff < n) return fail(GS_ERR_SHAPE, "%s: the G1 array has %zu points, %zu were asked for from index %zu", fn, ps->n, n, poff);
+  if (qoff > qs->n || qs->n - qoff < n) return fail(GS_ERR_SHAPE, "%s: the G2 array has %zu points, %zu were asked for from index %zu", fn, qs->n, n, qoff);
+  if (n >= 0xffffffffull) return fail(GS_ERR_SHAPE, "%s: %zu pairs, indices are 32 bits", fn, n);
+  c.drain();
+  PhaseTimer t(c.stream);
+  if (!n) {
+    t.stop();
+    reset_timing(c);
+    c.timing.total_ms = t.ms();
+    return GS_OK;
+  }
+  const size_t count = (n + kPairBlock - 1) / kPairBlock;
+  DevBuf ws(count * kWorkspaceWords * 4), vals(n * kF12Words * 4), flags(n * 4);
+  PhaseTimer tm(c.stream);
+  hipLaunchKernelGGL(k_miller_each, dim3((unsigned)count), dim3(kPairBlock), 0, c.stream,
+                     ps->buf.as<uint32_t>() + poff * PointIO<FqTag>::kAffineWords, qs->buf.as<uint32_t>() + qoff * PointIO<Fq2Tag>::kAffineWords,
+                     (uint32_t)n, ws.as<uint32_t>());
+  GS_HIP(hipGetLastError());
+  tm.stop();
+  PhaseTimer tf(c.stream);
+  hipLaunchKernelGGL(k_final_exp, dim3((unsigned)count), dim3(kPairBlock), 0, c.stream, ws.as<uint32_t>(), (uint32_t)n, vals.as<uint32_t>(),
+                     flags.as<uint32_t>());
+  GS_HIP(hipGetLastError());
+  tf.stop();
+  t.stop();
+  std::vector<uint32_t> host_flags(is_one ? n : 0);
+  if (out_fq12) GS_HIP(hipMemcpyAsync(out_fq12, vals.p, n * kF12Words * 4, hipMemcpyDeviceToHost, c.stream));
+  if (is_one) GS_HIP(hipMemcpyAsync(host_flags.data(), flags.p, n * 4, hipMemcpyDeviceToHost, c.stream));
+  GS_HIP(hipStreamSynchronize(c.stream));
+  if (is_one) for (size_t i = 0; i < n; ++i) is_one[i] = (int)host_flags[i];
+  reset_timing(c);
+  c.timing.total_ms = t.ms();
+  c.timing.accumulate_ms = tm.ms();                                    // the Miller loops
+  c.timing.reduce_ms = tf.ms();                                        // the final exponentiations
+  return GS_OK;
+}
+
+// ---- a verdict per Groth16 proof: gs_groth16_verify_each (verify.hip) ----------------------------------------------------------
+constexpr int kLineWords = 4 * NL;                                     // lambda.c0, lambda.c1, c.c0, c.c1 as limbs
+
+// prepared lines arrive in standard form (pairing.h, prepare_g2_lines): one thread per field element makes limbs of them, once
+__global__ void k_std_to_limbs(const uint32_t* __restrict__ in, uint32_t nfe, uint32_t* __restrict__ out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nfe) return;
+  uint32_t w[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) w[k] = in[(size_t)i * 8 + k];
+  const Fe<ModQ, 1> v = canon(to_mont(unpack32<ModQ>(w)));
+#pragma unroll
+  for (int k = 0; k < NL; ++k) out[(size_t)i * NL + k] = v.l[k];
+}
+
+struct PreparedLines {                                                 // the same words for every lane: a broadcast load
+  const uint32_t* __restrict__ base;
+  __device__ __forceinline__ Fq2e<2> pair_at(const uint32_t* p) const {
+    Fq2e<2> r;
+#pragma unroll
+    for (int k = 0; k < NL; ++k) { r.c0.l[k] = p[k]; r.c1.l[k] = p[NL + k]; }
+    return r;
+  }
+  __device__ __forceinline__ Fq2e<2> lambda(int k) const { return pair_at(base + (size_t)k * kLineWords); }
+  __device__ __forceinline__ Fq2e<2> c(int k) const { return pair_at(base + (size_t)k * kLineWords + 2 * NL); }
+};
+
+// vkx_i = IC_0 + sum_j pub_ij IC_{j+1}, one lane per proof (miller.h, groth16_vkx)
+__global__ void __launch_bounds__(kPairBlock) k_groth16_vkx(const uint32_t* __restrict__ ic, const uint32_t* __restrict__ pub, uint32_t npublic,
+                                                            uint32_t n, uint32_t* __restrict__ out) {
+  constexpr int kAw = PointIO<FqTag>::kAffineWords;
+  const size_t i = (size_t)blockIdx.x * kPairBlock + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t* mine = pub + i * npublic * 8;
+  const auto point = [&](int j) { return PointIO<FqTag>::load_affine(ic + (size_t)j * kAw); };
+  const auto bit = [&](int j, int b) { return ((mine[(size_t)j * 8 + (b >> 5)] >> (b & 31)) & 1u) != 0; };
+  PointIO<FqTag>::store_affine(out + i * kAw, groth16_vkx(point, bit, (int)npublic));
+}
+
+// flags[i] = is point i in G2?  (g2_subgroup.h; gs_g2_subgroup_check's kernel reports a count and the first index only)
+__global__ void __launch_bounds__(kPairBlock) k_g2_member_flags(const uint32_t* __restrict__ in, uint32_t n, uint32_t* __restrict__ flags) {
+  const size_t i = (size_t)blockIdx.x * kPairBlock + threadIdx.x;
+  if (i >= n) return;
+  flags[i] = g2_in_subgroup(PointIO<Fq2Tag>::load_affine(in + i * PointIO<Fq2Tag>::kAffineWords)) ? 1u : 0u;
+}
+
+// lane i: the Miller value of e(-A_i, B_i) e(vkx_i, gamma) e(C_i, delta) in ONE accumulator, times the key's e(alpha, beta) Miller
+// value (ab, standard encoding), into slot 0 of the workgroup's workspace for k_final_exp
+__global__ void __launch_bounds__(kPairBlock) k_miller_groth16(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b, const uint32_t* __restrict__ c,
+                                                               const uint32_t* __restrict__ vkx, uint32_t n, const uint32_t* __restrict__ lines,
+                                                               uint32_t skip_gamma, uint32_t skip_delta, const uint64_t* __restrict__ ab,
+                                                               uint32_t* __restrict__ workspace) {
+  __shared__ uint32_t lds[kF12Limbs][kPairBlock];
+  constexpr int kA1 = PointIO<FqTag>::kAffineWords, kA2 = PointIO<Fq2Tag>::kAffineWords;
+  const size_t i = (size_t)blockIdx.x * kPairBlock + threadIdx.x;
+  const size_t at = i < n ? i : 0;                                     // lanes past the end read proof 0 and are not read back
+  Affine<FqTag> p1 = PointIO<FqTag>::load_affine(a + at * kA1);
+  const Affine<Fq2Tag> q1 = PointIO<Fq2Tag>::load_affine(b + at * kA2);
+  const Affine<FqTag> p2 = PointIO<FqTag>::load_affine(vkx + at * kA1);
+  const Affine<FqTag> p3 = PointIO<FqTag>::load_affine(c + at * kA1);
+  p1.y = canon(neg(p1.y));                                             // -A; infinity (0, 0) stays infinity
+  LdsF12 f{&lds[0][threadIdx.x]};
+  miller_loop_groth16(f, p1, q1, p2, skip_gamma != 0, PreparedLines{lines}, p3, skip_delta != 0,
+                      PreparedLines{lines + (size_t)kPreparedSteps * kLineWords});
+  GlbBank bank{workspace + (size_t)blockIdx.x * kWorkspaceWords + threadIdx.x};
+  GlbF12 key = bank.slot(1);
+  f12_from_std(key, ab);
+  f12_mul(f, key);
+  GlbF12 out = bank.slot(0);
+  f12_copy(out, f);
+}
+
+int verify_each_impl(Ctx& c, const char* fn, gs_handle ha, gs_handle hb, gs_handle hc, gs_handle hic, const uint64_t* pub, size_t npublic, size_t n,
+                     const uint64_t* gamma_lines, const uint64_t* delta_lines, const uint64_t* ab, int* member, int* is_one) {
+  Bases* as = c.get<Bases>(ha, Kind::G1Bases);
+  Bases* bs = c.get<Bases>(hb, Kind::G2Bases);
+  Bases* cs = c.get<Bases>(hc, Kind::G1Bases);
+  Bases* ics = c.get<Bases>(hic, Kind::G1Bases);
+  if (!as || !bs || !cs || !ics) return fail(GS_ERR_ARG, "%s: bad base-array handle", fn);
+  if (as->n != n || bs->n != n || cs->n != n || ics->n < npublic + 1) return fail(GS_ERR_SHAPE, "%s: the arrays do not hold %zu proofs", fn, n);
+  if (!n || n >= 0xffffffffull || npublic >= 0xffffffffull) return fail(GS_ERR_SHAPE, "%s: %zu proofs, indices are 32 bits", fn, n);
+  c.drain();
+  constexpr size_t kLineStd = (size_t)kPreparedSteps * 16;              // u64 words of one prepared list
+  const size_t count = (n + kPairBlock - 1) / kPairBlock;
+  const size_t pub_bytes = n * npublic * 32;
+  DevBuf ws(count * kWorkspaceWords * 4), vals(n * kF12Words * 4), flags(n * 4), members(n * 4), vkx(n * PointIO<FqTag>::kAffineWords * 4);
+  DevBuf dpub(pub_bytes ? pub_bytes : 32), lines_std(2 * kLineStd * 8), lines(2 * (size_t)kPreparedSteps * kLineWords * 4), dab(48 * 8);
+  PhaseTimer t(c.stream), tu(c.stream);
+  std::vector<uint64_t> host_lines(2 * kLineStd, 0);
+  if (gamma_lines) memcpy(host_lines.data(), gamma_lines, kLineStd * 8);
+  if (delta_lines) memcpy(host_lines.data() + kLineStd, delta_lines, kLineStd * 8);
+  if (pub_bytes) GS_HIP(hipMemcpyAsync(dpub.p, pub, pub_bytes, hipMemcpyHostToDevice, c.stream));
+  GS_HIP(hipMemcpyAsync(lines_std.p, host_lines.data(), 2 * kLineStd * 8, hipMemcpyHostToDevice, c.stream));
+  GS_HIP(hipMemcpyAsync(dab.p, ab, 48 * 8, hipMemcpyHostToDevice, c.stream));
+  const uint32_t nfe = 2 * kPreparedSteps * 4;
+  hipLaunchKernelGGL(k_std_to_limbs, dim3((nfe + 63) / 64), dim3(64), 0, c.stream, lines_std.as<uint32_t>(), nfe, lines.as<uint32_t>());
+  GS_HIP(hipGetLastError());
+  tu.stop();
+  PhaseTimer tmem(c.stream);
+  hipLaunchKernelGGL(k_g2_member_flags, dim3((unsigned)count), dim3(kPairBlock), 0, c.stream, bs->buf.as<uint32_t>(), (uint32_t)n, members.as<uint32_t>());
+  GS_HIP(hipGetLastError());
+  tmem.stop();
+  PhaseTimer tv(c.stream);
+  hipLaunchKernelGGL(k_groth16_vkx, dim3((unsigned)count), dim3(kPairBlock), 0, c.stream, ics->buf.as<uint32_t>(), dpub.as<uint32_t>(), (uint32_t)npublic,
+                     (uint32_t)n, vkx.as<uint32_t>());
+  GS_HIP(hipGetLastError());
+  tv.stop();
+  PhaseTimer tm(c.stream);
+  hipLaunchKernelGGL(k_miller_groth16, dim3((unsigned)count), dim3(kPairBlock), 0, c.stream, as->buf.as<uint32_t>(), bs->buf.as<uint32_t>(),
+                     cs->buf.as<uint32_t>(), vkx.as<uint32_t>(), (uint32_t)n, lines.as<uint32_t>(), gamma_lines ? 0u : 1u, delta_lines ? 0u : 1u,
+                     dab.as<uint64_t>(), ws.as<uint32_t>());
+  GS_HIP(hipGetLastError());
+  tm.stop();
+  PhaseTimer tf(c.stream);
+  hipLaunchKernelGGL(k_final_exp, dim3((unsigned)count), dim3(kPairBlock), 0, c.stream, ws.as<uint32_t>(), (uint32_t)n, vals.as<uint32_t>(),
+                     flags.as<uint32_t>());
+  GS_HIP(hipGetLastError());
+  tf.stop();
+  t.stop();
+  std::vector<uint32_t> hf(n), hm(n);
+  GS_HIP(hipMemcpyAsync(hf.data(), flags.p, n * 4, hipMemcpyDeviceToHost, c.stream));
+  GS_HIP(hipMemcpyAsync(hm.data(), members.p, n * 4, hipMemcpyDeviceToHost, c.stream));
+  GS_HIP(hipStreamSynchronize(c.stream));
+  for (size_t i = 0; i < n; ++i) { is_one[i] = (int)hf[i]; member[i] = (int)hm[i]; }
+  reset_timing(c);
+  c.timing.total_ms = t.ms();
+  c.timing.h2d_ms = tu.ms();                                           // signals, lines, the key's Miller value
+  c.timing.poly_ms = tmem.ms();                                        // membership of the B_i
+  c.timing.plan_ms = tv.ms();                                          // vkx
+  c.timing.accumulate_ms = tm.ms();                                    // the Miller loops
+  c.timing.reduce_ms = tf.ms();                                        // the final exponentiations
+  return GS_OK;
+}
+
 pairing::Fp12 host_f12(const uint64_t* w) {
   using namespace gs::pairing;
   Fp12 f;
@@ -147,6 +383,16 @@ int miller_product(const char* fn, gs_handle g1, size_t poff, gs_handle g2, size
   return guarded([&](Ctx& ctx) -> int { return miller_product_impl(ctx, fn, g1, poff, g2, qoff, n, out); }, true, false, g1);
 }
 
+// for gs_groth16_verify_each (verify.hip): per proof, is B in G2 and is the exponentiated product of the four pairs one.  The four
+// arrays are resident; gamma_lines / delta_lines are prepared lists (pairing.h) or null for an infinite gamma / delta; ab is the
+// Miller value of e(alpha, beta) in the standard encoding.
+int groth16_verify_each_device(const char* fn, gs_handle ha, gs_handle hb, gs_handle hc, gs_handle hic, const uint64_t* pub, size_t npublic, size_t n,
+                               const uint64_t* gamma_lines, const uint64_t* delta_lines, const uint64_t* ab, int* member, int* is_one) {
+  return guarded([&](Ctx& ctx) -> int { return verify_each_impl(ctx, fn, ha, hb, hc, hic, pub, npublic, n, gamma_lines, delta_lines, ab, member, is_one); },
+                 true, false, ha);
+}
+void f12_words(const pairing::Fp12& f, uint64_t* out) { host_f12_to_std(f, out); }
+
 }  // namespace gs
 
 extern "C" {
@@ -162,6 +408,10 @@ int gs_pairing_product(gs_handle g1, size_t poff, gs_handle g2, size_t qoff, siz
   if (out_fq12) host_f12_to_std(v, out_fq12);
   if (is_one) *is_one = pairing::f12_eq(v, pairing::f12_one()) ? 1 : 0;
   return GS_OK;
+}
+
+int gs_pairing_each(gs_handle g1, size_t poff, gs_handle g2, size_t qoff, size_t n, uint64_t* out_fq12, int* is_one) {
+  return guarded([&](Ctx& ctx) -> int { return pairing_each_impl(ctx, "gs_pairing_each", g1, poff, g2, qoff, n, out_fq12, is_one); }, true, false, g1);
 }
 
 }  // extern "C"

@@ -200,6 +200,9 @@ int gs_pinocchio_verify(const uint64_t vka[24], const uint64_t vkb[12], const ui
 
 namespace gs {
 int miller_product(const char* fn, gs_handle g1, size_t poff, gs_handle g2, size_t qoff, size_t n, pairing::Fp12* out);   // pairing_device.hip
+int groth16_verify_each_device(const char* fn, gs_handle ha, gs_handle hb, gs_handle hc, gs_handle hic, const uint64_t* pub, size_t npublic, size_t n,
+                               const uint64_t* gamma_lines, const uint64_t* delta_lines, const uint64_t* ab, int* member, int* is_one);
+void f12_words(const pairing::Fp12& f, uint64_t* out);
 }
 
 namespace {
@@ -364,6 +367,85 @@ int gs_groth16_verify_batch(const uint64_t vk_g1_alpha[12], const uint64_t vk_g2
     Fp12 f;
     if ((rc = gs::miller_product(fn, *hna, 0, *hb, 0, n, &f)) != GS_OK) return rc;
     *ok = f12_eq(final_exponentiation(f12_mul(f, fkey)), f12_one()) ? 1 : 0;
+    return GS_OK;
+  });
+}
+
+// gs_groth16_verify_each (include/gosnark_hip.h): the verdict of gs_groth16_verify for every proof of a batch, on the device.  The host
+// does what is O(1) per call or a few products per proof: the key (curve tests, the Miller value of e(alpha, beta), the prepared lines
+// of gamma and delta) and the screening of the 3n points, because the uploads refuse a whole array for one point off its curve: such a
+// proof gets 0 and the point at infinity travels in its place.
+int gs_groth16_verify_each(const uint64_t vk_g1_alpha[12], const uint64_t vk_g2_beta[24], const uint64_t vk_g2_gamma[24],
+                           const uint64_t vk_g2_delta[24], const uint64_t* vk_ic, size_t nic, const uint64_t* public_signals, size_t npublic,
+                           const uint64_t* pi_a, const uint64_t* pi_b, const uint64_t* pi_c, size_t nproofs, int* ok_each, uint64_t* nbad) {
+  return host_guarded([&]() -> int {
+    const char* fn = "gs_groth16_verify_each";
+    const size_t n = nproofs;
+    if (!vk_g1_alpha || !vk_g2_beta || !vk_g2_gamma || !vk_g2_delta || !vk_ic || (n && (!pi_a || !pi_b || !pi_c || !ok_each)) ||
+        (n && npublic && !public_signals))
+      return fail(GS_ERR_ARG, "%s: null argument", fn);
+    if (nic < npublic + 1) return fail(GS_ERR_SHAPE, "%s: %zu public signals need %zu IC points, vk has %zu", fn, npublic, npublic + 1, nic);
+    const bool strict = g_strict.load() != 0;
+    if (strict && nic != npublic + 1)
+      return fail(GS_ERR_SHAPE, "%s (strict): vk has %zu IC points, so exactly %zu public signals are required (got %zu)", fn, nic, nic - 1, npublic);
+    if (!n) {
+      if (nbad) *nbad = 0;
+      return GS_OK;
+    }
+    // the IC points go up first: without a device this is where the call ends, before any work and with nothing written
+    HandleBag bag;
+    gs_handle *ha = &bag.hs[0], *hb = &bag.hs[1], *hc = &bag.hs[2], *hic = &bag.hs[3];
+    bool key_ok = true;
+    int rc = gs_g1_upload(vk_ic, nic, hic);
+    if (rc == GS_ERR_ARG) key_ok = false;                               // an IC point off the curve
+    else if (rc != GS_OK) return rc;
+    const auto all_zero = [&]() -> int {
+      for (size_t i = 0; i < n; ++i) ok_each[i] = 0;
+      if (nbad) *nbad = n;
+      return GS_OK;
+    };
+    // the key: a point off its curve or a degenerate step makes every verdict 0, as it makes gs_groth16_verify answer 0 for every proof
+    const G1Aff alpha = g1_from_jacobian_std(vk_g1_alpha);
+    const G2Aff beta = g2_from_jacobian_std(vk_g2_beta), gamma = g2_from_jacobian_std(vk_g2_gamma), delta = g2_from_jacobian_std(vk_g2_delta);
+    if (!key_ok || !g1_on_curve(alpha) || !g2_on_curve(beta) || !g2_on_curve(gamma) || !g2_on_curve(delta)) return all_zero();
+    Fp12 fab;
+    if (!multi_miller_loop({alpha}, {beta}, fab)) return all_zero();
+    uint64_t ab[48];
+    gs::f12_words(fab, ab);
+    std::vector<uint64_t> gl, dl;
+    if (!gamma.inf && !prepare_g2_lines(gamma, gl)) return all_zero();
+    if (!delta.inf && !prepare_g2_lines(delta, dl)) return all_zero();
+    // the proofs: per proof what the single verifier tests before its pairings
+    std::vector<uint64_t> a(pi_a, pi_a + 12 * n), b(pi_b, pi_b + 24 * n), c(pi_c, pi_c + 12 * n);
+    std::vector<char> bad(n, 0);
+    for (size_t i = 0; i < n; ++i) {
+      bool good = true;
+      if (strict && (!scalars_canonical(public_signals + 4 * i * npublic, npublic) || !coords_canonical(pi_a + 12 * i, 3) ||
+                     !coords_canonical(pi_b + 24 * i, 6) || !coords_canonical(pi_c + 12 * i, 3)))
+        good = false;
+      if (good && (!g1_on_curve(g1_from_jacobian_std(pi_a + 12 * i)) || !g2_on_curve(g2_from_jacobian_std(pi_b + 24 * i)) ||
+                   !g1_on_curve(g1_from_jacobian_std(pi_c + 12 * i))))
+        good = false;
+      if (!good) {
+        bad[i] = 1;
+        memset(a.data() + 12 * i, 0, 96);
+        memset(b.data() + 24 * i, 0, 192);
+        memset(c.data() + 12 * i, 0, 96);
+      }
+    }
+    if ((rc = gs_g1_upload(a.data(), n, ha)) != GS_OK) return rc;
+    if ((rc = gs_g2_upload(b.data(), n, hb)) != GS_OK) return rc;
+    if ((rc = gs_g1_upload(c.data(), n, hc)) != GS_OK) return rc;
+    std::vector<int> member(n), one(n);
+    rc = gs::groth16_verify_each_device(fn, *ha, *hb, *hc, *hic, public_signals, npublic, n, gamma.inf ? nullptr : gl.data(),
+                                        delta.inf ? nullptr : dl.data(), ab, member.data(), one.data());
+    if (rc != GS_OK) return rc;
+    uint64_t count = 0;
+    for (size_t i = 0; i < n; ++i) {
+      ok_each[i] = (!bad[i] && member[i] && one[i]) ? 1 : 0;
+      count += ok_each[i] ? 0 : 1;
+    }
+    if (nbad) *nbad = count;
     return GS_OK;
   });
 }

@@ -26,6 +26,30 @@ func PairingProduct(g1 Handle, poff int, g2 Handle, qoff, n int) (value [48]uint
 	return value, one == 1, err
 }
 
+// PairingEach is e(P[poff+i], Q[qoff+i]) for EVERY i < n over a resident G1 and a resident G2 array (gs_pairing_each): Miller loop and
+// final exponentiation on the device, one lane per pair.  values holds n x 48 words in Pairing's encoding, each equal to Pairing of
+// that pair bit for bit; isOne[i] says whether value i is one.  A pair with an infinite member gives one.  The Q must be in G2
+// (G2SubgroupCheck on the same handle).  Call sequence = tests/c/pairing_each.c.
+func PairingEach(g1 Handle, poff int, g2 Handle, qoff, n int) (values []uint64, isOne []bool, err error) {
+	if n < 0 {
+		return nil, nil, errors.New("gosnarkhip: PairingEach: negative count")
+	}
+	values = make([]uint64, 48*n+48)
+	ones := make([]C.int, n+1)
+	err = call(func() C.int {
+		return C.gs_pairing_each(C.gs_handle(g1), C.size_t(poff), C.gs_handle(g2), C.size_t(qoff), C.size_t(n), ptr(values), &ones[0])
+	})
+	runtime.KeepAlive(ones)
+	if err != nil {
+		return nil, nil, err
+	}
+	isOne = make([]bool, n)
+	for i := range isOne {
+		isOne[i] = ones[i] == 1
+	}
+	return values[:48*n], isOne, nil
+}
+
 // Groth16BatchProof is one proof of a batch with its public signals.
 type Groth16BatchProof struct {
 	PiA           [3]*big.Int
@@ -37,7 +61,7 @@ type Groth16BatchProof struct {
 // Groth16VerifyBatch checks many proofs of ONE verification key in one randomised product check (gs_groth16_verify_batch): true iff
 // every proof verifies, wrong with probability at most (len(proofs) - 1) / r over a challenge drawn uniformly after the proofs are
 // fixed, and only towards true.  The challenge is the caller's randomness (crypto/rand); 0 and 1 mod r are refused.  false does not
-// say which proof is bad: Groth16Verify on each locates it.  Needs Init.  Call sequence = tests/c/verify_batch.c.
+// say which proof is bad: Groth16VerifyEach says which.  Needs Init.  Call sequence = tests/c/verify_batch.c.
 func Groth16VerifyBatch(vk Groth16VkParts, proofs []Groth16BatchProof, challenge *big.Int, order *big.Int) (bool, error) {
 	ic, err := G1Points(vk.IC)
 	if err != nil {
@@ -106,4 +130,79 @@ func Groth16VerifyBatch(vk Groth16VkParts, proofs []Groth16BatchProof, challenge
 	runtime.KeepAlive(c)
 	runtime.KeepAlive(ch)
 	return ok == 1, err
+}
+
+// Groth16VerifyEach gives the verdict of Groth16Verify for EVERY proof of a batch under one verification key, on the device
+// (gs_groth16_verify_each): exact and deterministic, no challenge.  A proof with a point off its curve, a B outside the order-r
+// subgroup or (under strict mode) a non-canonical encoding gets false and is not an error; a key point off its curve makes every
+// verdict false.  Needs Init.  Call sequence = tests/c/verify_each.c.
+func Groth16VerifyEach(vk Groth16VkParts, proofs []Groth16BatchProof, order *big.Int) ([]bool, error) {
+	if len(proofs) == 0 {
+		return []bool{}, nil
+	}
+	ic, err := G1Points(vk.IC)
+	if err != nil {
+		return nil, err
+	}
+	g1, err := G1Points([][3]*big.Int{vk.G1Alpha})
+	if err != nil {
+		return nil, err
+	}
+	g2, err := G2Points([][3][2]*big.Int{vk.G2Beta, vk.G2Gamma, vk.G2Delta})
+	if err != nil {
+		return nil, err
+	}
+	npublic := len(proofs[0].PublicSignals)
+	as := make([][3]*big.Int, 0, len(proofs))
+	bs := make([][3][2]*big.Int, 0, len(proofs))
+	cs := make([][3]*big.Int, 0, len(proofs))
+	signals := make([]*big.Int, 0, len(proofs)*npublic)
+	for _, p := range proofs {
+		if len(p.PublicSignals) != npublic {
+			return nil, errors.New("gosnarkhip: every proof of one key has the same number of public signals")
+		}
+		as, bs, cs = append(as, p.PiA), append(bs, p.PiB), append(cs, p.PiC)
+		signals = append(signals, p.PublicSignals...)
+	}
+	a, err := G1Points(as)
+	if err != nil {
+		return nil, err
+	}
+	b, err := G2Points(bs)
+	if err != nil {
+		return nil, err
+	}
+	c, err := G1Points(cs)
+	if err != nil {
+		return nil, err
+	}
+	pub, err := Scalars(signals, order)
+	if err != nil {
+		return nil, err
+	}
+	if len(pub) == 0 {
+		pub = make([]uint64, 4)
+	}
+	oks := make([]C.int, len(proofs))
+	var nbad C.uint64_t
+	err = call(func() C.int {
+		return C.gs_groth16_verify_each(ptr(g1[0:]), ptr(g2[0:]), ptr(g2[24:]), ptr(g2[48:]), ptr(ic), C.size_t(len(vk.IC)),
+			ptr(pub), C.size_t(npublic), ptr(a), ptr(b), ptr(c), C.size_t(len(proofs)), &oks[0], &nbad)
+	})
+	runtime.KeepAlive(ic)
+	runtime.KeepAlive(g1)
+	runtime.KeepAlive(g2)
+	runtime.KeepAlive(pub)
+	runtime.KeepAlive(a)
+	runtime.KeepAlive(b)
+	runtime.KeepAlive(c)
+	runtime.KeepAlive(oks)
+	if err != nil {
+		return nil, err
+	}
+	out := make([]bool, len(proofs))
+	for i := range out {
+		out[i] = oks[i] == 1
+	}
+	return out, nil
 }

@@ -890,6 +890,46 @@ int gs_groth16_verify_batch(const uint64_t vk_g1_alpha[12], const uint64_t vk_g2
                             const uint64_t* public_signals /* nproofs x npublic x 4 */, size_t npublic,
                             const uint64_t* pi_a /* nproofs x 12 */, const uint64_t* pi_b /* nproofs x 24 */,
                             const uint64_t* pi_c /* nproofs x 12 */, size_t nproofs, const uint64_t challenge[4], int* ok);
+/* gs_groth16_verify_each: the verdict of gs_groth16_verify for EVERY proof of a batch under one key, on the device: ok_each[i] is exactly
+ * what gs_groth16_verify writes to *ok for proof i with its signals, in both settings of gs_verify_set_strict.  No challenge, no
+ * soundness caveat: the call is deterministic and never wrong.  *nbad (optional) = how many verdicts are 0.
+ * The arguments are gs_groth16_verify_batch's without the challenge, and so are the shape errors: null arguments GS_ERR_ARG,
+ * nic < npublic + 1 GS_ERR_SHAPE, under strict mode nic != npublic + 1 GS_ERR_SHAPE; in these cases nothing is written.  Not errors,
+ * but verdicts: a proof with a point off its curve gets 0 (the host tests the 3n points first, a few products each, and the point at
+ * infinity is uploaded in their place, because the uploads refuse a whole array for one such point); under strict mode a proof with a
+ * non-canonical coordinate or signal gets 0; a B on the twist outside the order-r subgroup gets 0 (a per-point flags kernel); a key
+ * point off its curve makes every verdict 0.  nproofs = 0 returns GS_OK with *nbad = 0 and needs no device; without a device every
+ * other call returns GS_ERR_NOT_INIT and writes nothing.  There is no host fallback.
+ * Per proof, one lane: vkx_i = IC_0 + sum_j pub_ij IC_{j+1} by a joint double-and-add (any 256-bit signal, the group law reduces it),
+ * then ONE Miller accumulator over the three pairs (-A_i, B_i), (vkx_i, gamma), (C_i, delta) -- the lines of gamma and delta are
+ * prepared once per call on the host and only evaluated per lane -- times the key's Miller value of e(alpha, beta), then the final
+ * exponentiation kernel of gs_pairing_each.  Memory: 135 KB of workspace per 64 proofs (see gs_pairing_each).  Blocking;
+ * gs_last_timing(): total_ms = device time, of which h2d_ms = signals, lines and the key value, poly_ms = membership, plan_ms = vkx,
+ * accumulate_ms = Miller loops, reduce_ms = final exponentiations.
+ * go-snark-study_amd/groth16.py (VerifyProofsEach), go/gosnarkhip/pairing_device.go (Groth16VerifyEach) and tests/c/verify_each.c. */
+int gs_groth16_verify_each(const uint64_t vk_g1_alpha[12], const uint64_t vk_g2_beta[24], const uint64_t vk_g2_gamma[24],
+                           const uint64_t vk_g2_delta[24], const uint64_t* vk_ic, size_t nic,
+                           const uint64_t* public_signals /* nproofs x npublic x 4 */, size_t npublic,
+                           const uint64_t* pi_a, const uint64_t* pi_b, const uint64_t* pi_c, size_t nproofs,
+                           int* ok_each /* nproofs */, uint64_t* nbad /* may be null */);
+/* gs_pairing_each: e(P[poff + i], Q[qoff + i]) for EVERY i < n, final exponentiation included, all of it on the device.  Value i
+ * goes to out_fq12 + 48 i in gs_pairing's encoding and is equal bit for bit to gs_pairing on that pair; is_one[i] = 1 iff it is 1.
+ * Either out-pointer may be NULL, not both.  A pair with an infinite member gives 1; n = 0 writes nothing (and still needs gs_init and
+ * valid handles, like gs_pairing_product).
+ * PRECONDITION (gs_pairing_product's): the Q are in G2, the subgroup of order r -- gs_g2_subgroup_check on the same handle.  For a
+ * point of the twist outside the subgroup the call still returns, with a value that means nothing.
+ * One lane per pair runs the Miller loop of gs_pairing_product and keeps its value (limb-major in a workspace of the one-wave
+ * workgroup, never in the 96-word encoding); a second kernel runs the final exponentiation per lane: the easy part with one
+ * inversion, three powers by the 63-bit BN parameter on cyclotomic squarings and the y0..y6 chain of the host verifier, the working
+ * value in LDS and five temporaries in the workspace.  No step branches on a value.
+ * Errors, locking and timing are gs_pairing_product's: a range beyond an array GS_ERR_SHAPE; a bad handle, a handle of the wrong kind
+ * or two null out-pointers GS_ERR_ARG; no device GS_ERR_NOT_INIT (nothing is written).  Blocking; gs_last_timing().total_ms = device
+ * time, of which accumulate_ms is the Miller kernel and reduce_ms the final exponentiation kernel.
+ * Memory: the call allocates 5 x 27 KB of workspace per 64 pairs plus 384 B per pair for the whole range at once (8.6 MB at 4096
+ * pairs, 2.2 GB at 2^20): a caller with millions of pairs passes them in windows (poff, qoff, n).
+ * go/gosnarkhip/pairing_device.go (PairingEach) and tests/c/pairing_each.c are the plain call. */
+int gs_pairing_each(gs_handle g1, size_t poff, gs_handle g2, size_t qoff, size_t n,
+                    uint64_t* out_fq12 /* n x 48, may be NULL */, int* is_one /* n, may be NULL, not both */);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

@@ -147,6 +147,35 @@ def g2_psi_constants():
     return (g2, g3), naf
 
 
+def frobenius_constants():
+    """gamma_k^i for k = 1, 2, 3 and i = 1..5, gamma_k = xi^((q^k - 1)/6), as a flat list of Fq coordinates: (c0, c1) per element
+    for k = 1 and 3, c0 alone for k = 2, whose elements are in Fq."""
+    def mul(a, b):
+        return ((a[0] * b[0] - a[1] * b[1]) % Q, (a[0] * b[1] + a[1] * b[0]) % Q)
+
+    def power(a, e):
+        r = (1, 0)
+        while e:
+            if e & 1:
+                r = mul(r, a)
+            a = mul(a, a)
+            e >>= 1
+        return r
+    out = []
+    for k in (1, 2, 3):
+        gamma = power((9, 1), (Q ** k - 1) // 6)
+        assert power(gamma, 6) == power((9, 1), Q ** k - 1)
+        g = (1, 0)
+        for _ in range(5):
+            g = mul(g, gamma)
+            if k == 2:
+                assert g[1] == 0                            # gamma_2 is in Fq: one row per power
+                out += [g[0]]
+            else:
+                out += [g[0], g[1]]
+    return out
+
+
 def main():
     out = "// GENERATED by tools/gen_constants.py -- do not edit.\n"
     out += "// BN128 constants (reference: bn128/bn128.go:40-83) in 9 x 29-bit limbs, Montgomery R = 2^261.\n"
@@ -183,6 +212,13 @@ def main():
     neg = sum(1 << i for i, d in enumerate(xnaf) if d < 0)
     out += "  static constexpr int kXNafDigits = %d;\n" % len(xnaf)
     out += "  static constexpr unsigned long long kXNafPos = 0x%016xULL, kXNafNeg = 0x%016xULL;\n" % (pos, neg)
+    # Frobenius of Fq12 (csrc/finalexp.h): gamma_k^i, i = 1..5, where gamma_k = w^(q^k - 1) = xi^((q^k - 1)/6); f^(q^k) multiplies the
+    # coefficient of w^i by gamma_k^i (pairing.h, twc()).  Rows 2 (i - 1) + c: coordinate c of gamma_1^i; rows 10 + (i - 1): gamma_2^i,
+    # which is in Fq; rows 15 + 2 (i - 1) + c: coordinate c of gamma_3^i
+    out += "  static __host__ __device__ __forceinline__ constexpr uint32_t frob(int row, int i) {\n    switch (row * 16 + i) {\n"
+    for row, v in enumerate(frobenius_constants()):
+        out += "      " + " ".join("case %d: return 0x%08xu;" % (row * 16 + i, l) for i, l in enumerate(limbs(v * MONT_R % Q))) + "\n"
+    out += "      default: return 0u;\n    }\n  }\n"
     out += "};\n\n}  // namespace gs\n"
     path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
                         "go-snark-study_amd", "csrc", "bn128_constants.h")
