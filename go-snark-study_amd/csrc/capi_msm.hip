@@ -162,8 +162,10 @@ int msm_begin(Ctx& c, Kind kind, gs_handle hb, size_t off, gs_handle hs, size_t 
     std::vector<MsmBase> bases{MsmBase{tab, off, b->buf.as<uint32_t>(), b->n}};
     if (!ticket_streams) c.next_tails((uint32_t)n);          // consecutive small MSMs reduce on alternating tail streams
     tail = ticket_streams ? plan_stream : c.tail_stream(0);
-    if constexpr (T::kWords == 8) msm_enqueue_g1(c, plan, bases, 8 * parity, 3 * parity, st->pend, tail);
-    else msm_enqueue_g2(c, plan, bases, 8 * parity + 4, 3 * parity, st->pend, tail);
+    // (a plain MSM: 256-thread accumulation groups whatever its size -- its plan is as long as its accumulation, acc_shape.h)
+    const int group = acc_group_policy(AccLaunch{st->g2, (uint32_t)n, !tabled, AccCaller::Msm, true, false, 1, false});
+    if constexpr (T::kWords == 8) msm_enqueue_g1(c, plan, bases, 8 * parity, 3 * parity, st->pend, group, tail);
+    else msm_enqueue_g2(c, plan, bases, 8 * parity + 4, 3 * parity, st->pend, group, tail);
   }
   GS_HIP(hipEventRecord(st->done, tail));
   sc->mark_read(plan_stream);                          // gs_scalars_update on this vector waits for the plan's digit pass

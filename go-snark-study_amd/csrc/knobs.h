@@ -33,6 +33,18 @@ inline long run_knob(const char* name, long dflt, long lo, long hi) {
   return knob_parse(name, lo, hi, 1, false, v) ? v : dflt;
 }
 
+// GS_ACC_GROUP_G1 / GS_ACC_GROUP_G2: threads per workgroup of k_bucket_accumulate<G1> / <G2>, 64, 128 or 256 (scheduling only: the
+// same additions in the same order whatever the size).  A set switch goes before acc_shape.h's policy for that curve in EVERY launch;
+// any other value is ignored.  The instrument of profiles/acc_group_ab.txt and tests/test_gpu_acc_group.py.
+inline long acc_group_env(const char* name) {           // the switch's value, or 0 = unset
+  const long v = run_knob(name, 0, 64, 256);
+  return (v == 64 || v == 128 || v == 256) ? v : 0;
+}
+inline long acc_group_forced(bool g2) {                 // read once per process
+  static const long g1_v = acc_group_env("GS_ACC_GROUP_G1"), g2_v = acc_group_env("GS_ACC_GROUP_G2");
+  return g2 ? g2_v : g1_v;
+}
+
 #ifdef GS_DEV_KNOBS
 inline bool dev_flag(const char* name) { return getenv(name) != nullptr; }
 inline long dev_knob(const char* name, long dflt, long lo, long hi, long multiple_of = 1, bool pow2 = false) {

@@ -3,6 +3,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "acc_shape.h"
 #include "ec.h"
 #include "runtime.h"
 #include "tables.h"
@@ -78,9 +79,13 @@ struct MsmPending {
   size_t stats_off = 0;
   std::shared_ptr<PhaseTimer> tacc, tker, tred;
 };
+// acc_group: threads per workgroup of the accumulation launch, 64 / 128 / 256 -- what acc_shape.h's policy says for this launch, which
+// only the caller can know (GS_ACC_GROUP_G1 / _G2, when set, go before it); msm_run_* are blocking calls and take 256
 // tail_stream: where the window merge / reduction / download go (nullptr = c.stream)
-void msm_enqueue_g1(Ctx& c, const MsmPlan& plan, const std::vector<MsmBase>& bases, int ws_base, int slot, MsmPending& p, hipStream_t tail_stream = nullptr);
-void msm_enqueue_g2(Ctx& c, const MsmPlan& plan, const std::vector<MsmBase>& bases, int ws_base, int slot, MsmPending& p, hipStream_t tail_stream = nullptr);
+void msm_enqueue_g1(Ctx& c, const MsmPlan& plan, const std::vector<MsmBase>& bases, int ws_base, int slot, MsmPending& p, int acc_group,
+                    hipStream_t tail_stream = nullptr);
+void msm_enqueue_g2(Ctx& c, const MsmPlan& plan, const std::vector<MsmBase>& bases, int ws_base, int slot, MsmPending& p, int acc_group,
+                    hipStream_t tail_stream = nullptr);
 void msm_book_timing(Ctx& c, const MsmPending& p);        // HIP event queries: call on the thread that drives the device
 void msm_finish_g1(Ctx& c, const MsmPending& p, std::vector<G1Xyzz>& out);   // pure host arithmetic (worker threads allowed)
 void msm_finish_g2(Ctx& c, const MsmPending& p, std::vector<G2Xyzz>& out);

@@ -228,8 +228,12 @@ void build_plan(Ctx& c, int slot, const uint32_t* scalars_dev, uint32_t n, MsmPl
 
 template <class T>
 static void msm_enqueue(Ctx& c, const MsmPlan& plan, const std::vector<MsmBase>& bases, int ws_base, int slot, MsmPending& p,
-                        hipStream_t tail_stream) {
+                        hipStream_t tail_stream, int acc_group) {
   const int njobs = (int)bases.size();
+  // threads per accumulation workgroup: the caller's (acc_shape.h), unless GS_ACC_GROUP_G1 / _G2 is set for this curve (knobs.h)
+  static_assert(kAccMaxBlock == kAccGroupDefault, "__launch_bounds__ of k_bucket_accumulate covers every size the policy may return");
+  if (const long forced = acc_group_forced(PointIO<T>::kAffineWords == 32)) acc_group = (int)forced;
+  if (!acc_group_valid(acc_group)) throw HipError{hipErrorInvalidValue, "accumulation workgroups have 64, 128 or 256 threads", __LINE__};
   p = MsmPending{};
   p.njobs = njobs; p.slot = slot; p.n = plan.n; p.g2 = PointIO<T>::kAffineWords == 32;
   p.c = plan.c; p.W = plan.W;
@@ -301,7 +305,7 @@ static void msm_enqueue(Ctx& c, const MsmPlan& plan, const std::vector<MsmBase>&
   p.tker = std::make_shared<PhaseTimer>(c.stream);
   // (round 6 tried one launch per base array instead of grid.y = njobs -- the proof stream runs at sclk 2.10 GHz where an MSM stream, one
   //  array per launch, runs at 2.31: no change in time or clock, profiles/r06_power_clock_streams.txt)
-  hipLaunchKernelGGL(k_bucket_accumulate<T>, dim3((plan.maxchunks + kAccBlock - 1) / kAccBlock, njobs), dim3(kAccBlock), 0, c.stream,
+  hipLaunchKernelGGL(k_bucket_accumulate<T>, dim3((plan.maxchunks + acc_group - 1) / acc_group, njobs), dim3(acc_group), 0, c.stream,
                      jobs, plan.offsets, plan.entries, plan.chunk_bucket, plan.nbuckets, plan.chunk);
   p.tker->stop();
   p.tacc->stop();
@@ -412,24 +416,24 @@ static void msm_finish(Ctx& c, const MsmPending& p, std::vector<Xyzz<T>>& out) {
   for (int j = 1; j < p.njobs; ++j) out[j] = fut[j - 1].get();
 }
 
-void msm_enqueue_g1(Ctx& c, const MsmPlan& plan, const std::vector<MsmBase>& bases, int ws_base, int slot, MsmPending& p, hipStream_t tail) {
-  msm_enqueue<FqTag>(c, plan, bases, ws_base, slot, p, tail);
+void msm_enqueue_g1(Ctx& c, const MsmPlan& plan, const std::vector<MsmBase>& bases, int ws_base, int slot, MsmPending& p, int acc_group, hipStream_t tail) {
+  msm_enqueue<FqTag>(c, plan, bases, ws_base, slot, p, tail, acc_group);
 }
-void msm_enqueue_g2(Ctx& c, const MsmPlan& plan, const std::vector<MsmBase>& bases, int ws_base, int slot, MsmPending& p, hipStream_t tail) {
-  msm_enqueue<Fq2Tag>(c, plan, bases, ws_base, slot, p, tail);
+void msm_enqueue_g2(Ctx& c, const MsmPlan& plan, const std::vector<MsmBase>& bases, int ws_base, int slot, MsmPending& p, int acc_group, hipStream_t tail) {
+  msm_enqueue<Fq2Tag>(c, plan, bases, ws_base, slot, p, tail, acc_group);
 }
 void msm_finish_g1(Ctx& c, const MsmPending& p, std::vector<G1Xyzz>& out) { msm_finish<FqTag>(c, p, out); }
 void msm_finish_g2(Ctx& c, const MsmPending& p, std::vector<G2Xyzz>& out) { msm_finish<Fq2Tag>(c, p, out); }
 void msm_run_g1(Ctx& c, const MsmPlan& plan, const std::vector<MsmBase>& bases, std::vector<G1Xyzz>& out) {
   MsmPending p;
-  msm_enqueue<FqTag>(c, plan, bases, 8 * c.blocking_slot(), 3 * c.blocking_slot(), p, nullptr);
+  msm_enqueue<FqTag>(c, plan, bases, 8 * c.blocking_slot(), 3 * c.blocking_slot(), p, nullptr, kAccGroupDefault);   // a blocking call
   GS_HIP(hipStreamSynchronize(c.stream));
   msm_book_timing(c, p);
   msm_finish<FqTag>(c, p, out);
 }
 void msm_run_g2(Ctx& c, const MsmPlan& plan, const std::vector<MsmBase>& bases, std::vector<G2Xyzz>& out) {
   MsmPending p;
-  msm_enqueue<Fq2Tag>(c, plan, bases, 8 * c.blocking_slot() + 4, 3 * c.blocking_slot(), p, nullptr);
+  msm_enqueue<Fq2Tag>(c, plan, bases, 8 * c.blocking_slot() + 4, 3 * c.blocking_slot(), p, nullptr, kAccGroupDefault);
   GS_HIP(hipStreamSynchronize(c.stream));
   msm_book_timing(c, p);
   msm_finish<Fq2Tag>(c, p, out);

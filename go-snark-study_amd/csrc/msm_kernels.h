@@ -531,15 +531,15 @@ template <> struct AccTuning<FqTag> { static constexpr int kMinWaves = GS_G1_WAV
 #endif
 template <> struct AccTuning<Fq2Tag> { static constexpr int kMinWaves = GS_G2_WAVES; static constexpr bool kRegisterPrefetch = GS_G2_PREFETCH != 0; static constexpr bool kTouch = GS_G2_TOUCH != 0; };
 
-// Threads per workgroup of the accumulation kernels.  The kernel uses no LDS and no barrier (one thread per chunk), so the workgroup is only
-// the unit the dispatcher places: a 256-thread group needs a free wave slot on all four SIMDs of a CU at once, a 64-thread group refills
-// any slot the moment it frees (round 5's counters showed 2.65 of 3 wave slots occupied on average).
-#ifndef GS_ACC_BLOCK
-#define GS_ACC_BLOCK 256
-#endif
-constexpr int kAccBlock = GS_ACC_BLOCK;
+// Threads per workgroup of the accumulation kernels: a LAUNCH parameter, 64, 128 or 256 (acc_shape.h decides per launch on the host,
+// msm.hip's msm_enqueue computes grid.x from it).  The kernel uses no LDS and no barrier and indexes with blockIdx.x * blockDim.x +
+// threadIdx.x (one thread per chunk), so the workgroup is only the unit the dispatcher places: a 256-thread group needs a free wave
+// slot on all four SIMDs of a CU at once, a 64-thread group refills any slot the moment it frees (round 5's counters showed 2.65 of
+// 3 wave slots occupied on average with 256).  __launch_bounds__ names the largest size a launch may ask for, together with the waves
+// per SIMD: register allocation is the same for every size.
+constexpr int kAccMaxBlock = 256;
 template <class T>
-__global__ void __launch_bounds__(kAccBlock, AccTuning<T>::kMinWaves) k_bucket_accumulate(AccJobs jobs, const uint32_t* __restrict__ offsets,
+__global__ void __launch_bounds__(kAccMaxBlock, AccTuning<T>::kMinWaves) k_bucket_accumulate(AccJobs jobs, const uint32_t* __restrict__ offsets,
                                                             const uint32_t* __restrict__ entries,
                                                             const uint32_t* __restrict__ chunk_bucket, uint32_t nbuckets, uint32_t chunk) {
   constexpr int pw = PointIO<T>::kXyzzWords;

@@ -133,6 +133,7 @@ int on_devices(int n, F&& f, const char* what) {
   std::vector<std::thread> th;
   for (int d = 0; d < n; ++d)
     th.emplace_back([&, d] {
+      multi_device_call() = true;          // (a fresh thread's own flag: proofs begun from here keep 256-thread accumulation groups)
       res[d].rc = f(d);
       if (res[d].rc != GS_OK) res[d].msg = gs_last_error();
     });

@@ -283,6 +283,13 @@ int proof_enqueue(Ctx& c, ProverKey* pk, DevVec w, const HSource& src, const Sha
   const size_t nterms_w = whi - wlo;
   st.split_b = pk->b_index.p != nullptr && nterms_w >= 4096 && !plan_partitions_first(cw) && pk->b_finite * 100 < (size_t)split_b_percent() * pk->n_w;
   MsmPlan plan_b;
+  const bool no_poly = route == HRoute::Quot && !r1cs;           // nothing between px and plan(h): no polynomial phase to time, or to starve
+  // threads per workgroup of this proof's accumulation launches (acc_shape.h): one-wave groups only where nothing of the proof's own
+  // side chain is long enough to stall the main stream when the accumulations take every wave slot
+  const bool multi_device = shard.count > 1 || multi_device_call();
+  auto acc_group = [&](bool g2, const MsmPlan& plan, int njobs) {
+    return acc_group_policy(AccLaunch{g2, plan.n, plan.table_free, AccCaller::Proof, pipelined, no_poly, njobs, multi_device});
+  };
   {                                                              // aux 1 (or aux 2, proof_streams): plan(w) [, the plan over the listed terms for B first: G2 starts the proof]
     StreamScope sc(c, ps.planw);
     if (st.split_b) {
@@ -309,16 +316,17 @@ int proof_enqueue(Ctx& c, ProverKey* pk, DevVec w, const HSource& src, const Sha
     // their first npublic+1 points forced to infinity at key creation, so they equal a full-range MSM sharing w's plan.
     // G2 first: its accumulation (2 waves/SIMD, 256 VGPRs) is the one a foreign wave hurts most, and its long
     // combine/reduce tail then hides behind the G1 accumulations.
-    msm_enqueue_g2(c, st.split_b ? plan_b : plan_w, {base_w(pk->g2w)}, ws + pk->ws_g2, pin + 1, st.pend_g2w, ps.tail_g2);
+    const MsmPlan& plan_g2 = st.split_b ? plan_b : plan_w;
+    msm_enqueue_g2(c, plan_g2, {base_w(pk->g2w)}, ws + pk->ws_g2, pin + 1, st.pend_g2w, acc_group(true, plan_g2, 1), ps.tail_g2);
     GS_HIP(hipEventRecord(st.done_g2, ps.tail_g2));
     std::vector<MsmBase> group;                                  // the G1 arrays over plan(w): all of them, or all but the B array
     for (int i = 0; i < ng; ++i) if (!(st.split_b && i == bg)) group.push_back(base_w(pk->g1w[i]));
     if (st.split_b) {
-      msm_enqueue_g1(c, plan_b, {base_w(pk->g1w[bg])}, ws + pk->ws_b, 3 * Ctx::kSlots + parity, st.pend_g1b, ps.tail_g1);
+      msm_enqueue_g1(c, plan_b, {base_w(pk->g1w[bg])}, ws + pk->ws_b, 3 * Ctx::kSlots + parity, st.pend_g1b, acc_group(false, plan_b, 1), ps.tail_g1);
       GS_HIP(hipEventRecord(st.done_g1b, ps.tail_g1));
       GS_HIP(hipStreamWaitEvent(c.stream, st.planw, 0));
     }
-    msm_enqueue_g1(c, plan_w, group, ws + 0, pin + 0, st.pend_g1w, ps.tail_g1);
+    msm_enqueue_g1(c, plan_w, group, ws + 0, pin + 0, st.pend_g1w, acc_group(false, plan_w, (int)group.size()), ps.tail_g1);
     GS_HIP(hipEventRecord(st.done_g1w, ps.tail_g1));
   };
   // (Starting H(x) and plan(h) of a lone proof beside plan(w) on another stream instead of behind it was tried: the blocking proof
@@ -331,7 +339,6 @@ int proof_enqueue(Ctx& c, ProverKey* pk, DevVec w, const HSource& src, const Sha
       th.stop();
       c.timing.h2d_ms += th.ms();
     }
-    const bool no_poly = route == HRoute::Quot && !r1cs;                         // nothing between px and plan(h): no polynomial phase to time
     if (!no_poly) st.tpoly = std::make_shared<PhaseTimer>(c.stream);
     uint32_t* hx = hxbuf.as<uint32_t>();
     const size_t dz = pk->nz - 1;
@@ -367,7 +374,7 @@ int proof_enqueue(Ctx& c, ProverKey* pk, DevVec w, const HSource& src, const Sha
     // a lone proof finishes soonest with the last tail right behind its accumulation; in a pipeline that tail must not sit
     // in front of the next proof's accumulations
     msm_enqueue_g1(c, plan_h, {MsmBase{&harr.table, hbase, harr.pts.as<uint32_t>(), n_harr}}, ws + pk->ws_h, pin + 2, st.pend_h,
-                   pipelined ? ps.tail_g1 : nullptr);                           // groth16.go:269-271, snark.go:284-286
+                   acc_group(false, plan_h, 1), pipelined ? ps.tail_g1 : nullptr);                           // groth16.go:269-271, snark.go:284-286
     GS_HIP(hipEventRecord(st.done_h, pipelined ? ps.tail_g1 : c.main_stream));
   }
   st.total->stop();

@@ -340,6 +340,12 @@ inline int& current_logical() {
   static thread_local int v = 0;
   return v;
 }
+// true on the host threads a multi-device entry point (multi.hip, on_devices) drives its logical devices with: what such a thread
+// enqueues shares its host, and often its physical device, with the other devices' work (acc_shape.h asks)
+inline bool& multi_device_call() {
+  static thread_local bool v = false;
+  return v;
+}
 // the context of a logical device, or null; *count (optional) = number of logical devices
 inline std::shared_ptr<Ctx> ctx_ref(int logical, size_t* count = nullptr) {
   Registry& r = registry();
