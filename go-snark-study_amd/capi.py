@@ -227,6 +227,8 @@ _SIGS = {
     "gs_pairing_product": [Handle, ctypes.c_size_t, Handle, ctypes.c_size_t, ctypes.c_size_t, u64p, intp],
     "gs_groth16_verify_each": [u64p, u64p, u64p, u64p, u64p, ctypes.c_size_t, u64p, ctypes.c_size_t, u64p, u64p, u64p, ctypes.c_size_t, intp,
                                ctypes.POINTER(ctypes.c_uint64)],
+    "gs_pinocchio_verify_each": [u64p, u64p, u64p, u64p, u64p, u64p, u64p, u64p, ctypes.c_size_t, u64p, ctypes.c_size_t, u64p, ctypes.c_size_t,
+                                 intp, intp, ctypes.POINTER(ctypes.c_uint64)],
     "gs_pairing_each": [Handle, ctypes.c_size_t, Handle, ctypes.c_size_t, ctypes.c_size_t, u64p, intp],
     "gs_groth16_verify_batch": [u64p, u64p, u64p, u64p, u64p, ctypes.c_size_t, u64p, ctypes.c_size_t, u64p, u64p, u64p, ctypes.c_size_t, u64p, intp],
 }

@@ -200,6 +200,51 @@ GS_HD void miller_loop_groth16(S& f, const Affine<FqTag>& p1_in, const Affine<Fq
   }
 }
 
+// ---- up to three pairs, ALL of their lines prepared -------------------------------------------------------------------------------
+// f <- the Miller value of e(P1, Q1) e(P2, Q2) e(P3, Q3) where every Q is the same in every lane (key points and the G2 generator of
+// a Pinocchio key): no G2 arithmetic and no running point, a lane only evaluates the three prepared lists at its own P.  The steps are
+// taken in the order prepare_g2_lines writes them: per bit of 6x + 2 the tangent, then the chord if the bit is set; then the two
+// Frobenius chords.  One squaring of f per bit, shared by the pairs.  A pair whose P is infinite or whose skip flag is set (an
+// infinite or absent Q) contributes one by line_or_one.
+template <class S, class L>
+GS_HD void miller_loop_prepared(S& f, const Affine<FqTag>& p1, bool skip_q1, const L& q1, const Affine<FqTag>& p2, bool skip_q2, const L& q2,
+                                const Affine<FqTag>& p3, bool skip_q3, const L& q3) {
+  const bool skip1 = skip_q1 | is_inf(p1), skip2 = skip_q2 | is_inf(p2), skip3 = skip_q3 | is_inf(p3);
+  const Fe<ModQ, 2> nxp1 = neg(p1.x), nxp2 = neg(p2.x), nxp3 = neg(p3.x);
+  f12_set_one(f);
+  int k = 0;
+#pragma unroll 1
+  for (int i = 63; i >= -2; --i) {
+#pragma unroll 1
+    for (int phase = 0; phase < 2; ++phase) {
+      if (phase == 0) {
+        if (i < 0) continue;
+        f12_sqr(f);
+      } else {
+        if (i >= 0 && !((kAteLoopLow >> i) & 1ull)) continue;
+      }
+      Line l = line_or_one(skip1, prepared_line_at(q1, k, nxp1, p1.y));
+      f12_mul_line(f, l.a, l.b, l.c);
+      l = line_or_one(skip2, prepared_line_at(q2, k, nxp2, p2.y));
+      f12_mul_line(f, l.a, l.b, l.c);
+      l = line_or_one(skip3, prepared_line_at(q3, k, nxp3, p3.y));
+      f12_mul_line(f, l.a, l.b, l.c);
+      ++k;
+    }
+  }
+}
+
+// the two sums the Pinocchio equations 4 and 5 share: vkx + A and vkx + A + C, by the complete formulas of ec.h (A may be vkx, -vkx or
+// infinite, and so may C against the first sum)
+GS_HD void pinocchio_sums(const Affine<FqTag>& vkx, const Affine<FqTag>& a, const Affine<FqTag>& c, Affine<FqTag>& xa, Affine<FqTag>& xac) {
+  Xyzz<FqTag> acc = xyzz_inf<FqTag>();
+  xyzz_madd(acc, vkx);
+  xyzz_madd(acc, a);
+  xa = xyzz_to_affine(acc);
+  xyzz_madd(acc, c);
+  xac = xyzz_to_affine(acc);
+}
+
 // vkx = IC_0 + sum_j pub_j IC_{j+1} (verify.hip, accumulate_ic): a joint double-and-add over the npublic points, ONE doubling chain of
 // 256 steps and an addition per set bit per signal, complete formulas (ec.h), so any 256-bit scalar is taken as it is -- the group law
 // reduces it -- and an addition that meets a doubling or the inverse is right.  ic(j) gives the affine IC_j, bit(j, b) bit b of signal j.

@@ -316,6 +316,141 @@ int verify_each_impl(Ctx& c, const char* fn, gs_handle ha, gs_handle hb, gs_hand
   return GS_OK;
 }
 
+// ---- a verdict per Pinocchio proof: gs_pinocchio_verify_each (verify.hip) -------------------------------------------------------
+// The five equations of snark.VerifyProof as products equal to one.  Six G2 points are the same in every lane and arrive as prepared
+// lists, in this order:
+enum { kListVka = 0, kListVkc, kListVkz, kListG2Kbg, kListG2Kg, kListGen, kPinLists };
+constexpr int kPinEquations = 5;
+// the proof's seven G1 points are one array of 7 slabs of n points:
+enum { kPtA = 0, kPtAp, kPtBp, kPtC, kPtCp, kPtH, kPtKp, kPinG1 };
+
+// lane i: vkx_i (groth16_vkx), then vkx_i + PiA_i and that sum + PiC_i, affine, for equations 4 and 5
+__global__ void __launch_bounds__(kPairBlock) k_pinocchio_points(const uint32_t* __restrict__ ic, const uint32_t* __restrict__ pub, uint32_t npublic,
+                                                                 const uint32_t* __restrict__ g1, uint32_t n, uint32_t* __restrict__ xa_out,
+                                                                 uint32_t* __restrict__ xac_out) {
+  constexpr int kAw = PointIO<FqTag>::kAffineWords;
+  const size_t i = (size_t)blockIdx.x * kPairBlock + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t* mine = pub + i * npublic * 8;
+  const auto point = [&](int j) { return PointIO<FqTag>::load_affine(ic + (size_t)j * kAw); };
+  const auto bit = [&](int j, int b) { return ((mine[(size_t)j * 8 + (b >> 5)] >> (b & 31)) & 1u) != 0; };
+  const Affine<FqTag> vkx = groth16_vkx(point, bit, (int)npublic);
+  Affine<FqTag> xa, xac;
+  pinocchio_sums(vkx, PointIO<FqTag>::load_affine(g1 + ((size_t)kPtA * n + i) * kAw), PointIO<FqTag>::load_affine(g1 + ((size_t)kPtC * n + i) * kAw), xa, xac);
+  PointIO<FqTag>::store_affine(xa_out + i * kAw, xa);
+  PointIO<FqTag>::store_affine(xac_out + i * kAw, xac);
+}
+
+// workgroup (x, y): the Miller value of equation y + 1 for the 64 proofs of block x, into slot 0 of workspace y * gridDim.x + x.
+//   1  (PiA, Vka) (-PiAp, g2)                         prepared lines only
+//   2  (Vkb, PiB) (-PiBp, g2)                         PiB is the live pair
+//   3  (PiC, Vkc) (-PiCp, g2)                         prepared lines only
+//   4  (vkx + PiA, PiB) (-PiH, Vkz) (-PiC, g2)
+//   5  (G1Kbg, PiB) (vkx + PiA + PiC, G2Kbg) (-PiKp, G2Kg)
+// The equation is blockIdx.y, so every lane of a workgroup takes the same loop.  key_g1 = Vkb, G1Kbg; skip bit l = list l is absent
+// (an infinite key point).
+__global__ void __launch_bounds__(kPairBlock) k_miller_pinocchio(const uint32_t* __restrict__ g1, const uint32_t* __restrict__ b,
+                                                                 const uint32_t* __restrict__ xa, const uint32_t* __restrict__ xac,
+                                                                 const uint32_t* __restrict__ key_g1, uint32_t n, const uint32_t* __restrict__ lines,
+                                                                 uint32_t skip_mask, uint32_t* __restrict__ workspace) {
+  __shared__ uint32_t lds[kF12Limbs][kPairBlock];
+  constexpr int kA1 = PointIO<FqTag>::kAffineWords, kA2 = PointIO<Fq2Tag>::kAffineWords;
+  const int eq = blockIdx.y;
+  const size_t i = (size_t)blockIdx.x * kPairBlock + threadIdx.x;
+  const size_t at = i < n ? i : 0;                                     // lanes past the end run proof 0 and are not read back
+  const auto slab = [&](int which) { return g1 + ((size_t)which * n + at) * kA1; };
+  // where the three G1 points come from, which of them is negated, and the lists of the second and third pair (the first pair's
+  // list for the prepared loop): the same for every lane
+  const uint32_t *s1, *s2, *s3 = slab(kPtA);
+  int l1 = kListGen, l2 = kListGen, l3 = kListGen;
+  bool neg2 = true, no3 = false;
+  switch (eq) {
+    case 0: s1 = slab(kPtA); l1 = kListVka; s2 = slab(kPtAp); no3 = true; break;
+    case 1: s1 = key_g1; s2 = slab(kPtBp); no3 = true; break;
+    case 2: s1 = slab(kPtC); l1 = kListVkc; s2 = slab(kPtCp); no3 = true; break;
+    case 3: s1 = xa + at * kA1; s2 = slab(kPtH); l2 = kListVkz; s3 = slab(kPtC); break;
+    default: s1 = key_g1 + kA1; s2 = xac + at * kA1; l2 = kListG2Kbg; neg2 = false; s3 = slab(kPtKp); l3 = kListG2Kg; break;
+  }
+  const Affine<FqTag> p1 = PointIO<FqTag>::load_affine(s1);
+  Affine<FqTag> p2 = PointIO<FqTag>::load_affine(s2), p3 = PointIO<FqTag>::load_affine(s3);
+  if (neg2) p2.y = canon(neg(p2.y));                                   // infinity (0, 0) stays infinity
+  p3.y = canon(neg(p3.y));
+  const auto list = [&](int l) { return PreparedLines{lines + (size_t)l * kPreparedSteps * kLineWords}; };
+  const auto absent = [&](int l) { return ((skip_mask >> l) & 1u) != 0; };
+  LdsF12 f{&lds[0][threadIdx.x]};
+  if (eq == 0 || eq == 2) {
+    miller_loop_prepared(f, p1, absent(l1), list(l1), p2, absent(l2), list(l2), p3, true, list(l3));
+  } else {
+    const Affine<Fq2Tag> q1 = PointIO<Fq2Tag>::load_affine(b + at * kA2);
+    miller_loop_groth16(f, p1, q1, p2, absent(l2), list(l2), p3, no3 || absent(l3), list(l3));
+  }
+  GlbF12 out{workspace + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * kWorkspaceWords + threadIdx.x};
+  f12_copy(out, f);
+}
+
+// member[i] = is PiB_i in G2, one[e * n + i] = is the exponentiated value of equation e + 1 of proof i one
+int pinocchio_each_impl(Ctx& c, const char* fn, gs_handle hg1, gs_handle hb, gs_handle hic, gs_handle hkey, const uint64_t* pub, size_t npublic, size_t n,
+                        const uint64_t* lines_std_host, unsigned skip_mask, int* member, int* one) {
+  Bases* gs1 = c.get<Bases>(hg1, Kind::G1Bases);
+  Bases* bs = c.get<Bases>(hb, Kind::G2Bases);
+  Bases* ics = c.get<Bases>(hic, Kind::G1Bases);
+  Bases* keys = c.get<Bases>(hkey, Kind::G1Bases);
+  if (!gs1 || !bs || !ics || !keys) return fail(GS_ERR_ARG, "%s: bad base-array handle", fn);
+  if (!n || n >= 0xffffffffull / (kPinEquations * 2) || npublic >= 0xffffffffull) return fail(GS_ERR_SHAPE, "%s: %zu proofs, indices are 32 bits", fn, n);
+  if (gs1->n != kPinG1 * n || bs->n != n || keys->n != 2 || ics->n < npublic + 1) return fail(GS_ERR_SHAPE, "%s: the arrays do not hold %zu proofs", fn, n);
+  c.drain();
+  constexpr size_t kLineStd = (size_t)kPreparedSteps * 16;              // u64 words of one prepared list
+  constexpr int kAw = PointIO<FqTag>::kAffineWords;
+  const size_t count = (n + kPairBlock - 1) / kPairBlock;
+  const size_t groups = kPinEquations * count, lanes = groups * kPairBlock;
+  const size_t pub_bytes = n * npublic * 32;
+  DevBuf ws(groups * kWorkspaceWords * 4), vals(lanes * kF12Words * 4), flags(lanes * 4), members(n * 4), xa(n * kAw * 4), xac(n * kAw * 4);
+  DevBuf dpub(pub_bytes ? pub_bytes : 32), lines_std(kPinLists * kLineStd * 8), lines((size_t)kPinLists * kPreparedSteps * kLineWords * 4);
+  PhaseTimer t(c.stream), tu(c.stream);
+  if (pub_bytes) GS_HIP(hipMemcpyAsync(dpub.p, pub, pub_bytes, hipMemcpyHostToDevice, c.stream));
+  GS_HIP(hipMemcpyAsync(lines_std.p, lines_std_host, kPinLists * kLineStd * 8, hipMemcpyHostToDevice, c.stream));
+  const uint32_t nfe = kPinLists * kPreparedSteps * 4;
+  hipLaunchKernelGGL(k_std_to_limbs, dim3((nfe + 63) / 64), dim3(64), 0, c.stream, lines_std.as<uint32_t>(), nfe, lines.as<uint32_t>());
+  GS_HIP(hipGetLastError());
+  tu.stop();
+  PhaseTimer tmem(c.stream);
+  hipLaunchKernelGGL(k_g2_member_flags, dim3((unsigned)count), dim3(kPairBlock), 0, c.stream, bs->buf.as<uint32_t>(), (uint32_t)n, members.as<uint32_t>());
+  GS_HIP(hipGetLastError());
+  tmem.stop();
+  PhaseTimer tv(c.stream);
+  hipLaunchKernelGGL(k_pinocchio_points, dim3((unsigned)count), dim3(kPairBlock), 0, c.stream, ics->buf.as<uint32_t>(), dpub.as<uint32_t>(),
+                     (uint32_t)npublic, gs1->buf.as<uint32_t>(), (uint32_t)n, xa.as<uint32_t>(), xac.as<uint32_t>());
+  GS_HIP(hipGetLastError());
+  tv.stop();
+  PhaseTimer tm(c.stream);
+  hipLaunchKernelGGL(k_miller_pinocchio, dim3((unsigned)count, kPinEquations), dim3(kPairBlock), 0, c.stream, gs1->buf.as<uint32_t>(),
+                     bs->buf.as<uint32_t>(), xa.as<uint32_t>(), xac.as<uint32_t>(), keys->buf.as<uint32_t>(), (uint32_t)n, lines.as<uint32_t>(),
+                     (uint32_t)skip_mask, ws.as<uint32_t>());
+  GS_HIP(hipGetLastError());
+  tm.stop();
+  PhaseTimer tf(c.stream);
+  hipLaunchKernelGGL(k_final_exp, dim3((unsigned)groups), dim3(kPairBlock), 0, c.stream, ws.as<uint32_t>(), (uint32_t)lanes, vals.as<uint32_t>(),
+                     flags.as<uint32_t>());
+  GS_HIP(hipGetLastError());
+  tf.stop();
+  t.stop();
+  std::vector<uint32_t> hf(lanes), hm(n);
+  GS_HIP(hipMemcpyAsync(hf.data(), flags.p, lanes * 4, hipMemcpyDeviceToHost, c.stream));
+  GS_HIP(hipMemcpyAsync(hm.data(), members.p, n * 4, hipMemcpyDeviceToHost, c.stream));
+  GS_HIP(hipStreamSynchronize(c.stream));
+  for (size_t i = 0; i < n; ++i) member[i] = (int)hm[i];
+  for (size_t e = 0; e < (size_t)kPinEquations; ++e)                    // equation e's lanes are padded to whole workgroups
+    for (size_t i = 0; i < n; ++i) one[e * n + i] = (int)hf[e * count * kPairBlock + i];
+  reset_timing(c);
+  c.timing.total_ms = t.ms();
+  c.timing.h2d_ms = tu.ms();                                           // signals and the six prepared lists
+  c.timing.poly_ms = tmem.ms();                                        // membership of the PiB_i
+  c.timing.plan_ms = tv.ms();                                          // vkx and the two sums
+  c.timing.accumulate_ms = tm.ms();                                    // the Miller loops
+  c.timing.reduce_ms = tf.ms();                                        // the final exponentiations
+  return GS_OK;
+}
+
 pairing::Fp12 host_f12(const uint64_t* w) {
   using namespace gs::pairing;
   Fp12 f;
@@ -390,6 +525,14 @@ int groth16_verify_each_device(const char* fn, gs_handle ha, gs_handle hb, gs_ha
                                const uint64_t* gamma_lines, const uint64_t* delta_lines, const uint64_t* ab, int* member, int* is_one) {
   return guarded([&](Ctx& ctx) -> int { return verify_each_impl(ctx, fn, ha, hb, hc, hic, pub, npublic, n, gamma_lines, delta_lines, ab, member, is_one); },
                  true, false, ha);
+}
+// for gs_pinocchio_verify_each (verify.hip): per proof, is PiB in G2 (member[i]) and is the exponentiated product of equation e + 1 one
+// (one[e * n + i]).  g1 holds the proofs' seven G1 points as slabs of n (PiA, PiAp, PiBp, PiC, PiCp, PiH, PiKp), key = Vkb, G1Kbg;
+// lines = the six prepared lists (Vka, Vkc, Vkz, G2Kbg, G2Kg, the generator; pairing.h), zeros for a list whose bit in skip_mask is set.
+int pinocchio_verify_each_device(const char* fn, gs_handle g1, gs_handle hb, gs_handle hic, gs_handle key, const uint64_t* pub, size_t npublic, size_t n,
+                                 const uint64_t* lines, unsigned skip_mask, int* member, int* one) {
+  return guarded([&](Ctx& ctx) -> int { return pinocchio_each_impl(ctx, fn, g1, hb, hic, key, pub, npublic, n, lines, skip_mask, member, one); }, true,
+                 false, g1);
 }
 void f12_words(const pairing::Fp12& f, uint64_t* out) { host_f12_to_std(f, out); }
 

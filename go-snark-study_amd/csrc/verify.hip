@@ -203,6 +203,8 @@ int miller_product(const char* fn, gs_handle g1, size_t poff, gs_handle g2, size
 int groth16_verify_each_device(const char* fn, gs_handle ha, gs_handle hb, gs_handle hc, gs_handle hic, const uint64_t* pub, size_t npublic, size_t n,
                                const uint64_t* gamma_lines, const uint64_t* delta_lines, const uint64_t* ab, int* member, int* is_one);
 void f12_words(const pairing::Fp12& f, uint64_t* out);
+int pinocchio_verify_each_device(const char* fn, gs_handle g1, gs_handle hb, gs_handle hic, gs_handle key, const uint64_t* pub, size_t npublic, size_t n,
+                                 const uint64_t* lines, unsigned skip_mask, int* member, int* one);
 }
 
 namespace {
@@ -443,6 +445,131 @@ int gs_groth16_verify_each(const uint64_t vk_g1_alpha[12], const uint64_t vk_g2_
     uint64_t count = 0;
     for (size_t i = 0; i < n; ++i) {
       ok_each[i] = (!bad[i] && member[i] && one[i]) ? 1 : 0;
+      count += ok_each[i] ? 0 : 1;
+    }
+    if (nbad) *nbad = count;
+    return GS_OK;
+  });
+}
+
+// gs_pinocchio_verify_each (include/gosnark_hip.h): gs_pinocchio_verify's verdict and first failing equation for every proof of a batch,
+// on the device.  The host does what is O(1) per call or a few products per proof: the key (curve tests, the six prepared lists) and the
+// screening of the 8n proof points, because the uploads refuse a whole array for one point off its curve: the point at infinity travels in
+// its place and the equations that use it are marked failed.  The device answers "is equation e of proof i one" and "is PiB_i in G2";
+// the fold below puts them in the reference's order.
+int gs_pinocchio_verify_each(const uint64_t vka[24], const uint64_t vkb[12], const uint64_t vkc[24], const uint64_t g1kbg[12], const uint64_t g2kbg[24],
+                             const uint64_t g2kg[24], const uint64_t vkz[24], const uint64_t* vk_ic, size_t nic, const uint64_t* public_signals,
+                             size_t npublic, const uint64_t* proofs, size_t nproofs, int* ok_each, int* failed_each, uint64_t* nbad) {
+  return host_guarded([&]() -> int {
+    const char* fn = "gs_pinocchio_verify_each";
+    const size_t n = nproofs;
+    if (!vka || !vkb || !vkc || !g1kbg || !g2kbg || !g2kg || !vkz || !vk_ic || (n && (!proofs || !ok_each)) || (n && npublic && !public_signals))
+      return fail(GS_ERR_ARG, "%s: null argument", fn);
+    if (nic < npublic + 1) return fail(GS_ERR_SHAPE, "%s: %zu public signals need %zu IC points, vk has %zu", fn, npublic, npublic + 1, nic);
+    const bool strict = g_strict.load() != 0;
+    if (strict && nic != npublic + 1)
+      return fail(GS_ERR_SHAPE, "%s (strict): vk has %zu IC points, so exactly %zu public signals are required (got %zu)", fn, nic, nic - 1, npublic);
+    if (!n) {
+      if (nbad) *nbad = 0;
+      return GS_OK;
+    }
+    const auto eq = [](int e) { return 1u << e; };                      // bit e = equation e (1..5) does not hold
+    // the IC points go up first: without a device this is where the call ends, before any work and with nothing written.  The host
+    // verifier sums them unchecked and then finds vkx + PiA off the curve: an IC point off its curve that a proof uses (IC_0, or
+    // IC_{j+1} with a nonzero signal j) fails that proof's equations 4 and 5; infinity travels in its place.
+    HandleBag bag;
+    gs_handle *hg1 = &bag.hs[0], *hb = &bag.hs[1], *hic = &bag.hs[2], *hkey = &bag.hs[3];
+    std::vector<uint64_t> ic(vk_ic, vk_ic + 12 * nic);
+    std::vector<char> ic_bad(npublic + 1, 0);
+    for (size_t j = 0; j <= npublic; ++j)
+      if (!g1_on_curve(g1_from_jacobian_std(vk_ic + 12 * j))) {
+        ic_bad[j] = 1;
+        memset(ic.data() + 12 * j, 0, 96);
+      }
+    for (size_t j = npublic + 1; j < nic; ++j)                          // not used by any proof
+      if (!g1_on_curve(g1_from_jacobian_std(vk_ic + 12 * j))) memset(ic.data() + 12 * j, 0, 96);
+    int rc = gs_g1_upload(ic.data(), nic, hic);
+    if (rc != GS_OK) return rc;
+    // the key: a point off its curve fails every equation that uses it, for every proof.  A G2 point with a degenerate step (on the
+    // twist, of small order) fails them where its partner in G1 is finite, as multi_miller_loop does; its list is left out.
+    unsigned key_fail = 0, skip_mask = 0;
+    uint64_t key_g1[24];
+    memcpy(key_g1, vkb, 96);
+    memcpy(key_g1 + 12, g1kbg, 96);
+    if (!g1_on_curve(g1_from_jacobian_std(vkb))) { key_fail |= eq(2); memset(key_g1, 0, 96); }
+    if (!g1_on_curve(g1_from_jacobian_std(g1kbg))) { key_fail |= eq(5); memset(key_g1 + 12, 0, 96); }
+    constexpr size_t kLineStd = (size_t)kPreparedSteps * 16;
+    enum { kVka = 0, kVkc, kVkz, kG2Kbg, kG2Kg, kGen, kLists };        // pairing_device.hip, the order of the lists
+    const uint64_t* key_g2[kLists] = {vka, vkc, vkz, g2kbg, g2kg, kG2Gen};
+    const unsigned uses[kLists] = {eq(1), eq(3), eq(4), eq(5), eq(5), 0};
+    bool degenerate[kLists] = {false, false, false, false, false, false};
+    std::vector<uint64_t> lines(kLists * kLineStd, 0), one_list;
+    for (int l = 0; l < kLists; ++l) {
+      const G2Aff q = g2_from_jacobian_std(key_g2[l]);
+      if (q.inf) { skip_mask |= 1u << l; continue; }
+      if (!g2_on_curve(q)) { key_fail |= uses[l]; skip_mask |= 1u << l; continue; }
+      if (!prepare_g2_lines(q, one_list)) { degenerate[l] = true; skip_mask |= 1u << l; continue; }
+      memcpy(lines.data() + l * kLineStd, one_list.data(), kLineStd * 8);
+    }
+    // the proofs: per proof what the single verifier tests before and inside its product checks
+    static const struct { int at; unsigned uses; } kG1[7] = {{0, 1u << 1 | 1u << 4 | 1u << 5}, {12, 1u << 1}, {48, 1u << 2}, {60, 1u << 3 | 1u << 4 | 1u << 5},
+                                                             {72, 1u << 3}, {84, 1u << 4}, {96, 1u << 5}};   // PiA PiAp PiBp PiC PiCp PiH PiKp
+    std::vector<uint64_t> g1(7 * 12 * n), b(24 * n);
+    std::vector<unsigned> forced(n, key_fail);
+    std::vector<char> refused(n, 0);
+    for (size_t i = 0; i < n; ++i) {
+      const uint64_t* proof = proofs + 108 * i;
+      const uint64_t* pub = public_signals + 4 * i * npublic;
+      if (strict && (!scalars_canonical(pub, npublic) || !coords_canonical(proof, 27))) {
+        refused[i] = 1;
+        for (int k = 0; k < 7; ++k) memset(g1.data() + 12 * (k * n + i), 0, 96);
+        memset(b.data() + 24 * i, 0, 192);
+        continue;
+      }
+      bool finite[7];
+      for (int k = 0; k < 7; ++k) {
+        uint64_t* dst = g1.data() + 12 * (k * n + i);
+        const G1Aff p = g1_from_jacobian_std(proof + kG1[k].at);
+        finite[k] = !p.inf;
+        if (g1_on_curve(p)) memcpy(dst, proof + kG1[k].at, 96);
+        else { forced[i] |= kG1[k].uses; memset(dst, 0, 96); }
+      }
+      if (g2_on_curve(g2_from_jacobian_std(proof + 24))) memcpy(b.data() + 24 * i, proof + 24, 192);
+      else { forced[i] |= eq(2) | eq(4) | eq(5); memset(b.data() + 24 * i, 0, 192); }
+      bool ic_used = ic_bad[0] != 0;
+      for (size_t j = 0; j < npublic; ++j)
+        if (ic_bad[j + 1] && (pub[4 * j] | pub[4 * j + 1] | pub[4 * j + 2] | pub[4 * j + 3])) ic_used = true;
+      if (ic_used) forced[i] |= eq(4) | eq(5);
+      if (degenerate[kVka] && finite[0]) forced[i] |= eq(1);
+      if (degenerate[kVkc] && finite[3]) forced[i] |= eq(3);
+      if (degenerate[kVkz] && finite[5]) forced[i] |= eq(4);
+      if (degenerate[kG2Kg] && finite[6]) forced[i] |= eq(5);
+      if (degenerate[kG2Kbg] && !(forced[i] & eq(5))) {                 // its partner is vkx + PiA + PiC: formed here, on this path only
+        const G1Jac sum = g1j_add(g1j_add(accumulate_ic(vk_ic, nic, pub, npublic), g1j_from(g1_from_jacobian_std(proof))),
+                                  g1j_from(g1_from_jacobian_std(proof + 60)));
+        if (!fp_is_zero(sum.z)) forced[i] |= eq(5);
+      }
+    }
+    if ((rc = gs_g1_upload(g1.data(), 7 * n, hg1)) != GS_OK) return rc;
+    if ((rc = gs_g2_upload(b.data(), n, hb)) != GS_OK) return rc;
+    if ((rc = gs_g1_upload(key_g1, 2, hkey)) != GS_OK) return rc;
+    std::vector<int> member(n), one(5 * n);
+    rc = gs::pinocchio_verify_each_device(fn, *hg1, *hb, *hic, *hkey, public_signals, npublic, n, lines.data(), skip_mask, member.data(), one.data());
+    if (rc != GS_OK) return rc;
+    // the fold, in gs_pinocchio_verify's order: equation 1, PiB's membership (reported as 2), equations 2 .. 5
+    uint64_t count = 0;
+    for (size_t i = 0; i < n; ++i) {
+      int bad = 0;
+      if (!refused[i]) {
+        unsigned fails = forced[i];
+        for (int e = 1; e <= 5; ++e)
+          if (!one[(size_t)(e - 1) * n + i]) fails |= eq(e);
+        if (!member[i]) fails |= eq(2);
+        for (int e = 5; e >= 1; --e)
+          if (fails & eq(e)) bad = e;
+      }
+      ok_each[i] = (refused[i] || bad) ? 0 : 1;
+      if (failed_each) failed_each[i] = bad;
       count += ok_each[i] ? 0 : 1;
     }
     if (nbad) *nbad = count;

@@ -240,15 +240,64 @@ _CHECKS = ("e(piA, Va) == e(piA', g2), valid knowledge commitment for A",
            "e(Vkx+piA+piC, g2KbetaKgamma) * e(g1KbetaKgamma, piB) == e(piK, g2Kgamma)")
 
 
+def _proof_words(proof):
+    """A proof as the 108 words of gs_pinocchio_verify: PiA, PiAp | PiB | PiBp, PiC, PiCp, PiH, PiKp."""
+    words = np.concatenate([capi.g1_points_to_u64([proof.PiA, proof.PiAp]).reshape(-1), capi.g2_points_to_u64([proof.PiB]).reshape(-1),
+                            capi.g1_points_to_u64([proof.PiBp, proof.PiC, proof.PiCp, proof.PiH, proof.PiKp]).reshape(-1)])
+    return np.ascontiguousarray(words, dtype=np.uint64)
+
+
+def VerifyProofsEachChecks(vk, proofs, publicSignalsList):
+    """Many proofs of ONE verification key on the device (gs_pinocchio_verify_each) -> list[int]: per proof 0, or 1..5 for the first of
+    the five equations, in the reference's order, that does not hold -- what gs_pinocchio_verify reports as failed_check for that proof
+    with its signals.  Under gs_verify_set_strict(1) a proof refused for a non-canonical encoding also reports 0: VerifyProofsEach
+    gives the verdicts.  Needs an initialised device."""
+    return _verify_each(vk, proofs, publicSignalsList, "VerifyProofsEachChecks")[1]
+
+
+def VerifyProofsEach(vk, proofs, publicSignalsList, debug=False):
+    """Many proofs of ONE verification key, a verdict for each, on the device (gs_pinocchio_verify_each) -> list[bool]: exactly
+    [VerifyProof(vk, p, s) for p, s in zip(proofs, publicSignalsList)], deterministic, no challenge.  debug=True prints, per rejected
+    proof, the line VerifyProof(debug=True) prints for its failing check.  VerifyProofsEachChecks returns the failing equation of each
+    proof instead; VerifyProof in a loop on the host gives the same answers and takes five final exponentiations per proof on one core.
+    Needs an initialised device."""
+    ok, bad = _verify_each(vk, proofs, publicSignalsList, "VerifyProofsEach")
+    if debug:
+        for i, which in enumerate(bad):
+            if which:
+                print("proof %d: ❌ %s" % (i, _CHECKS[which - 1]))
+    return ok
+
+
+def _verify_each(vk, proofs, publicSignalsList, who):
+    if len(proofs) != len(publicSignalsList):
+        raise ValueError("%s: %d proofs, %d lists of public signals" % (who, len(proofs), len(publicSignalsList)))
+    npublic = len(publicSignalsList[0]) if publicSignalsList else 0
+    if any(len(s) != npublic for s in publicSignalsList):
+        raise ValueError("%s: every proof of one key has the same number of public signals" % who)
+    ic, nic, _, _ = _scheme.verify_inputs(vk, [0] * npublic)
+    g1 = capi.g1_points_to_u64([vk.Vkb, vk.G1Kbg])
+    g2 = capi.g2_points_to_u64([vk.Vka, vk.Vkc, vk.G2Kbg, vk.G2Kg, vk.Vkz])
+    flat = [int(x) % capi.R for s in publicSignalsList for x in s]
+    pub = capi.ints_to_u64(flat) if flat else np.zeros((1, 4), dtype=np.uint64)
+    n = len(proofs)
+    words = np.ascontiguousarray(np.concatenate([_proof_words(p) for p in proofs])) if n else np.zeros(108, dtype=np.uint64)
+    ok, bad = np.zeros(max(n, 1), dtype=np.intc), np.zeros(max(n, 1), dtype=np.intc)
+    nbad = ctypes.c_uint64(0)
+    capi.call("gs_pinocchio_verify_each", capi.ptr64(g2[0]), capi.ptr64(g1[0]), capi.ptr64(g2[1]), capi.ptr64(g1[1]), capi.ptr64(g2[2]),
+              capi.ptr64(g2[3]), capi.ptr64(g2[4]), ic, nic, capi.ptr64(pub), npublic, capi.ptr64(words), n, ok.ctypes.data_as(capi.intp),
+              bad.ctypes.data_as(capi.intp), ctypes.byref(nbad))
+    return [bool(x) for x in ok[:n]], [int(x) for x in bad[:n]]
+
+
 def VerifyProof(vk, proof, publicSignals, debug=False):
     """snark.VerifyProof(vk, proof, publicSignals, debug) (snark.go:292-368) -> bool: the five pairing equations in the
-    reference's order (gs_pinocchio_verify, host side, no device needed)."""
+    reference's order (gs_pinocchio_verify, host side, no device needed).  Many proofs of one key: VerifyProofsEach gives the same
+    verdicts on the device, VerifyProofsEachChecks the failing equation of each."""
     inputs = _scheme.verify_inputs(vk, publicSignals)
     g1 = capi.g1_points_to_u64([vk.Vkb, vk.G1Kbg])
     g2 = capi.g2_points_to_u64([vk.Vka, vk.Vkc, vk.G2Kbg, vk.G2Kg, vk.Vkz])
-    words = np.concatenate([capi.g1_points_to_u64([proof.PiA, proof.PiAp]).reshape(-1), capi.g2_points_to_u64([proof.PiB]).reshape(-1),
-                            capi.g1_points_to_u64([proof.PiBp, proof.PiC, proof.PiCp, proof.PiH, proof.PiKp]).reshape(-1)])
-    words = np.ascontiguousarray(words, dtype=np.uint64)
+    words = _proof_words(proof)
     ok, bad = ctypes.c_int(0), ctypes.c_int(0)
     capi.call("gs_pinocchio_verify", capi.ptr64(g2[0]), capi.ptr64(g1[0]), capi.ptr64(g2[1]), capi.ptr64(g1[1]), capi.ptr64(g2[2]),
               capi.ptr64(g2[3]), capi.ptr64(g2[4]), *inputs, capi.ptr64(words), ctypes.byref(ok), ctypes.byref(bad))

@@ -206,3 +206,85 @@ func Groth16VerifyEach(vk Groth16VkParts, proofs []Groth16BatchProof, order *big
 	}
 	return out, nil
 }
+
+// PinocchioBatchProof is one Pinocchio proof of a batch with its public signals.
+type PinocchioBatchProof struct {
+	Proof         PinocchioProof
+	PublicSignals []*big.Int
+}
+
+// PinocchioVerifyEach gives the answers of PinocchioVerify for EVERY proof of a batch under one verification key, on the device
+// (gs_pinocchio_verify_each): ok[i] is its verdict and failed[i] is 0 or the number (1..5) of the first of the five equations, in the
+// reference's order, that does not hold.  Exact and deterministic, no challenge.  A proof with a point off its curve, a PiB outside
+// the order-r subgroup or (under strict mode, then with failed 0) a non-canonical encoding gets false and is not an error; a key point
+// off its curve fails every equation that uses it.  Needs Init.  Call sequence = tests/c/pinocchio_verify_each.c.
+func PinocchioVerifyEach(vk PinocchioVkParts, proofs []PinocchioBatchProof, order *big.Int) (ok []bool, failed []int, err error) {
+	if len(proofs) == 0 {
+		return []bool{}, []int{}, nil
+	}
+	g2, err := G2Points([][3][2]*big.Int{vk.Vka, vk.Vkc, vk.G2Kbg, vk.G2Kg, vk.Vkz})
+	if err != nil {
+		return nil, nil, err
+	}
+	g1, err := G1Points([][3]*big.Int{vk.Vkb, vk.G1Kbg})
+	if err != nil {
+		return nil, nil, err
+	}
+	ic, err := G1Points(vk.IC)
+	if err != nil {
+		return nil, nil, err
+	}
+	npublic := len(proofs[0].PublicSignals)
+	signals := make([]*big.Int, 0, len(proofs)*npublic)
+	words := make([]uint64, 0, 108*len(proofs))
+	for _, bp := range proofs {
+		if len(bp.PublicSignals) != npublic {
+			return nil, nil, errors.New("gosnarkhip: every proof of one key has the same number of public signals")
+		}
+		signals = append(signals, bp.PublicSignals...)
+		p := bp.Proof
+		// a proof = PiA, PiAp (12 words each), PiB (24), PiBp, PiC, PiCp, PiH, PiKp (12 each) = 108 words
+		pa, err := G1Points([][3]*big.Int{p.PiA, p.PiAp})
+		if err != nil {
+			return nil, nil, err
+		}
+		pb, err := G2Points([][3][2]*big.Int{p.PiB})
+		if err != nil {
+			return nil, nil, err
+		}
+		pc, err := G1Points([][3]*big.Int{p.PiBp, p.PiC, p.PiCp, p.PiH, p.PiKp})
+		if err != nil {
+			return nil, nil, err
+		}
+		words = append(append(append(words, pa...), pb...), pc...)
+	}
+	pub, err := Scalars(signals, order)
+	if err != nil {
+		return nil, nil, err
+	}
+	if len(pub) == 0 {
+		pub = make([]uint64, 4)
+	}
+	oks := make([]C.int, len(proofs))
+	fails := make([]C.int, len(proofs))
+	var nbad C.uint64_t
+	err = call(func() C.int {
+		return C.gs_pinocchio_verify_each(ptr(g2[0:]), ptr(g1[0:]), ptr(g2[24:]), ptr(g1[12:]), ptr(g2[48:]), ptr(g2[72:]), ptr(g2[96:]),
+			ptr(ic), C.size_t(len(vk.IC)), ptr(pub), C.size_t(npublic), ptr(words), C.size_t(len(proofs)), &oks[0], &fails[0], &nbad)
+	})
+	runtime.KeepAlive(g1)
+	runtime.KeepAlive(g2)
+	runtime.KeepAlive(ic)
+	runtime.KeepAlive(pub)
+	runtime.KeepAlive(words)
+	runtime.KeepAlive(oks)
+	runtime.KeepAlive(fails)
+	if err != nil {
+		return nil, nil, err
+	}
+	ok, failed = make([]bool, len(proofs)), make([]int, len(proofs))
+	for i := range ok {
+		ok[i], failed[i] = oks[i] == 1, int(fails[i])
+	}
+	return ok, failed, nil
+}

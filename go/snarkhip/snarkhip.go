@@ -341,3 +341,24 @@ func VerifyProof(vk snark.Vk, proof snark.Proof, publicSignals []*big.Int, debug
 	}
 	return true
 }
+
+// VerifyProofsEach gives VerifyProof's answer for every proof of a batch under one verification key, on the device
+// (gosnarkhip.PinocchioVerifyEach): exact, no challenge; failed[i] is 0 or the number (1..5) of the first equation of proof i that
+// does not hold.  VerifyProof in a loop gives the same answers on one host core.  An error (no device, ragged input) reads as nil.
+func VerifyProofsEach(vk snark.Vk, proofs []snark.Proof, publicSignals [][]*big.Int) (ok []bool, failed []int) {
+	if len(proofs) != len(publicSignals) {
+		return nil, nil
+	}
+	batch := make([]gosnarkhip.PinocchioBatchProof, len(proofs))
+	for i, p := range proofs {
+		batch[i] = gosnarkhip.PinocchioBatchProof{Proof: gosnarkhip.PinocchioProof{PiA: p.PiA, PiAp: p.PiAp, PiB: p.PiB, PiBp: p.PiBp,
+			PiC: p.PiC, PiCp: p.PiCp, PiH: p.PiH, PiKp: p.PiKp}, PublicSignals: publicSignals[i]}
+	}
+	ok, failed, err := gosnarkhip.PinocchioVerifyEach(gosnarkhip.PinocchioVkParts{
+		Vka: vk.Vka, Vkb: vk.Vkb, Vkc: vk.Vkc, IC: vk.IC, G1Kbg: vk.G1Kbg, G2Kbg: vk.G2Kbg, G2Kg: vk.G2Kg, Vkz: vk.Vkz,
+	}, batch, snark.Utils.FqR.Q)
+	if err != nil {
+		return nil, nil
+	}
+	return ok, failed
+}

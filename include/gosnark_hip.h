@@ -912,6 +912,38 @@ int gs_groth16_verify_each(const uint64_t vk_g1_alpha[12], const uint64_t vk_g2_
                            const uint64_t* public_signals /* nproofs x npublic x 4 */, size_t npublic,
                            const uint64_t* pi_a, const uint64_t* pi_b, const uint64_t* pi_c, size_t nproofs,
                            int* ok_each /* nproofs */, uint64_t* nbad /* may be null */);
+/* gs_pinocchio_verify_each: the verdict of gs_pinocchio_verify for EVERY proof of a batch under one key, on the device: ok_each[i] is
+ * exactly what gs_pinocchio_verify writes to *ok for proof i with its signals and failed_each[i] (optional) what it writes to
+ * *failed_check -- 0, or 1..5 for the first equation in the reference's order that does not hold -- in both settings of
+ * gs_verify_set_strict.  Deterministic, no challenge.  *nbad (optional) = how many verdicts are 0.
+ * The arguments are gs_pinocchio_verify's with one more dimension (proofs: nproofs x 108 words in its layout), the errors those of
+ * gs_groth16_verify_each: null arguments GS_ERR_ARG, nic < npublic + 1 GS_ERR_SHAPE, under strict mode nic != npublic + 1 GS_ERR_SHAPE; in
+ * these cases nothing is written.  nproofs = 0 returns GS_OK with *nbad = 0 and needs no device; without a device every other call
+ * returns GS_ERR_NOT_INIT and writes nothing.  There is no host fallback.  Every temporary array is freed on every path.
+ * Not errors, but verdicts, each with the equation number the host gives: under strict mode a proof with a non-canonical coordinate or
+ * signal gets (0, 0).  A proof point off its curve fails the equations that use it (PiA 1, 4, 5; PiAp 1; PiB 2, 4, 5; PiBp 2; PiC 3,
+ * 4, 5; PiCp 3; PiH 4; PiKp 5): the host tests the 8n points first, a few products each, and the point at infinity is uploaded in
+ * their place, because the uploads refuse a whole array for one such point.  A PiB on the twist outside the order-r subgroup (a
+ * per-point flags kernel) fails at equation 2 unless equation 1 failed already.  A key point off its curve fails every equation that
+ * uses it, for every proof (an IC point: equations 4 and 5 of the proofs whose sum takes it); a key G2 point with a degenerate step in
+ * prepare_g2_lines fails them where its partner in G1 is finite.
+ * The host prepares the lines of the six G2 points that are the same for every proof (Vka, Vkc, Vkz, G2Kbg, G2Kg and the generator)
+ * once per call.  Per proof, one lane: vkx_i by the joint double-and-add of gs_groth16_verify_each, then vkx_i + PiA_i and that sum
+ * plus PiC_i by complete formulas; then one workgroup row per equation, (nproofs / 64, 5) workgroups of one wave: equations 1 and 3
+ * only evaluate prepared lines (no G2 arithmetic), equations 2, 4 and 5 run PiB_i as the one live pair beside up to two prepared
+ * pairs; then the final exponentiation kernel of gs_pairing_each over all 5 nproofs values.  The host folds the 5 nproofs flags,
+ * the membership flags and its own screening into verdicts.
+ * Memory: per 64 proofs 5 x 135 KB of workspace and 5 x 24 KB of exponentiated values and flags (52 MB at 4096 proofs): a caller with
+ * millions of proofs passes them in windows.  Blocking; gs_last_timing(): total_ms = device time, of which h2d_ms = signals and lines,
+ * poly_ms = membership, plan_ms = vkx and the two sums, accumulate_ms = Miller loops, reduce_ms = final exponentiations.
+ * go-snark-study_amd/snark.py (VerifyProofsEach, VerifyProofsEachChecks), go/gosnarkhip/pairing_device.go (PinocchioVerifyEach) and
+ * tests/c/pinocchio_verify_each.c. */
+int gs_pinocchio_verify_each(const uint64_t vka[24], const uint64_t vkb[12], const uint64_t vkc[24], const uint64_t g1kbg[12],
+                             const uint64_t g2kbg[24], const uint64_t g2kg[24], const uint64_t vkz[24],
+                             const uint64_t* vk_ic /* nic x 12 */, size_t nic,
+                             const uint64_t* public_signals /* nproofs x npublic x 4 */, size_t npublic,
+                             const uint64_t* proofs /* nproofs x 108 words, gs_pinocchio_verify's layout */, size_t nproofs,
+                             int* ok_each /* nproofs */, int* failed_each /* nproofs, may be NULL */, uint64_t* nbad /* may be NULL */);
 /* gs_pairing_each: e(P[poff + i], Q[qoff + i]) for EVERY i < n, final exponentiation included, all of it on the device.  Value i
  * goes to out_fq12 + 48 i in gs_pairing's encoding and is equal bit for bit to gs_pairing on that pair; is_one[i] = 1 iff it is 1.
  * Either out-pointer may be NULL, not both.  A pair with an infinite member gives 1; n = 0 writes nothing (and still needs gs_init and
