@@ -100,6 +100,25 @@ def PairingEach(g1_handle, g2_handle, poff=0, qoff=0, n=None):
     return vals, [bool(x) for x in one]
 
 
+def G1Compress(g1_handle, off=0, n=None):
+    """A resident G1 array -> (x as [n, 4] uint64 in standard form, flag bytes) (gs_g1_compress; compressed.py has the byte codecs)."""
+    return capi.g1_compress(g1_handle, off, n)
+
+
+def G1Decompress(x_u64, flags):
+    """x coordinates and flag bytes -> (a resident G1 array, which entries decoded) (gs_g1_decompress)."""
+    return capi.g1_decompress(x_u64, flags)
+
+
+def G2Compress(g2_handle, off=0, n=None):
+    return capi.g2_compress(g2_handle, off, n)
+
+
+def G2Decompress(x_u64, flags):
+    """The same over the twist (gs_g2_decompress).  The points are NOT tested for membership of the order-r subgroup."""
+    return capi.g2_decompress(x_u64, flags)
+
+
 def PairingCheck(g1_points, g2_points):
     """prod_i e(g1_i, g2_i) == 1 with one shared final exponentiation (gs_pairing_check)."""
     if len(g1_points) != len(g2_points):

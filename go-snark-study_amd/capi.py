@@ -12,6 +12,7 @@ _INIT_DEVICE = None
 
 u64p = ctypes.POINTER(ctypes.c_uint64)
 u32p = ctypes.POINTER(ctypes.c_uint32)
+u8p = ctypes.POINTER(ctypes.c_uint8)
 intp = ctypes.POINTER(ctypes.c_int)
 Handle = ctypes.c_uint64
 
@@ -122,6 +123,10 @@ _SIGS = {
     "gs_g1_lagrange_levels_check": [Handle, Handle, ctypes.c_size_t, u64p, ctypes.POINTER(CheckResult)],
     "gs_g2_lagrange_levels_check": [Handle, Handle, ctypes.c_size_t, u64p, ctypes.POINTER(CheckResult)],
     "gs_g2_subgroup_check": [Handle, ctypes.c_size_t, ctypes.c_size_t, u64p, u64p],
+    "gs_g1_decompress": [u64p, u8p, ctypes.c_size_t, ctypes.POINTER(Handle), u8p, u64p, u64p],
+    "gs_g2_decompress": [u64p, u8p, ctypes.c_size_t, ctypes.POINTER(Handle), u8p, u64p, u64p],
+    "gs_g1_compress": [Handle, ctypes.c_size_t, ctypes.c_size_t, u64p, u8p],
+    "gs_g2_compress": [Handle, ctypes.c_size_t, ctypes.c_size_t, u64p, u8p],
     "gs_groth16_pk_create": [Handle, Handle, Handle, Handle, Handle, u64p, u64p, u64p, u64p, u64p,
                              u64p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(Handle)],
     "gs_groth16_prove": [Handle, u64p, ctypes.c_size_t, u64p, ctypes.c_size_t, u64p, u64p, u64p, intp],
@@ -693,6 +698,56 @@ def g2_subgroup_check(bases, off=0, n=None):
     nbad, first = ctypes.c_uint64(0), ctypes.c_uint64(0)
     call("gs_g2_subgroup_check", raw(bases), off, n, ctypes.byref(nbad), ctypes.byref(first))
     return int(nbad.value), (None if first.value == (1 << 64) - 1 else int(first.value))
+
+
+POINT_LARGEST_Y, POINT_INFINITY = 1, 2          # GS_POINT_LARGEST_Y, GS_POINT_INFINITY
+
+
+def _decompress(name, x_u64, flags, words):
+    init()
+    x = np.ascontiguousarray(x_u64, dtype=np.uint64).reshape(-1, words)
+    f = np.ascontiguousarray(flags, dtype=np.uint8).reshape(-1)
+    if f.shape[0] != x.shape[0]:
+        raise ValueError("%s: %d x coordinates, %d flag bytes" % (name, x.shape[0], f.shape[0]))
+    n = x.shape[0]
+    ok = np.zeros(max(n, 1), dtype=np.uint8)
+    nbad, first = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    cell = HandleCell()
+    one = np.zeros(max(words, 1), dtype=np.uint64)           # n = 0 still hands over readable memory
+    call(name, ptr64(x) if n else ptr64(one), (f if n else ok).ctypes.data_as(u8p), n, cell.ref, ok.ctypes.data_as(u8p), ctypes.byref(nbad),
+         ctypes.byref(first))
+    return cell.result(), ok[:n] != 0
+
+
+def g1_decompress(x_u64, flags):
+    """gs_g1_decompress: x coordinates ([n, 4] uint64, standard form) and flag bytes (POINT_LARGEST_Y: y is the larger of {y, q - y};
+    POINT_INFINITY) -> (a G1 base-array handle of n points, a bool array: which entries decoded).  An entry that does not decode -- x >= q,
+    x^3 + 3 not a square, an inconsistent flag -- is the point at infinity in the array; nothing is raised for it."""
+    return _decompress("gs_g1_decompress", x_u64, flags, 4)
+
+
+def g2_decompress(x_u64, flags):
+    """gs_g2_decompress: the same over the twist, x as [n, 8] uint64 (c0 | c1), "larger" decided by c1 and by c0 only when c1 = 0.  The
+    points are on the twist, NOT tested for membership of the order-r subgroup: g2_subgroup_check on the handle does that."""
+    return _decompress("gs_g2_decompress", x_u64, flags, 8)
+
+
+def _compress(name, handle, off, n, words):
+    off = int(off)
+    n = max(len(handle) - off, 0) if n is None else int(n)
+    x, f = np.zeros((max(n, 1), words), dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint8)
+    call(name, raw(handle), off, n, ptr64(x), f.ctypes.data_as(u8p))
+    return x[:n], f[:n]
+
+
+def g1_compress(handle, off=0, n=None):
+    """gs_g1_compress: the points off .. off + n - 1 (default: all from off on) of a resident G1 array -> (x as [n, 4] uint64 in standard
+    form, flag bytes); a point at infinity gives x = 0 and POINT_INFINITY."""
+    return _compress("gs_g1_compress", handle, off, n, 4)
+
+
+def g2_compress(handle, off=0, n=None):
+    return _compress("gs_g2_compress", handle, off, n, 8)
 
 
 def pairing_product(g1, poff, g2, qoff, n):

@@ -412,20 +412,30 @@ def VerifyProofsEach(vk, proofs, publicSignalsList):
     npublic = len(publicSignalsList[0]) if publicSignalsList else 0
     if any(len(s) != npublic for s in publicSignalsList):
         raise ValueError("VerifyProofsEach: every proof of one key has the same number of public signals")
+    return _verify_each_words(vk, _proof_words(proofs), publicSignalsList, npublic)
+
+
+def _proof_words(proofs):
+    """[Proof] -> (A as [n, 12] uint64 Jacobian words, B as [n, 24], C as [n, 12])."""
+    return (capi.g1_points_to_u64([p.PiA for p in proofs]), capi.g2_points_to_u64([p.PiB for p in proofs]),
+            capi.g1_points_to_u64([p.PiC for p in proofs]))
+
+
+def _verify_each_words(vk, abc, publicSignalsList, npublic):
+    """gs_groth16_verify_each on the proofs' points as word arrays (_proof_words, or compressed.decompress_proof_arrays) -> list[bool]."""
+    n = len(publicSignalsList)
     ic, nic, _, _ = _scheme.verify_inputs(vk, [0] * npublic)
     g1 = capi.g1_points_to_u64([vk.G1_Alpha])
     g2 = capi.g2_points_to_u64([vk.G2_Beta, vk.G2_Gamma, vk.G2_Delta])
     flat = [int(x) % capi.R for s in publicSignalsList for x in s]
     pub = capi.ints_to_u64(flat) if flat else np.zeros((1, 4), dtype=np.uint64)
-    a = capi.g1_points_to_u64([p.PiA for p in proofs]) if proofs else np.zeros((1, 12), dtype=np.uint64)
-    b = capi.g2_points_to_u64([p.PiB for p in proofs]) if proofs else np.zeros((1, 24), dtype=np.uint64)
-    c = capi.g1_points_to_u64([p.PiC for p in proofs]) if proofs else np.zeros((1, 12), dtype=np.uint64)
-    ok = np.zeros(max(len(proofs), 1), dtype=np.intc)
+    a, b, c = [np.ascontiguousarray(v, dtype=np.uint64) if n else np.zeros((1, w), dtype=np.uint64) for v, w in zip(abc, (12, 24, 12))]
+    ok = np.zeros(max(n, 1), dtype=np.intc)
     nbad = ctypes.c_uint64(0)
     capi.call("gs_groth16_verify_each", capi.ptr64(g1[0]), capi.ptr64(g2[0]), capi.ptr64(g2[1]), capi.ptr64(g2[2]), ic, nic,
-              capi.ptr64(pub), npublic, capi.ptr64(a), capi.ptr64(b), capi.ptr64(c), len(proofs), ok.ctypes.data_as(capi.intp),
+              capi.ptr64(pub), npublic, capi.ptr64(a), capi.ptr64(b), capi.ptr64(c), n, ok.ctypes.data_as(capi.intp),
               ctypes.byref(nbad))
-    return [bool(x) for x in ok[:len(proofs)]]
+    return [bool(x) for x in ok[:n]]
 
 
 def VerifyProofs(vk, proofs, publicSignalsList, seed=None):
@@ -439,6 +449,12 @@ def VerifyProofs(vk, proofs, publicSignalsList, seed=None):
     npublic = len(publicSignalsList[0]) if publicSignalsList else 0
     if any(len(s) != npublic for s in publicSignalsList):
         raise ValueError("VerifyProofs: every proof of one key has the same number of public signals")
+    return _verify_batch_words(vk, _proof_words(proofs), publicSignalsList, npublic, seed)
+
+
+def _verify_batch_words(vk, abc, publicSignalsList, npublic, seed):
+    """gs_groth16_verify_batch on the proofs' points as word arrays -> bool."""
+    n = len(publicSignalsList)
     ic, nic, _, _ = _scheme.verify_inputs(vk, [0] * npublic)
     if seed is None:
         import secrets
@@ -450,11 +466,39 @@ def VerifyProofs(vk, proofs, publicSignalsList, seed=None):
     g2 = capi.g2_points_to_u64([vk.G2_Beta, vk.G2_Gamma, vk.G2_Delta])
     flat = [int(x) % capi.R for s in publicSignalsList for x in s]
     pub = capi.ints_to_u64(flat) if flat else np.zeros((1, 4), dtype=np.uint64)
-    a = capi.g1_points_to_u64([p.PiA for p in proofs]) if proofs else np.zeros((1, 12), dtype=np.uint64)
-    b = capi.g2_points_to_u64([p.PiB for p in proofs]) if proofs else np.zeros((1, 24), dtype=np.uint64)
-    c = capi.g1_points_to_u64([p.PiC for p in proofs]) if proofs else np.zeros((1, 12), dtype=np.uint64)
+    a, b, c = [np.ascontiguousarray(v, dtype=np.uint64) if n else np.zeros((1, w), dtype=np.uint64) for v, w in zip(abc, (12, 24, 12))]
     ok = ctypes.c_int(0)
     capi.call("gs_groth16_verify_batch", capi.ptr64(g1[0]), capi.ptr64(g2[0]), capi.ptr64(g2[1]), capi.ptr64(g2[2]), ic, nic,
-              capi.ptr64(pub), npublic, capi.ptr64(a), capi.ptr64(b), capi.ptr64(c), len(proofs), capi.ptr64(capi.ints_to_u64([challenge])),
+              capi.ptr64(pub), npublic, capi.ptr64(a), capi.ptr64(b), capi.ptr64(c), n, capi.ptr64(capi.ints_to_u64([challenge])),
               ctypes.byref(ok))
     return bool(ok.value)
+
+
+def _compressed_inputs(what, blobs, publicSignalsList, codec):
+    from . import compressed
+    if len(blobs) != len(publicSignalsList):
+        raise ValueError("%s: %d proofs, %d lists of public signals" % (what, len(blobs), len(publicSignalsList)))
+    npublic = len(publicSignalsList[0]) if publicSignalsList else 0
+    if any(len(s) != npublic for s in publicSignalsList):
+        raise ValueError("%s: every proof of one key has the same number of public signals" % what)
+    a, b, c, ok = compressed.decompress_proof_arrays(blobs, codec)
+    return (a, b, c), ok, npublic
+
+
+def VerifyProofsEachCompressed(vk, blobs, publicSignalsList, codec):
+    """VerifyProofsEach on proofs as they arrive over a wire: 128 bytes each, A | B | C, compressed points in the format `codec`
+    (compressed.GNARK, .ARKWORKS, .BN256_PAIRING) -> list[bool].  The points are decompressed on the device (one gs_g1_decompress call
+    over A and C, one gs_g2_decompress call) and go to gs_groth16_verify_each as they come back: exactly VerifyProofsEach of
+    compressed.DecompressProofs(blobs, codec), and False for a proof with a point that does not decompress; the other verdicts are
+    unaffected by it."""
+    abc, ok, npublic = _compressed_inputs("VerifyProofsEachCompressed", blobs, publicSignalsList, codec)
+    return [bool(v and o) for v, o in zip(_verify_each_words(vk, abc, publicSignalsList, npublic), ok)]
+
+
+def VerifyProofsCompressed(vk, blobs, publicSignalsList, codec, seed=None):
+    """VerifyProofs on compressed proofs -> bool: False when any point fails to decompress, else VerifyProofs of the decompressed
+    proofs (same challenge rule, same bound)."""
+    abc, ok, npublic = _compressed_inputs("VerifyProofsCompressed", blobs, publicSignalsList, codec)
+    if not bool(np.all(ok)):
+        return False
+    return _verify_batch_words(vk, abc, publicSignalsList, npublic, seed)

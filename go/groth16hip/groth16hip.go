@@ -458,3 +458,32 @@ func VerifyProofsEach(vk groth16.Vk, proofs []groth16.Proof, publicSignals [][]*
 	}
 	return oks
 }
+
+// VerifyProofsEachCompressed is VerifyProofsEach on proofs as they arrive over a wire: 128 bytes each, A | B | C, compressed points in
+// the layout `codec` (gosnarkhip.Gnark, .Arkworks, .Bn256Pairing).  The points are decompressed on the device
+// (gosnarkhip.DecompressProofs: one G1 call over A and C, one G2 call) and go to gosnarkhip.Groth16VerifyEach: a proof with a point
+// that does not decompress reads false and the other verdicts are unaffected by it.  An error (no device, ragged input, a blob that
+// is not 128 bytes) reads as nil.
+func VerifyProofsEachCompressed(vk groth16.Vk, blobs [][]byte, publicSignals [][]*big.Int, codec gosnarkhip.PointCodec) []bool {
+	if len(blobs) != len(publicSignals) {
+		return nil
+	}
+	a, b, c, decoded, err := gosnarkhip.DecompressProofs(Device, blobs, codec)
+	if err != nil {
+		return nil
+	}
+	batch := make([]gosnarkhip.Groth16BatchProof, len(blobs))
+	for i := range batch {
+		batch[i] = gosnarkhip.Groth16BatchProof{PiA: a[i], PiB: b[i], PiC: c[i], PublicSignals: publicSignals[i]}
+	}
+	oks, err := gosnarkhip.Groth16VerifyEach(gosnarkhip.Groth16VkParts{
+		IC: vk.IC, G1Alpha: vk.G1.Alpha, G2Beta: vk.G2.Beta, G2Gamma: vk.G2.Gamma, G2Delta: vk.G2.Delta,
+	}, batch, groth16.Utils.FqR.Q)
+	if err != nil {
+		return nil
+	}
+	for i := range oks {
+		oks[i] = oks[i] && decoded[i]
+	}
+	return oks
+}

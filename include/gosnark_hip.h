@@ -443,6 +443,44 @@ int gs_g2_lagrange_levels_check(gs_handle powers, gs_handle levels, size_t hi, c
  * upload; go/gosnarkhip/g2_membership.go and tests/c/g2_membership.c are the plain call. */
 int gs_g2_subgroup_check(gs_handle points, size_t off, size_t n, uint64_t* nbad, uint64_t* first_bad);
 
+/* ---- compressed points: an x coordinate and a sign bit <-> a resident array of affine points -------------------------------------- */
+/* A point on the wire is usually its x coordinate and one bit that says which of the two roots of y^2 = x^3 + b is meant: 32 bytes for
+ * G1, 64 for G2, 128 for a Groth16 proof.  Getting y back is a square root in Fq (one power with a 252-bit exponent, q = 3 mod 4) or
+ * in Fq2 (two such powers, the complex method, no inversion): go-snark-study_amd/csrc/sqrt.h.
+ *
+ * Coordinates here are 4 little-endian 64-bit words in STANDARD form, not Montgomery -- the form of the gs_g*_upload triples -- and an
+ * Fq2 coordinate is c0 | c1.  Byte order and flag positions of a wire format are the host codec's business
+ * (go-snark-study_amd/compressed.py: gnark, arkworks, the bn256 pairing crate); the device never sees a wire format.  One flag byte per
+ * point:
+ *   GS_POINT_LARGEST_Y   y is the LARGER of {y, q - y} as canonical integers; in Fq2 decided by c1, and by c0 only when c1 = 0
+ *   GS_POINT_INFINITY    the point at infinity; x must be 0 and GS_POINT_LARGEST_Y clear
+ * y = 0 cannot occur: a point with y = 0 has order 2 and both curves have odd order, so "larger" never ties.
+ *
+ * gs_g1_decompress / gs_g2_decompress: one lane per point computes y = sqrt(x^3 + 3) (G1) or sqrt(x^3 + 3/(9 + u)) (the twist), takes
+ * the root the flag asks for and writes an ordinary affine base array of n points into *out -- every entry point that takes a base
+ * array takes it.  An entry is BAD when a coordinate is >= q, when the right-hand side has no root, when GS_POINT_INFINITY comes with
+ * x != 0 or with GS_POINT_LARGEST_Y, or when any flag bit above bit 1 is set.  A bad entry becomes the point at infinity and gets
+ * ok[i] = 0 (a good one 1); the call still returns GS_OK -- unlike the uploads, which refuse a whole array for one point off the curve:
+ * one malformed proof must not sink a batch.  ok may be NULL.  *nbad = how many entries are bad, *first_bad = the smallest index of
+ * one, UINT64_MAX when there is none.  n = 0 gives an empty array.
+ * gs_g2_decompress does NOT test subgroup membership: the result is on the twist, not necessarily in G2.  Run gs_g2_subgroup_check on
+ * the handle where that matters (the pairing entry points require it).  G1 has cofactor 1.
+ *
+ * gs_g1_compress / gs_g2_compress: the points off .. off + n - 1 of a resident array -> x (n x 4 or n x 8 words) and flags (n bytes);
+ * a point at infinity gives x = 0 and GS_POINT_INFINITY.
+ *
+ * A bad handle, a handle of the other group or a null pointer is GS_ERR_ARG, a range beyond the array GS_ERR_SHAPE.  All four calls
+ * are blocking; gs_last_timing().total_ms = device time of the kernel.  No window table is built and no device memory is left behind
+ * but the array of gs_g*_decompress.  go/gosnarkhip/point_codec.go and tests/c/point_codec.c are the plain call sequence. */
+#define GS_POINT_LARGEST_Y 1u
+#define GS_POINT_INFINITY  2u
+int gs_g1_decompress(const uint64_t* x /* n x 4 */, const uint8_t* flags /* n */, size_t n,
+                     gs_handle* out, uint8_t* ok /* n, or NULL */, uint64_t* nbad, uint64_t* first_bad);
+int gs_g2_decompress(const uint64_t* x /* n x 8: c0 | c1 */, const uint8_t* flags, size_t n,
+                     gs_handle* out, uint8_t* ok, uint64_t* nbad, uint64_t* first_bad);
+int gs_g1_compress(gs_handle bases, size_t off, size_t n, uint64_t* x /* n x 4 */, uint8_t* flags /* n */);
+int gs_g2_compress(gs_handle bases, size_t off, size_t n, uint64_t* x /* n x 8 */, uint8_t* flags);
+
 /* ---- Groth16 prover (groth16/groth16.go) --------------------------------------------------- */
 /* Device-resident proving key: groth16.Pk (groth16.go:15-32).  At, BACGamma (G1), BACDelta:
  * m points; G2 BACGamma: m points; PowersTauDelta: len(Z) points; single points as Jacobian

@@ -219,6 +219,15 @@ def main():
     for row, v in enumerate(frobenius_constants()):
         out += "      " + " ".join("case %d: return 0x%08xu;" % (row * 16 + i, l) for i, l in enumerate(limbs(v * MONT_R % Q))) + "\n"
     out += "      default: return 0u;\n    }\n  }\n"
+    # square roots (csrc/sqrt.h): q = 3 mod 4, so a^((q+1)/4) is a root of a residue a and a^((q-3)/4) is the inverse of that root; both
+    # exponents have 252 bits = 84 digits of 3 bits, written as 32-bit words, least significant first.  1/2 in Montgomery form, and
+    # (q-1)/2 as plain limbs: y is the larger of {y, q - y} exactly when y > (q-1)/2
+    e_root, e_inv = (Q + 1) // 4, (Q - 3) // 4
+    assert Q % 4 == 3 and e_root.bit_length() == 252 and e_inv.bit_length() == 252 and (e_root >> 249) and (e_inv >> 249)
+    assert pow(4, e_root, Q) in (2, Q - 2) and pow(4, e_inv, Q) * pow(4, e_root, Q) % Q == 1
+    out += "  static constexpr int kSqrtDigits = 84;      // 3-bit digits of either exponent; the top digit is not zero\n"
+    out += arr("sqrt_root32", words8(e_root), 8) + arr("sqrt_inv32", words8(e_inv), 8)
+    out += arr("half", limbs((Q + 1) // 2 * MONT_R % Q)) + arr("qhalf", limbs((Q - 1) // 2))
     out += "};\n\n}  // namespace gs\n"
     path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
                         "go-snark-study_amd", "csrc", "bn128_constants.h")
