@@ -235,6 +235,9 @@ _SIGS = {
     "gs_pinocchio_verify_each": [u64p, u64p, u64p, u64p, u64p, u64p, u64p, u64p, ctypes.c_size_t, u64p, ctypes.c_size_t, u64p, ctypes.c_size_t,
                                  intp, intp, ctypes.POINTER(ctypes.c_uint64)],
     "gs_pairing_each": [Handle, ctypes.c_size_t, Handle, ctypes.c_size_t, ctypes.c_size_t, u64p, intp],
+    "gs_groth16_vk_create": [u64p, u64p, u64p, u64p, u64p, ctypes.c_size_t, ctypes.POINTER(Handle)],
+    "gs_groth16_verify_each_keys": [ctypes.POINTER(Handle), ctypes.c_size_t, u32p, u64p, u64p, u64p, u64p, ctypes.c_size_t, intp,
+                                    ctypes.POINTER(ctypes.c_uint64)],
     "gs_groth16_verify_batch": [u64p, u64p, u64p, u64p, u64p, ctypes.c_size_t, u64p, ctypes.c_size_t, u64p, u64p, u64p, ctypes.c_size_t, u64p, intp],
 }
 EXPORTS = sorted(list(_SIGS) + ["gs_shutdown", "gs_last_error", "gs_version", "gs_comm_destroy"])
@@ -767,6 +770,36 @@ def pairing_each(g1, poff, g2, qoff, n):
     call("gs_pairing_each", raw(g1), int(poff), raw(g2), int(qoff), n, ptr64(out) if n else ptr64(np.zeros(48, dtype=np.uint64)),
          one.ctypes.data_as(intp))
     return out, one[:n] != 0
+
+
+def groth16_vk_create(alpha_u64, beta_u64, gamma_u64, delta_u64, ic_u64):
+    """gs_groth16_vk_create: the key's points as Jacobian word arrays (alpha [12], beta / gamma / delta [24], IC [nic, 12]) -> the
+    DeviceHandle of a prepared verification key.  A key that cannot verify anything is refused (GosnarkHipError, the point is named)."""
+    init()
+    ic = np.ascontiguousarray(ic_u64, dtype=np.uint64).reshape(-1, 12)
+    cell = HandleCell()
+    call("gs_groth16_vk_create", *[ptr64(np.ascontiguousarray(v, dtype=np.uint64).reshape(-1)) for v in (alpha_u64, beta_u64, gamma_u64, delta_u64)],
+         ptr64(ic) if ic.shape[0] else None, ic.shape[0], cell.ref)
+    return cell.result()
+
+
+def groth16_verify_each_keys(keys, key_of_proof, pub_u64, a_u64, b_u64, c_u64):
+    """gs_groth16_verify_each_keys: prepared keys (whatever raw() takes), the key index of every proof, the signals of all proofs
+    concatenated in proof order ([total, 4] uint64) and the proofs' points as [n, 12], [n, 24], [n, 12] Jacobian words ->
+    (a bool array of n verdicts, the count of zeros)."""
+    kop = np.ascontiguousarray(key_of_proof, dtype=np.uint32).reshape(-1)
+    n = kop.shape[0]
+    pub = np.ascontiguousarray(pub_u64, dtype=np.uint64).reshape(-1, 4)
+    if pub.shape[0] == 0:
+        pub = np.zeros((1, 4), dtype=np.uint64)
+    a, b, c = [np.ascontiguousarray(v, dtype=np.uint64).reshape(-1, w) if n else np.zeros((1, w), dtype=np.uint64)
+               for v, w in zip((a_u64, b_u64, c_u64), (12, 24, 12))]
+    if a.shape[0] != max(n, 1) or b.shape[0] != max(n, 1) or c.shape[0] != max(n, 1):
+        raise ValueError("gs_groth16_verify_each_keys: %d key indices, %d / %d / %d points" % (n, a.shape[0], b.shape[0], c.shape[0]))
+    ok, nbad = np.zeros(max(n, 1), dtype=np.intc), ctypes.c_uint64(0)
+    call("gs_groth16_verify_each_keys", harr(keys) if len(keys) else None, len(keys), ptr32(kop) if n else None, ptr64(pub), ptr64(a), ptr64(b),
+         ptr64(c), n, ok.ctypes.data_as(intp), ctypes.byref(nbad))
+    return ok[:n] != 0, int(nbad.value)
 
 
 def scalars_upload(s_u64):

@@ -37,6 +37,10 @@ uint64_t object_bytes(Object* o) {
   switch (o->kind) {
     case Kind::G1Bases: case Kind::G2Bases: return static_cast<Bases*>(o)->buf.bytes;
     case Kind::Scalars: return static_cast<Scalars*>(o)->buf.bytes;
+    case Kind::GrothVk: {
+      auto* v = static_cast<GrothVk*>(o);
+      return v->ic->buf.bytes + v->lines.bytes + v->ab.bytes;
+    }
     case Kind::R1cs: {
       auto* r = static_cast<R1csObj*>(o);
       uint64_t t = r->w_mont.bytes + r->vals.bytes + r->coef.bytes + r->prod.bytes;

@@ -17,6 +17,7 @@
 #include "pairing.h"
 #include "point_io.h"
 #include "runtime.h"
+#include "verify_plan.h"
 
 using namespace gs;
 
@@ -316,6 +317,162 @@ int verify_each_impl(Ctx& c, const char* fn, gs_handle ha, gs_handle hb, gs_hand
   return GS_OK;
 }
 
+// ---- proofs of many keys: gs_groth16_vk_create, gs_groth16_verify_each_keys (verify.hip) ------------------------------------------
+// One key per one-wave workgroup (verify_plan.h): workgroup g reads its group record and through it its key record, both at addresses
+// that depend on blockIdx.x alone, so the key's words -- the pointers here, and the lines, the IC points and the e(alpha, beta) value
+// behind them -- stay what they are in the single-key kernels: the same for every lane of the wave.  Every slot exists (the groups are
+// whole), padded slots hold the point at infinity and are not read back.  The bodies are those of k_groth16_vkx and k_miller_groth16.
+struct VkRecord {                                                      // the per-call key table, one per entry of `keys`
+  const uint32_t* lines;                                               // gamma's list, then delta's, as limbs
+  const uint32_t* ic;
+  const uint64_t* ab;
+  uint32_t npublic, skip_gamma, skip_delta, reserved;
+};
+
+__global__ void __launch_bounds__(kPairBlock) k_groth16_vkx_keys(const VkRecord* __restrict__ keys, const VerifyGroup* __restrict__ groups,
+                                                                 const uint32_t* __restrict__ pub, uint32_t* __restrict__ out) {
+  constexpr int kAw = PointIO<FqTag>::kAffineWords;
+  const VerifyGroup g = groups[blockIdx.x];
+  const VkRecord key = keys[g.key];
+  if (threadIdx.x >= g.valid) return;                                  // a padded slot keeps the infinity the buffer was cleared to
+  const size_t i = (size_t)blockIdx.x * kPairBlock + threadIdx.x;
+  const uint32_t* mine = pub + (g.sig_off + (uint64_t)threadIdx.x * key.npublic) * 8;
+  const auto point = [&](int j) { return PointIO<FqTag>::load_affine(key.ic + (size_t)j * kAw); };
+  const auto bit = [&](int j, int b) { return ((mine[(size_t)j * 8 + (b >> 5)] >> (b & 31)) & 1u) != 0; };
+  PointIO<FqTag>::store_affine(out + i * kAw, groth16_vkx(point, bit, (int)key.npublic));
+}
+
+__global__ void __launch_bounds__(kPairBlock) k_miller_groth16_keys(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b,
+                                                                    const uint32_t* __restrict__ c, const uint32_t* __restrict__ vkx,
+                                                                    const VkRecord* __restrict__ keys, const VerifyGroup* __restrict__ groups,
+                                                                    uint32_t* __restrict__ workspace) {
+  __shared__ uint32_t lds[kF12Limbs][kPairBlock];
+  constexpr int kA1 = PointIO<FqTag>::kAffineWords, kA2 = PointIO<Fq2Tag>::kAffineWords;
+  const VkRecord key = keys[groups[blockIdx.x].key];
+  const size_t at = (size_t)blockIdx.x * kPairBlock + threadIdx.x;
+  Affine<FqTag> p1 = PointIO<FqTag>::load_affine(a + at * kA1);
+  const Affine<Fq2Tag> q1 = PointIO<Fq2Tag>::load_affine(b + at * kA2);
+  const Affine<FqTag> p2 = PointIO<FqTag>::load_affine(vkx + at * kA1);
+  const Affine<FqTag> p3 = PointIO<FqTag>::load_affine(c + at * kA1);
+  p1.y = canon(neg(p1.y));                                             // -A; infinity (0, 0) stays infinity
+  LdsF12 f{&lds[0][threadIdx.x]};
+  miller_loop_groth16(f, p1, q1, p2, key.skip_gamma != 0, PreparedLines{key.lines}, p3, key.skip_delta != 0,
+                      PreparedLines{key.lines + (size_t)kPreparedSteps * kLineWords});
+  GlbBank bank{workspace + (size_t)blockIdx.x * kWorkspaceWords + threadIdx.x};
+  GlbF12 keyval = bank.slot(1);
+  f12_from_std(keyval, key.ab);
+  f12_mul(f, keyval);
+  GlbF12 out = bank.slot(0);
+  f12_copy(out, f);
+}
+
+// the resident part of a key: the IC array (already uploaded, shared with its handle), the two lists as limbs, the key's Miller value
+int vk_install_impl(Ctx& c, const char* fn, gs_handle hic, size_t nic, const uint64_t* gamma_lines, const uint64_t* delta_lines, const uint64_t* ab,
+                    gs_handle* out) {
+  std::shared_ptr<Bases> ics = c.share<Bases>(hic, Kind::G1Bases);
+  if (!ics || ics->n != nic || !nic) return fail(GS_ERR_ARG, "%s: bad IC array", fn);
+  if (nic - 1 >= 0xffffffffull) return fail(GS_ERR_SHAPE, "%s: %zu IC points, indices are 32 bits", fn, nic);
+  constexpr size_t kLineStd = (size_t)kPreparedSteps * 16;              // u64 words of one prepared list
+  auto vk = std::make_shared<GrothVk>();
+  vk->ic = ics;
+  vk->npublic = nic - 1;
+  vk->skip_gamma = !gamma_lines;
+  vk->skip_delta = !delta_lines;
+  vk->lines.alloc(2 * (size_t)kPreparedSteps * kLineWords * 4);
+  vk->ab.alloc(48 * 8);
+  DevBuf lines_std(2 * kLineStd * 8);
+  std::vector<uint64_t> host_lines(2 * kLineStd, 0);
+  if (gamma_lines) memcpy(host_lines.data(), gamma_lines, kLineStd * 8);
+  if (delta_lines) memcpy(host_lines.data() + kLineStd, delta_lines, kLineStd * 8);
+  GS_HIP(hipMemcpyAsync(lines_std.p, host_lines.data(), 2 * kLineStd * 8, hipMemcpyHostToDevice, c.stream));
+  GS_HIP(hipMemcpyAsync(vk->ab.p, ab, 48 * 8, hipMemcpyHostToDevice, c.stream));
+  const uint32_t nfe = 2 * kPreparedSteps * 4;
+  hipLaunchKernelGGL(k_std_to_limbs, dim3((nfe + 63) / 64), dim3(64), 0, c.stream, lines_std.as<uint32_t>(), nfe, vk->lines.as<uint32_t>());
+  GS_HIP(hipGetLastError());
+  GS_HIP(hipStreamSynchronize(c.stream));                               // the host buffers and lines_std end with this call
+  *out = c.put(std::move(vk));
+  return GS_OK;
+}
+
+int vk_info_impl(Ctx& c, const char* fn, const gs_handle* keys, size_t nkeys, uint32_t* npublic) {
+  for (size_t k = 0; k < nkeys; ++k) {
+    GrothVk* vk = c.get<GrothVk>(keys[k], Kind::GrothVk);
+    if (!vk) return fail(GS_ERR_ARG, "%s: keys[%zu] is not a prepared verification key (gs_groth16_vk_create)", fn, k);
+    npublic[k] = (uint32_t)vk->npublic;
+  }
+  return GS_OK;
+}
+
+// member[s], is_one[s] for every SLOT s (64 per group); a, b, c hold the proofs' points in slot order, pub the signals in slot order
+int verify_each_keys_impl(Ctx& c, const char* fn, const gs_handle* keys, size_t nkeys, gs_handle ha, gs_handle hb, gs_handle hc, const VerifyGroup* groups,
+                          size_t ngroups, const uint64_t* pub, uint64_t nsignals, int* member, int* is_one) {
+  Bases* as = c.get<Bases>(ha, Kind::G1Bases);
+  Bases* bs = c.get<Bases>(hb, Kind::G2Bases);
+  Bases* cs = c.get<Bases>(hc, Kind::G1Bases);
+  if (!as || !bs || !cs) return fail(GS_ERR_ARG, "%s: bad base-array handle", fn);
+  const size_t n = ngroups * kPairBlock;                                // slots
+  if (!ngroups || n >= 0xffffffffull) return fail(GS_ERR_SHAPE, "%s: %zu slots, indices are 32 bits", fn, n);
+  if (as->n != n || bs->n != n || cs->n != n) return fail(GS_ERR_SHAPE, "%s: the arrays do not hold %zu slots", fn, n);
+  std::vector<VkRecord> table(nkeys);
+  for (size_t k = 0; k < nkeys; ++k) {
+    GrothVk* vk = c.get<GrothVk>(keys[k], Kind::GrothVk);
+    if (!vk) return fail(GS_ERR_ARG, "%s: keys[%zu] is not a prepared verification key on logical device %d", fn, k, c.logical);
+    table[k] = VkRecord{vk->lines.as<uint32_t>(), vk->ic->buf.as<uint32_t>(), vk->ab.as<uint64_t>(), (uint32_t)vk->npublic, vk->skip_gamma ? 1u : 0u,
+                        vk->skip_delta ? 1u : 0u, 0u};
+  }
+  uint64_t expect = 0;                                                  // the plan against the keys as they are now, under the lock
+  for (size_t g = 0; g < ngroups; ++g) {
+    if (groups[g].key >= nkeys || !groups[g].valid || groups[g].valid > (uint32_t)kPairBlock || groups[g].sig_off != expect)
+      return fail(GS_ERR_ARG, "%s: group %zu does not fit its key", fn, g);
+    expect += (uint64_t)groups[g].valid * table[groups[g].key].npublic;
+  }
+  if (expect != nsignals) return fail(GS_ERR_ARG, "%s: %llu signals for slots that take %llu", fn, (unsigned long long)nsignals, (unsigned long long)expect);
+  c.drain();
+  constexpr int kAw = PointIO<FqTag>::kAffineWords;
+  const size_t pub_bytes = (size_t)nsignals * 32;
+  DevBuf ws(ngroups * kWorkspaceWords * 4), vals(n * kF12Words * 4), flags(n * 4), members(n * 4), vkx(n * kAw * 4);
+  DevBuf dpub(pub_bytes ? pub_bytes : 32), dkeys(nkeys * sizeof(VkRecord)), dgroups(ngroups * sizeof(VerifyGroup));
+  PhaseTimer t(c.stream), tu(c.stream);
+  if (pub_bytes) GS_HIP(hipMemcpyAsync(dpub.p, pub, pub_bytes, hipMemcpyHostToDevice, c.stream));
+  GS_HIP(hipMemcpyAsync(dkeys.p, table.data(), nkeys * sizeof(VkRecord), hipMemcpyHostToDevice, c.stream));
+  GS_HIP(hipMemcpyAsync(dgroups.p, groups, ngroups * sizeof(VerifyGroup), hipMemcpyHostToDevice, c.stream));
+  GS_HIP(hipMemsetAsync(vkx.p, 0, n * kAw * 4, c.stream));              // infinity in the padded slots
+  tu.stop();
+  PhaseTimer tmem(c.stream);
+  hipLaunchKernelGGL(k_g2_member_flags, dim3((unsigned)ngroups), dim3(kPairBlock), 0, c.stream, bs->buf.as<uint32_t>(), (uint32_t)n, members.as<uint32_t>());
+  GS_HIP(hipGetLastError());
+  tmem.stop();
+  PhaseTimer tv(c.stream);
+  hipLaunchKernelGGL(k_groth16_vkx_keys, dim3((unsigned)ngroups), dim3(kPairBlock), 0, c.stream, dkeys.as<VkRecord>(), dgroups.as<VerifyGroup>(),
+                     dpub.as<uint32_t>(), vkx.as<uint32_t>());
+  GS_HIP(hipGetLastError());
+  tv.stop();
+  PhaseTimer tm(c.stream);
+  hipLaunchKernelGGL(k_miller_groth16_keys, dim3((unsigned)ngroups), dim3(kPairBlock), 0, c.stream, as->buf.as<uint32_t>(), bs->buf.as<uint32_t>(),
+                     cs->buf.as<uint32_t>(), vkx.as<uint32_t>(), dkeys.as<VkRecord>(), dgroups.as<VerifyGroup>(), ws.as<uint32_t>());
+  GS_HIP(hipGetLastError());
+  tm.stop();
+  PhaseTimer tf(c.stream);
+  hipLaunchKernelGGL(k_final_exp, dim3((unsigned)ngroups), dim3(kPairBlock), 0, c.stream, ws.as<uint32_t>(), (uint32_t)n, vals.as<uint32_t>(),
+                     flags.as<uint32_t>());
+  GS_HIP(hipGetLastError());
+  tf.stop();
+  t.stop();
+  std::vector<uint32_t> hf(n), hm(n);
+  GS_HIP(hipMemcpyAsync(hf.data(), flags.p, n * 4, hipMemcpyDeviceToHost, c.stream));
+  GS_HIP(hipMemcpyAsync(hm.data(), members.p, n * 4, hipMemcpyDeviceToHost, c.stream));
+  GS_HIP(hipStreamSynchronize(c.stream));                               // the pageable host tables above are read by now
+  for (size_t i = 0; i < n; ++i) { is_one[i] = (int)hf[i]; member[i] = (int)hm[i]; }
+  reset_timing(c);
+  c.timing.total_ms = t.ms();
+  c.timing.h2d_ms = tu.ms();                                           // signals, the key table, the group table
+  c.timing.poly_ms = tmem.ms();                                        // membership of the B_i
+  c.timing.plan_ms = tv.ms();                                          // vkx
+  c.timing.accumulate_ms = tm.ms();                                    // the Miller loops
+  c.timing.reduce_ms = tf.ms();                                        // the final exponentiations
+  return GS_OK;
+}
+
 // ---- a verdict per Pinocchio proof: gs_pinocchio_verify_each (verify.hip) -------------------------------------------------------
 // The five equations of snark.VerifyProof as products equal to one.  Six G2 points are the same in every lane and arrive as prepared
 // lists, in this order:
@@ -535,6 +692,23 @@ int pinocchio_verify_each_device(const char* fn, gs_handle g1, gs_handle hb, gs_
                  false, g1);
 }
 void f12_words(const pairing::Fp12& f, uint64_t* out) { host_f12_to_std(f, out); }
+
+// for gs_groth16_vk_create (verify.hip): the key object over an uploaded IC array (the object keeps the array alive, the caller frees
+// its handle), the prepared lists (null for an infinite gamma / delta) and the Miller value of e(alpha, beta)
+int groth16_vk_install(const char* fn, gs_handle hic, size_t nic, const uint64_t* gamma_lines, const uint64_t* delta_lines, const uint64_t* ab,
+                       gs_handle* out) {
+  return guarded([&](Ctx& ctx) -> int { return vk_install_impl(ctx, fn, hic, nic, gamma_lines, delta_lines, ab, out); }, true, true, hic);
+}
+// for gs_groth16_verify_each_keys (verify.hip): npublic of every key; GS_ERR_ARG for a handle that is not a prepared key
+int groth16_vk_info(const char* fn, const gs_handle* keys, size_t nkeys, uint32_t* npublic) {
+  return guarded([&](Ctx& ctx) -> int { return vk_info_impl(ctx, fn, keys, nkeys, npublic); }, true, true, nkeys ? keys[0] : 0);
+}
+// per SLOT of the plan (verify_plan.h), is B in G2 and is the exponentiated product of the four pairs one
+int groth16_verify_each_keys_device(const char* fn, const gs_handle* keys, size_t nkeys, gs_handle ha, gs_handle hb, gs_handle hc,
+                                    const VerifyGroup* groups, size_t ngroups, const uint64_t* pub, uint64_t nsignals, int* member, int* is_one) {
+  return guarded([&](Ctx& ctx) -> int { return verify_each_keys_impl(ctx, fn, keys, nkeys, ha, hb, hc, groups, ngroups, pub, nsignals, member, is_one); },
+                 true, false, ha);
+}
 
 }  // namespace gs
 

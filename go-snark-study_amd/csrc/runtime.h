@@ -121,7 +121,7 @@ struct DevBuf {
 };
 
 // ---- handle table ---------------------------------------------------------------------------------
-enum class Kind : uint32_t { G1Bases = 1, G2Bases, Scalars, GrothPk, PinocchioPk, R1cs };
+enum class Kind : uint32_t { G1Bases = 1, G2Bases, Scalars, GrothPk, PinocchioPk, R1cs, GrothVk };
 
 struct Object {
   Kind kind;
@@ -135,6 +135,14 @@ struct Bases : Object {          // packed affine Montgomery points, resident (+
   size_t n = 0;
   std::shared_ptr<BaseTable> table;   // created on first MSM use (tables.h, table_of)
   explicit Bases(Kind k) : Object(k) {}
+};
+struct GrothVk : Object {        // a prepared Groth16 verification key (gs_groth16_vk_create: verify.hip, pairing_device.hip)
+  std::shared_ptr<Bases> ic;     // the nic = npublic + 1 IC points
+  DevBuf lines;                  // the prepared lines of gamma, then of delta, as limbs (zeros for an infinite point)
+  DevBuf ab;                     // the Miller value of e(alpha, beta): 48 words, standard encoding
+  size_t npublic = 0;
+  bool skip_gamma = false, skip_delta = false;      // gamma / delta is the point at infinity: its pair contributes one
+  GrothVk() : Object(Kind::GrothVk) {}
 };
 struct R1csObj : Object {        // sparse R1CS resident on the device: A, B, C in CSR (values standard form) + per-proof workspaces
   size_t n = 0, m = 0, nnz[3] = {0, 0, 0};

@@ -5,6 +5,7 @@
 
 #include "pairing.h"
 #include "runtime.h"
+#include "verify_plan.h"
 
 using namespace gs;
 using namespace gs::pairing;
@@ -205,6 +206,11 @@ int groth16_verify_each_device(const char* fn, gs_handle ha, gs_handle hb, gs_ha
 void f12_words(const pairing::Fp12& f, uint64_t* out);
 int pinocchio_verify_each_device(const char* fn, gs_handle g1, gs_handle hb, gs_handle hic, gs_handle key, const uint64_t* pub, size_t npublic, size_t n,
                                  const uint64_t* lines, unsigned skip_mask, int* member, int* one);
+int groth16_vk_install(const char* fn, gs_handle hic, size_t nic, const uint64_t* gamma_lines, const uint64_t* delta_lines, const uint64_t* ab,
+                       gs_handle* out);
+int groth16_vk_info(const char* fn, const gs_handle* keys, size_t nkeys, uint32_t* npublic);
+int groth16_verify_each_keys_device(const char* fn, const gs_handle* keys, size_t nkeys, gs_handle ha, gs_handle hb, gs_handle hc,
+                                    const VerifyGroup* groups, size_t ngroups, const uint64_t* pub, uint64_t nsignals, int* member, int* is_one);
 }
 
 namespace {
@@ -285,6 +291,13 @@ struct HandleBag {
   gs_handle hs[4] = {0, 0, 0, 0};
   ~HandleBag() { for (gs_handle h : hs) if (h) (void)gs_free(h); }
 };
+
+// what gs_groth16_verify tests of one proof before its pairings: under strict mode canonical signals and coordinates, and always the
+// three points on their curves.  false: the proof's verdict is 0 and the point at infinity travels in place of its points.
+bool groth16_proof_passes_screen(bool strict, const uint64_t* pub, size_t npublic, const uint64_t* a, const uint64_t* b, const uint64_t* c) {
+  if (strict && (!scalars_canonical(pub, npublic) || !coords_canonical(a, 3) || !coords_canonical(b, 6) || !coords_canonical(c, 3))) return false;
+  return g1_on_curve(g1_from_jacobian_std(a)) && g2_on_curve(g2_from_jacobian_std(b)) && g1_on_curve(g1_from_jacobian_std(c));
+}
 
 }  // namespace
 
@@ -421,14 +434,7 @@ int gs_groth16_verify_each(const uint64_t vk_g1_alpha[12], const uint64_t vk_g2_
     std::vector<uint64_t> a(pi_a, pi_a + 12 * n), b(pi_b, pi_b + 24 * n), c(pi_c, pi_c + 12 * n);
     std::vector<char> bad(n, 0);
     for (size_t i = 0; i < n; ++i) {
-      bool good = true;
-      if (strict && (!scalars_canonical(public_signals + 4 * i * npublic, npublic) || !coords_canonical(pi_a + 12 * i, 3) ||
-                     !coords_canonical(pi_b + 24 * i, 6) || !coords_canonical(pi_c + 12 * i, 3)))
-        good = false;
-      if (good && (!g1_on_curve(g1_from_jacobian_std(pi_a + 12 * i)) || !g2_on_curve(g2_from_jacobian_std(pi_b + 24 * i)) ||
-                   !g1_on_curve(g1_from_jacobian_std(pi_c + 12 * i))))
-        good = false;
-      if (!good) {
+      if (!groth16_proof_passes_screen(strict, public_signals + 4 * i * npublic, npublic, pi_a + 12 * i, pi_b + 24 * i, pi_c + 12 * i)) {
         bad[i] = 1;
         memset(a.data() + 12 * i, 0, 96);
         memset(b.data() + 24 * i, 0, 192);
@@ -445,6 +451,114 @@ int gs_groth16_verify_each(const uint64_t vk_g1_alpha[12], const uint64_t vk_g2_
     uint64_t count = 0;
     for (size_t i = 0; i < n; ++i) {
       ok_each[i] = (!bad[i] && member[i] && one[i]) ? 1 : 0;
+      count += ok_each[i] ? 0 : 1;
+    }
+    if (nbad) *nbad = count;
+    return GS_OK;
+  });
+}
+
+// gs_groth16_vk_create (include/gosnark_hip.h): the per-key host work of gs_groth16_verify_each, done once: the curve tests of the key,
+// the Miller value of e(alpha, beta) and the prepared lines of gamma and delta, kept on the device beside the IC points.  Where
+// gs_groth16_verify_each answers a key that cannot verify anything with all-zero verdicts, this call refuses to install it.
+int gs_groth16_vk_create(const uint64_t vk_g1_alpha[12], const uint64_t vk_g2_beta[24], const uint64_t vk_g2_gamma[24],
+                         const uint64_t vk_g2_delta[24], const uint64_t* vk_ic, size_t nic, gs_handle* out) {
+  return host_guarded([&]() -> int {
+    const char* fn = "gs_groth16_vk_create";
+    if (!vk_g1_alpha || !vk_g2_beta || !vk_g2_gamma || !vk_g2_delta || !out || (nic && !vk_ic)) return fail(GS_ERR_ARG, "%s: null argument", fn);
+    if (!nic) return fail(GS_ERR_SHAPE, "%s: a key has at least IC[0]", fn);
+    // the IC points go up first: without a device this is where the call ends, before any work and with nothing written
+    HandleBag bag;
+    gs_handle* hic = &bag.hs[0];
+    int rc = gs_g1_upload(vk_ic, nic, hic);
+    if (rc == GS_ERR_ARG) {
+      for (size_t j = 0; j < nic; ++j)
+        if (!g1_on_curve(g1_from_jacobian_std(vk_ic + 12 * j))) return fail(GS_ERR_ARG, "%s: IC[%zu] is not on the curve", fn, j);
+    }
+    if (rc != GS_OK) return rc;
+    const G1Aff alpha = g1_from_jacobian_std(vk_g1_alpha);
+    const G2Aff beta = g2_from_jacobian_std(vk_g2_beta), gamma = g2_from_jacobian_std(vk_g2_gamma), delta = g2_from_jacobian_std(vk_g2_delta);
+    if (!g1_on_curve(alpha)) return fail(GS_ERR_ARG, "%s: alpha is not on the curve", fn);
+    if (!g2_on_curve(beta)) return fail(GS_ERR_ARG, "%s: beta is not on the twist", fn);
+    if (!g2_on_curve(gamma)) return fail(GS_ERR_ARG, "%s: gamma is not on the twist", fn);
+    if (!g2_on_curve(delta)) return fail(GS_ERR_ARG, "%s: delta is not on the twist", fn);
+    Fp12 fab;
+    if (!multi_miller_loop({alpha}, {beta}, fab)) return fail(GS_ERR_ARG, "%s: beta is not of order r (a degenerate step in its Miller loop)", fn);
+    uint64_t ab[48];
+    gs::f12_words(fab, ab);
+    std::vector<uint64_t> gl, dl;
+    if (!gamma.inf && !prepare_g2_lines(gamma, gl)) return fail(GS_ERR_ARG, "%s: gamma is not of order r (a degenerate step in its prepared lines)", fn);
+    if (!delta.inf && !prepare_g2_lines(delta, dl)) return fail(GS_ERR_ARG, "%s: delta is not of order r (a degenerate step in its prepared lines)", fn);
+    gs_handle h = 0;
+    if ((rc = gs::groth16_vk_install(fn, *hic, nic, gamma.inf ? nullptr : gl.data(), delta.inf ? nullptr : dl.data(), ab, &h)) != GS_OK) return rc;
+    *out = h;
+    return GS_OK;
+  });
+}
+
+// gs_groth16_verify_each_keys (include/gosnark_hip.h): gs_groth16_verify_each for proofs that each name their key.  The keys are
+// prepared objects, so what is left for the host is per proof: the screening of the 3n points and the permutation into the slot order
+// of verify_plan.h, one key per one-wave workgroup.
+int gs_groth16_verify_each_keys(const gs_handle* keys, size_t nkeys, const uint32_t* key_of_proof, const uint64_t* public_signals,
+                                const uint64_t* pi_a, const uint64_t* pi_b, const uint64_t* pi_c, size_t nproofs, int* ok_each, uint64_t* nbad) {
+  return host_guarded([&]() -> int {
+    const char* fn = "gs_groth16_verify_each_keys";
+    const size_t n = nproofs;
+    if ((nkeys && !keys) || (n && (!key_of_proof || !pi_a || !pi_b || !pi_c || !ok_each))) return fail(GS_ERR_ARG, "%s: null argument", fn);
+    if (!n) {
+      if (nbad) *nbad = 0;
+      return GS_OK;
+    }
+    for (size_t i = 0; i < n; ++i)
+      if (key_of_proof[i] >= nkeys) return fail(GS_ERR_ARG, "%s: key_of_proof[%zu] = %u, the call has %zu keys", fn, i, key_of_proof[i], nkeys);
+    for (size_t k = 1; k < nkeys; ++k)
+      if (handle_device(keys[k]) != handle_device(keys[0]))
+        return fail(GS_ERR_ARG, "%s: keys[%zu] lives on logical device %d, keys[0] on %d", fn, k, handle_device(keys[k]), handle_device(keys[0]));
+    // the keys' signal counts: without a device this is where the call ends, before any work and with nothing written
+    std::vector<uint32_t> npublic(nkeys);
+    int rc = gs::groth16_vk_info(fn, keys, nkeys, npublic.data());
+    if (rc != GS_OK) return rc;
+    const int here = gs_get_device();                                   // the proofs' arrays are created where the calling thread works
+    if (handle_device(keys[0]) != here)
+      return fail(GS_ERR_ARG, "%s: the keys live on logical device %d, the calling thread works on %d (gs_set_device)", fn, handle_device(keys[0]), here);
+    VerifyPlan plan;
+    const VerifyPlanStatus ps = plan_verify_slots(key_of_proof, n, nkeys, npublic.data(), plan);
+    if (ps != kVpOk) return fail(GS_ERR_SHAPE, "%s: %zu proofs need more than 2^32 slots (64 per key and started group): pass them in windows", fn, n);
+    if (plan.nsignals && !public_signals) return fail(GS_ERR_ARG, "%s: null argument", fn);
+    const bool strict = g_strict.load() != 0;
+    // the proofs in slot order: per proof what the single verifier tests before its pairings; infinity in bad and in padded slots
+    const size_t slots = plan.proof_of_slot.size();
+    std::vector<uint64_t> a(12 * slots, 0), b(24 * slots, 0), c(12 * slots, 0), pub(plan.nsignals ? 4 * (size_t)plan.nsignals : 4, 0);
+    std::vector<const uint64_t*> pub_of(n);
+    {
+      const uint64_t* at = public_signals;
+      for (size_t i = 0; i < n; ++i) { pub_of[i] = at; at += 4 * (size_t)npublic[key_of_proof[i]]; }
+    }
+    std::vector<char> bad(n, 0);
+    for (size_t g = 0; g < plan.groups.size(); ++g) {
+      const size_t np = npublic[plan.groups[g].key];
+      for (uint32_t l = 0; l < plan.groups[g].valid; ++l) {
+        const size_t s = g * kVpLanes + l, i = plan.proof_of_slot[s];
+        if (np) memcpy(pub.data() + 4 * ((size_t)plan.groups[g].sig_off + l * np), pub_of[i], 32 * np);
+        if (!groth16_proof_passes_screen(strict, pub_of[i], np, pi_a + 12 * i, pi_b + 24 * i, pi_c + 12 * i)) { bad[i] = 1; continue; }
+        memcpy(a.data() + 12 * s, pi_a + 12 * i, 96);
+        memcpy(b.data() + 24 * s, pi_b + 24 * i, 192);
+        memcpy(c.data() + 12 * s, pi_c + 12 * i, 96);
+      }
+    }
+    HandleBag bag;
+    gs_handle *ha = &bag.hs[0], *hb = &bag.hs[1], *hc = &bag.hs[2];
+    if ((rc = gs_g1_upload(a.data(), slots, ha)) != GS_OK) return rc;
+    if ((rc = gs_g2_upload(b.data(), slots, hb)) != GS_OK) return rc;
+    if ((rc = gs_g1_upload(c.data(), slots, hc)) != GS_OK) return rc;
+    std::vector<int> member(slots), one(slots);
+    rc = gs::groth16_verify_each_keys_device(fn, keys, nkeys, *ha, *hb, *hc, plan.groups.data(), plan.groups.size(), pub.data(), plan.nsignals,
+                                             member.data(), one.data());
+    if (rc != GS_OK) return rc;
+    uint64_t count = 0;
+    for (size_t i = 0; i < n; ++i) {
+      const size_t s = plan.slot_of_proof[i];
+      ok_each[i] = (!bad[i] && member[s] && one[s]) ? 1 : 0;
       count += ok_each[i] ? 0 : 1;
     }
     if (nbad) *nbad = count;

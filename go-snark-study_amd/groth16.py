@@ -438,6 +438,61 @@ def _verify_each_words(vk, abc, publicSignalsList, npublic):
     return [bool(x) for x in ok[:n]]
 
 
+class DeviceVk:
+    """A verification key prepared and resident on the device (gs_groth16_vk_create): its IC points, the prepared lines of gamma and
+    delta and the Miller value of e(alpha, beta).  `handle` is freed like the other device objects; `npublic` = len(vk.IC) - 1."""
+
+    def __init__(self, handle, npublic):
+        self.handle, self.npublic = handle, npublic
+
+
+def PrepareVerificationKey(vk):
+    """Do once per key what VerifyProofsEach does per call -- the curve tests of the key, the Miller value of e(alpha, beta), the
+    prepared lines of gamma and delta -- and keep the result on the device -> DeviceVk, for VerifyProofsEachKeys.  A key that cannot
+    verify anything (a point off its curve, a G2 point that is not of order r) raises GosnarkHipError naming the point, where
+    VerifyProofsEach would answer False for every proof."""
+    g2 = capi.g2_points_to_u64([vk.G2_Beta, vk.G2_Gamma, vk.G2_Delta])
+    handle = capi.groth16_vk_create(capi.g1_points_to_u64([vk.G1_Alpha])[0], g2[0], g2[1], g2[2], capi.g1_points_to_u64(vk.IC))
+    return DeviceVk(handle, len(vk.IC) - 1)
+
+
+def VerifyProofsEachKeys(keys, key_of_proof, proofs, publicSignalsList):
+    """Proofs of MANY verification keys in one call, a verdict for each, on the device (gs_groth16_verify_each_keys) -> list[bool]:
+    exactly [VerifyProof(vk of keys[key_of_proof[i]], proofs[i], publicSignalsList[i]) for i ...].  `keys` are DeviceVk objects from
+    PrepareVerificationKey (the same one may appear twice, one may have no proofs); every proof brings exactly its key's npublic
+    signals.  One call costs the latency of one wave's loop however many keys it names, where VerifyProofsEach per key costs it once
+    per key.  A proof whose key index is out of range raises GosnarkHipError; a length mismatch ValueError."""
+    return _verify_each_keys_words(keys, key_of_proof, _proof_words(proofs), publicSignalsList, "VerifyProofsEachKeys")
+
+
+def _verify_each_keys_words(keys, key_of_proof, abc, publicSignalsList, what):
+    key_of_proof = [int(k) for k in key_of_proof]
+    n = len(publicSignalsList)
+    if len(key_of_proof) != n or len(abc[0]) != n:
+        raise ValueError("%s: %d proofs, %d key indices, %d lists of public signals" % (what, len(abc[0]), len(key_of_proof), n))
+    for i, (k, s) in enumerate(zip(key_of_proof, publicSignalsList)):
+        if 0 <= k < len(keys) and len(s) != keys[k].npublic:
+            raise ValueError("%s: proof %d has %d public signals, its key (keys[%d]) takes %d" % (what, i, len(s), k, keys[k].npublic))
+        if k < 0:
+            raise ValueError("%s: proof %d has the key index %d" % (what, i, k))
+    flat = [int(x) % capi.R for s in publicSignalsList for x in s]
+    pub = capi.ints_to_u64(flat) if flat else np.zeros((1, 4), dtype=np.uint64)
+    ok, _ = capi.groth16_verify_each_keys(keys, key_of_proof, pub, *abc)
+    return [bool(x) for x in ok]
+
+
+def VerifyProofsEachKeysCompressed(keys, key_of_proof, blobs, publicSignalsList, codec):
+    """VerifyProofsEachKeys on proofs as they arrive over a wire (128 bytes each, see VerifyProofsEachCompressed): the points are
+    decompressed on the device, then go to gs_groth16_verify_each_keys -> list[bool], False for a proof with a point that does not
+    decompress; the other verdicts are unaffected by it."""
+    from . import compressed
+    if len(blobs) != len(publicSignalsList):
+        raise ValueError("VerifyProofsEachKeysCompressed: %d proofs, %d lists of public signals" % (len(blobs), len(publicSignalsList)))
+    a, b, c, ok = compressed.decompress_proof_arrays(blobs, codec)
+    got = _verify_each_keys_words(keys, key_of_proof, (a, b, c), publicSignalsList, "VerifyProofsEachKeysCompressed")
+    return [bool(v and o) for v, o in zip(got, ok)]
+
+
 def VerifyProofs(vk, proofs, publicSignalsList, seed=None):
     """Many proofs of ONE verification key in one randomised check on the device (gs_groth16_verify_batch) -> bool: the answer of
     all(VerifyProof(vk, p, s) ...), wrong with probability at most (len(proofs) - 1) / r, and only towards True.  The challenge is

@@ -7,6 +7,7 @@ import "C"
 
 import (
 	"errors"
+	"fmt"
 	"math/big"
 	"runtime"
 )
@@ -192,6 +193,133 @@ func Groth16VerifyEach(vk Groth16VkParts, proofs []Groth16BatchProof, order *big
 	runtime.KeepAlive(ic)
 	runtime.KeepAlive(g1)
 	runtime.KeepAlive(g2)
+	runtime.KeepAlive(pub)
+	runtime.KeepAlive(a)
+	runtime.KeepAlive(b)
+	runtime.KeepAlive(c)
+	runtime.KeepAlive(oks)
+	if err != nil {
+		return nil, err
+	}
+	out := make([]bool, len(proofs))
+	for i := range out {
+		out[i] = oks[i] == 1
+	}
+	return out, nil
+}
+
+// Groth16Vk is a verification key prepared and resident on the device (gs_groth16_vk_create): its IC points, the prepared lines of
+// gamma and delta and the Miller value of e(alpha, beta).  NPublic = len(IC) - 1.
+type Groth16Vk struct {
+	h       Handle
+	NPublic int
+}
+
+// Handle exposes the raw gs_handle.
+func (k *Groth16Vk) Handle() Handle { return k.h }
+
+// Free releases the key's device memory.
+func (k *Groth16Vk) Free() error {
+	h := k.h
+	k.h = 0
+	return Free(h)
+}
+
+// Groth16VkCreate does once per key what Groth16VerifyEach does per call -- the curve tests of the key, the Miller value of
+// e(alpha, beta), the prepared lines of gamma and delta -- and keeps the result on logical device `device` (gs_groth16_vk_create).  A
+// key that cannot verify anything (a point off its curve, a G2 point that is not of order r) is refused with an error that names the
+// point.  Needs Init.  Call sequence = tests/c/verify_each_keys.c.
+func Groth16VkCreate(device int, vk Groth16VkParts) (*Groth16Vk, error) {
+	ic, err := G1Points(vk.IC)
+	if err != nil {
+		return nil, err
+	}
+	if len(vk.IC) == 0 {
+		return nil, errors.New("gosnarkhip: a verification key has at least IC[0]")
+	}
+	g1, err := G1Points([][3]*big.Int{vk.G1Alpha})
+	if err != nil {
+		return nil, err
+	}
+	g2, err := G2Points([][3][2]*big.Int{vk.G2Beta, vk.G2Gamma, vk.G2Delta})
+	if err != nil {
+		return nil, err
+	}
+	var h C.gs_handle
+	err = onDevice(device, func() C.int {
+		return C.gs_groth16_vk_create(ptr(g1[0:]), ptr(g2[0:]), ptr(g2[24:]), ptr(g2[48:]), ptr(ic), C.size_t(len(vk.IC)), &h)
+	})
+	runtime.KeepAlive(ic)
+	runtime.KeepAlive(g1)
+	runtime.KeepAlive(g2)
+	if err != nil {
+		return nil, err
+	}
+	return &Groth16Vk{h: Handle(h), NPublic: len(vk.IC) - 1}, nil
+}
+
+// Groth16VerifyEachKeys gives the verdict of Groth16Verify for every proof of a batch in which each proof names its key: proof i is
+// checked under keys[keyOfProof[i]] (gs_groth16_verify_each_keys).  One call costs the latency of one wave's loop however many keys
+// it names.  Every proof brings exactly NPublic signals of its key; the same key may appear twice and a key may have no proofs.  The
+// keys live on logical device `device`.  A proof with a point off its curve, a B outside the order-r subgroup or (under strict mode) a
+// non-canonical encoding gets false and is not an error; a key index out of range is.  Needs Init.  Call sequence =
+// tests/c/verify_each_keys.c.
+func Groth16VerifyEachKeys(device int, keys []*Groth16Vk, keyOfProof []int, proofs []Groth16BatchProof, order *big.Int) ([]bool, error) {
+	if len(keyOfProof) != len(proofs) {
+		return nil, errors.New("gosnarkhip: one key index per proof")
+	}
+	if len(proofs) == 0 {
+		return []bool{}, nil
+	}
+	if len(keys) == 0 {
+		return nil, errors.New("gosnarkhip: proofs but no keys")
+	}
+	hs := make([]C.gs_handle, len(keys))
+	for i, k := range keys {
+		hs[i] = C.gs_handle(k.h)
+	}
+	kop := make([]C.uint32_t, len(proofs))
+	as := make([][3]*big.Int, 0, len(proofs))
+	bs := make([][3][2]*big.Int, 0, len(proofs))
+	cs := make([][3]*big.Int, 0, len(proofs))
+	signals := make([]*big.Int, 0, len(proofs))
+	for i, p := range proofs {
+		if keyOfProof[i] < 0 || keyOfProof[i] >= len(keys) {
+			return nil, fmt.Errorf("gosnarkhip: proof %d names key %d of %d", i, keyOfProof[i], len(keys))
+		}
+		if len(p.PublicSignals) != keys[keyOfProof[i]].NPublic {
+			return nil, fmt.Errorf("gosnarkhip: proof %d has %d public signals, its key takes %d", i, len(p.PublicSignals), keys[keyOfProof[i]].NPublic)
+		}
+		kop[i] = C.uint32_t(keyOfProof[i])
+		as, bs, cs = append(as, p.PiA), append(bs, p.PiB), append(cs, p.PiC)
+		signals = append(signals, p.PublicSignals...)
+	}
+	a, err := G1Points(as)
+	if err != nil {
+		return nil, err
+	}
+	b, err := G2Points(bs)
+	if err != nil {
+		return nil, err
+	}
+	c, err := G1Points(cs)
+	if err != nil {
+		return nil, err
+	}
+	pub, err := Scalars(signals, order)
+	if err != nil {
+		return nil, err
+	}
+	if len(pub) == 0 {
+		pub = make([]uint64, 4)
+	}
+	oks := make([]C.int, len(proofs))
+	var nbad C.uint64_t
+	err = onDevice(device, func() C.int {
+		return C.gs_groth16_verify_each_keys(&hs[0], C.size_t(len(keys)), &kop[0], ptr(pub), ptr(a), ptr(b), ptr(c), C.size_t(len(proofs)), &oks[0], &nbad)
+	})
+	runtime.KeepAlive(hs)
+	runtime.KeepAlive(kop)
 	runtime.KeepAlive(pub)
 	runtime.KeepAlive(a)
 	runtime.KeepAlive(b)

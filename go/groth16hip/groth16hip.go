@@ -459,6 +459,33 @@ func VerifyProofsEach(vk groth16.Vk, proofs []groth16.Proof, publicSignals [][]*
 	return oks
 }
 
+// PrepareVerificationKey does once per key what VerifyProofsEach does per call and keeps the result on the device
+// (gosnarkhip.Groth16VkCreate), for VerifyProofsEachKeys.  A key that cannot verify anything is refused with an error that names the
+// offending point.
+func PrepareVerificationKey(vk groth16.Vk) (*gosnarkhip.Groth16Vk, error) {
+	return gosnarkhip.Groth16VkCreate(Device, gosnarkhip.Groth16VkParts{
+		IC: vk.IC, G1Alpha: vk.G1.Alpha, G2Beta: vk.G2.Beta, G2Gamma: vk.G2.Gamma, G2Delta: vk.G2.Delta,
+	})
+}
+
+// VerifyProofsEachKeys gives VerifyProof's answer for every proof of a batch whose proofs belong to many verification keys: proof i is
+// checked under keys[keyOfProof[i]] (gosnarkhip.Groth16VerifyEachKeys), all keys side by side in one call.  An error (no device,
+// ragged input, a key index out of range, a signal count that is not the key's) reads as nil.
+func VerifyProofsEachKeys(keys []*gosnarkhip.Groth16Vk, keyOfProof []int, proofs []groth16.Proof, publicSignals [][]*big.Int) []bool {
+	if len(proofs) != len(publicSignals) || len(proofs) != len(keyOfProof) {
+		return nil
+	}
+	batch := make([]gosnarkhip.Groth16BatchProof, len(proofs))
+	for i, p := range proofs {
+		batch[i] = gosnarkhip.Groth16BatchProof{PiA: p.PiA, PiB: p.PiB, PiC: p.PiC, PublicSignals: publicSignals[i]}
+	}
+	oks, err := gosnarkhip.Groth16VerifyEachKeys(Device, keys, keyOfProof, batch, groth16.Utils.FqR.Q)
+	if err != nil {
+		return nil
+	}
+	return oks
+}
+
 // VerifyProofsEachCompressed is VerifyProofsEach on proofs as they arrive over a wire: 128 bytes each, A | B | C, compressed points in
 // the layout `codec` (gosnarkhip.Gnark, .Arkworks, .Bn256Pairing).  The points are decompressed on the device
 // (gosnarkhip.DecompressProofs: one G1 call over A and C, one G2 call) and go to gosnarkhip.Groth16VerifyEach: a proof with a point

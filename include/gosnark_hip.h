@@ -950,6 +950,49 @@ int gs_groth16_verify_each(const uint64_t vk_g1_alpha[12], const uint64_t vk_g2_
                            const uint64_t* public_signals /* nproofs x npublic x 4 */, size_t npublic,
                            const uint64_t* pi_a, const uint64_t* pi_b, const uint64_t* pi_c, size_t nproofs,
                            int* ok_each /* nproofs */, uint64_t* nbad /* may be null */);
+/* ---- proofs of many keys in one call ----
+ * gs_groth16_vk_create: a PREPARED verification key as a device object.  It does once what gs_groth16_verify_each does per call: the
+ * curve tests of the five key points and the IC points, the Miller value of e(alpha, beta), the prepared lines of gamma and delta.  The
+ * object keeps on the device the nic IC points, both prepared lists as limbs (29 KB), the 48 words of the Miller value, npublic =
+ * nic - 1 and the two skip flags of an infinite gamma or delta (allowed, as in the single verifier).  gs_free, gs_handle_bytes,
+ * gs_handle_device and gs_memory_query treat it like any other object.
+ * A key that cannot verify anything is REFUSED when it is installed -- where gs_groth16_verify_each answers such a key with all-zero
+ * verdicts on every call: a key point off its curve is GS_ERR_ARG and the message names the point (alpha, beta, gamma, delta, IC[j]);
+ * a degenerate step in the Miller loop of beta or the prepared lines of gamma or delta (a point of the twist that is not of order r) is
+ * GS_ERR_ARG naming the point.  nic = 0 is GS_ERR_SHAPE, a null argument GS_ERR_ARG; without a device GS_ERR_NOT_INIT.  On every
+ * error nothing is written and nothing stays allocated. */
+int gs_groth16_vk_create(const uint64_t vk_g1_alpha[12], const uint64_t vk_g2_beta[24], const uint64_t vk_g2_gamma[24],
+                         const uint64_t vk_g2_delta[24], const uint64_t* vk_ic /* nic x 12 */, size_t nic, gs_handle* out);
+/* gs_groth16_verify_each_keys: gs_groth16_verify_each for proofs that each NAME THEIR KEY: ok_each[i] is exactly what gs_groth16_verify
+ * writes for (the key keys[key_of_proof[i]], proof i, its signals), in both settings of gs_verify_set_strict.  *nbad (optional) = how
+ * many verdicts are 0.  Every proof brings exactly nic - 1 signals of its key in BOTH settings; the lax rule of the single verifier,
+ * "missing signals count as 0", is what zero padding by the caller gives.
+ * Verdicts, not errors, exactly as in gs_groth16_verify_each: a proof point off its curve gives 0 and infinity travels in its place;
+ * under strict mode a non-canonical coordinate or signal gives 0; a B outside the order-r subgroup gives 0.
+ * Errors, with nothing written: key_of_proof[i] >= nkeys, a bad handle or one of another kind, keys on different logical devices (or
+ * not on the calling thread's: the proofs' arrays are created there), a null argument: GS_ERR_ARG; no device: GS_ERR_NOT_INIT, unless
+ * nproofs = 0, which is GS_OK with *nbad = 0 and needs no device, keys or handles.  The same handle may appear twice in keys; a key may
+ * have no proofs.  Every temporary is freed on every path.  There is no host fallback.  Blocking.
+ * Layout: the Miller-loop kernel is fast because the 2 x 102 prepared lines of a key are the same words for every lane of a wave, so a
+ * wave never mixes keys: the host groups the proofs by key, stably, pads every key's run to a multiple of 64 SLOTS, and one one-wave
+ * workgroup is one key (csrc/verify_plan.h).  The three point arrays and the signals go up in slot order; padded slots hold the point
+ * at infinity, compute on it and are never read back.  Each workgroup reads its group record and then its key record { lines, ic, ab,
+ * npublic, skip_gamma, skip_delta } -- a table uploaded per call from the key objects -- at addresses that are uniform across the
+ * wave; the kernels' bodies are those of gs_groth16_verify_each, and its membership and final-exponentiation kernels run unchanged
+ * over all slots.
+ * Memory: per key 29 KB of lines resident (plus its IC points); per call 135 KB of workspace and 25 KB of values and flags per GROUP
+ * of 64 slots, and a group is started for every key with a proof: 256 keys with one proof each cost what 16384 proofs of one key
+ * cost.  Slots are indexed with 32 bits: a call whose padded runs reach 2^32 slots is GS_ERR_SHAPE; pass the proofs in windows.
+ * Limits, deliberately: no per-lane key (dense packing of keys with few proofs: the lines would become per-lane gathers and the
+ * register budget of the loop is gone), no randomised multi-key batch, no Pinocchio.
+ * gs_last_timing(): total_ms = device time, of which h2d_ms = signals and the two tables, poly_ms = membership, plan_ms = vkx,
+ * accumulate_ms = Miller loops, reduce_ms = final exponentiations.
+ * go-snark-study_amd/groth16.py (PrepareVerificationKey, VerifyProofsEachKeys), go/gosnarkhip/pairing_device.go (Groth16VkCreate,
+ * Groth16VerifyEachKeys) and tests/c/verify_each_keys.c. */
+int gs_groth16_verify_each_keys(const gs_handle* keys, size_t nkeys, const uint32_t* key_of_proof /* nproofs */,
+                                const uint64_t* public_signals /* concatenated in proof order; proof i has nic(key_of_proof[i]) - 1 signals */,
+                                const uint64_t* pi_a, const uint64_t* pi_b, const uint64_t* pi_c, size_t nproofs,
+                                int* ok_each, uint64_t* nbad /* may be NULL */);
 /* gs_pinocchio_verify_each: the verdict of gs_pinocchio_verify for EVERY proof of a batch under one key, on the device: ok_each[i] is
  * exactly what gs_pinocchio_verify writes to *ok for proof i with its signals and failed_each[i] (optional) what it writes to
  * *failed_check -- 0, or 1..5 for the first equation in the reference's order that does not hold -- in both settings of
