@@ -309,6 +309,20 @@ inline Fp6 f6_inv(const Fp6& a) {
 struct Fp12 { Fp6 a0, a1; };
 inline Fp12 f12_one() { return Fp12{f6_one(), f6_zero()}; }
 inline bool f12_eq(const Fp12& a, const Fp12& b) { return f6_eq(a.a0, b.a0) && f6_eq(a.a1, b.a1); }
+// the 48-word standard encoding of gs_pairing, the reference's [2][3][2]*big.Int order: per Fq2 coefficient c0 then c1, four words each
+inline Fp12 f12_from_std(const uint64_t* w) {
+  Fp12 f;
+  Fp2* c[6] = {&f.a0.c0, &f.a0.c1, &f.a0.c2, &f.a1.c0, &f.a1.c1, &f.a1.c2};
+  for (int i = 0; i < 6; ++i) *c[i] = Fp2{fp_from_std(w + 8 * i), fp_from_std(w + 8 * i + 4)};
+  return f;
+}
+inline void f12_to_std(const Fp12& f, uint64_t* out) {
+  const Fp2* c[6] = {&f.a0.c0, &f.a0.c1, &f.a0.c2, &f.a1.c0, &f.a1.c1, &f.a1.c2};
+  for (int i = 0; i < 6; ++i) {
+    fp_to_std(c[i]->c0, out + 8 * i);
+    fp_to_std(c[i]->c1, out + 8 * i + 4);
+  }
+}
 inline Fp12 f12_mul(const Fp12& a, const Fp12& b) {
   Fp6 t0 = f6_mul(a.a0, b.a0), t1 = f6_mul(a.a1, b.a1);
   Fp6 c1 = f6_sub(f6_sub(f6_mul(f6_add(a.a0, a.a1), f6_add(b.a0, b.a1)), t0), t1);

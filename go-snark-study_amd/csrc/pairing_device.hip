@@ -9,14 +9,15 @@
 // The running G2 point, the pair and the line stay in registers.  Partials travel in gs_pairing's standard encoding (96 words).
 //
 // gs_pairing_each: e(P_i, Q_i) for EVERY i.  k_miller_each is the same loop without the product; k_final_exp runs the final
-// exponentiation of finalexp.h per lane ("one value per pair" below).
+// exponentiation of finalexp.h per lane ("one value per pair" below).  The per-proof verifiers (verify.hip, through verify_device.h)
+// put their own Miller kernels in front of the same k_final_exp ("the verify chain" below).
 #include <vector>
 
 #include "finalexp.h"
 #include "miller.h"
-#include "pairing.h"
 #include "point_io.h"
 #include "runtime.h"
+#include "verify_device.h"
 #include "verify_plan.h"
 
 using namespace gs;
@@ -28,8 +29,8 @@ constexpr int kF12Limbs = 12 * NL;
 constexpr int kF12Words = 96;                  // standard encoding, 32-bit words
 constexpr size_t kHostPartials = 4;            // at most this many values are downloaded (a host product is ~3 us, a pass ~a launch)
 
-// the accumulator of one lane: limb k of coefficient i at lds[18 i + k][lane]
-struct LdsF12 {
+// the accumulator of one lane, in LDS or in a slot of the global workspace below: limb k of coefficient i at base[(18 i + k) * 64]
+struct LaneF12 {
   uint32_t* base;
   __device__ __forceinline__ Fq2e<2> get(int i) const {
     Fq2e<2> r;
@@ -50,28 +51,33 @@ __device__ __forceinline__ void wave_product_store(uint32_t (*lds)[kPairBlock], 
   for (int s = kPairBlock / 2; s >= 1; s >>= 1) {
     __syncthreads();
     if (lane < s) {
-      LdsF12 mine{&lds[0][lane]};
-      const LdsF12 other{&lds[0][lane + s]};
+      LaneF12 mine{&lds[0][lane]};
+      const LaneF12 other{&lds[0][lane + s]};
       f12_mul(mine, other);
     }
   }
   __syncthreads();
   if (lane == 0) {
-    const LdsF12 mine{&lds[0][0]};
+    const LaneF12 mine{&lds[0][0]};
     f12_to_std(mine, reinterpret_cast<uint64_t*>(out + (size_t)blockIdx.x * kF12Words));
   }
+}
+
+// pair i of two resident arrays; past the end pair 0 with P at infinity, which contributes one
+struct PairPQ { Affine<FqTag> p; Affine<Fq2Tag> q; };
+__device__ __forceinline__ PairPQ load_pair_or_one(const uint32_t* __restrict__ g1, const uint32_t* __restrict__ g2, size_t i, uint32_t n) {
+  const size_t at = i < n ? i : 0;
+  PairPQ r{PointIO<FqTag>::load_affine(g1 + at * PointIO<FqTag>::kAffineWords), PointIO<Fq2Tag>::load_affine(g2 + at * PointIO<Fq2Tag>::kAffineWords)};
+  if (i >= n) { r.p.x = fe_zero<ModQ, 1>(); r.p.y = fe_zero<ModQ, 1>(); }
+  return r;
 }
 
 __global__ void __launch_bounds__(kPairBlock) k_miller_pairs(const uint32_t* __restrict__ g1, const uint32_t* __restrict__ g2, uint32_t n,
                                                              uint32_t* __restrict__ partial) {
   __shared__ uint32_t lds[kF12Limbs][kPairBlock];
-  const size_t i = (size_t)blockIdx.x * kPairBlock + threadIdx.x;
-  const size_t at = i < n ? i : 0;                                     // lanes past the end read pair 0 and contribute one
-  Affine<FqTag> p = PointIO<FqTag>::load_affine(g1 + at * PointIO<FqTag>::kAffineWords);
-  const Affine<Fq2Tag> q = PointIO<Fq2Tag>::load_affine(g2 + at * PointIO<Fq2Tag>::kAffineWords);
-  if (i >= n) { p.x = fe_zero<ModQ, 1>(); p.y = fe_zero<ModQ, 1>(); }
-  LdsF12 f{&lds[0][threadIdx.x]};
-  miller_loop(f, p, q);
+  const PairPQ pq = load_pair_or_one(g1, g2, (size_t)blockIdx.x * kPairBlock + threadIdx.x, n);
+  LaneF12 f{&lds[0][threadIdx.x]};
+  miller_loop(f, pq.p, pq.q);
   wave_product_store(lds, partial);
 }
 
@@ -79,7 +85,7 @@ __global__ void __launch_bounds__(kPairBlock) k_miller_pairs(const uint32_t* __r
 __global__ void __launch_bounds__(kPairBlock) k_f12_product(const uint32_t* __restrict__ in, uint32_t m, uint32_t* __restrict__ out) {
   __shared__ uint32_t lds[kF12Limbs][kPairBlock];
   const size_t i = (size_t)blockIdx.x * kPairBlock + threadIdx.x;
-  LdsF12 f{&lds[0][threadIdx.x]};
+  LaneF12 f{&lds[0][threadIdx.x]};
   if (i < m) f12_from_std(f, reinterpret_cast<const uint64_t*>(in + i * kF12Words));
   else f12_set_one(f);
   wave_product_store(lds, out);
@@ -92,63 +98,55 @@ __global__ void __launch_bounds__(kPairBlock) k_f12_product(const uint32_t* __re
 constexpr size_t kSlotWords = (size_t)kF12Limbs * kPairBlock;
 constexpr size_t kWorkspaceWords = kFeSlots * kSlotWords;             // per workgroup
 
-struct GlbF12 {
-  uint32_t* __restrict__ base;
-  __device__ __forceinline__ Fq2e<2> get(int i) const {
-    Fq2e<2> r;
-#pragma unroll
-    for (int k = 0; k < NL; ++k) { r.c0.l[k] = base[(2 * NL * i + k) * kPairBlock]; r.c1.l[k] = base[(2 * NL * i + NL + k) * kPairBlock]; }
-    return r;
-  }
-  __device__ __forceinline__ void set(int i, const Fq2e<2>& v) {
-#pragma unroll
-    for (int k = 0; k < NL; ++k) { base[(2 * NL * i + k) * kPairBlock] = v.c0.l[k]; base[(2 * NL * i + NL + k) * kPairBlock] = v.c1.l[k]; }
-  }
-};
 struct GlbBank {
   uint32_t* base;                                                      // the workgroup's workspace + lane
-  __device__ __forceinline__ GlbF12 slot(int i) const { return GlbF12{base + (size_t)i * kSlotWords}; }
+  __device__ __forceinline__ LaneF12 slot(int i) const { return LaneF12{base + (size_t)i * kSlotWords}; }
 };
 
 // lane i's Miller value, kept: written to slot 0 of the workgroup's workspace (lanes past the end write one)
 __global__ void __launch_bounds__(kPairBlock) k_miller_each(const uint32_t* __restrict__ g1, const uint32_t* __restrict__ g2, uint32_t n,
                                                             uint32_t* __restrict__ workspace) {
   __shared__ uint32_t lds[kF12Limbs][kPairBlock];
-  const size_t i = (size_t)blockIdx.x * kPairBlock + threadIdx.x;
-  const size_t at = i < n ? i : 0;
-  Affine<FqTag> p = PointIO<FqTag>::load_affine(g1 + at * PointIO<FqTag>::kAffineWords);
-  const Affine<Fq2Tag> q = PointIO<Fq2Tag>::load_affine(g2 + at * PointIO<Fq2Tag>::kAffineWords);
-  if (i >= n) { p.x = fe_zero<ModQ, 1>(); p.y = fe_zero<ModQ, 1>(); }
-  LdsF12 f{&lds[0][threadIdx.x]};
-  miller_loop(f, p, q);
-  GlbF12 out{workspace + (size_t)blockIdx.x * kWorkspaceWords + threadIdx.x};
+  const PairPQ pq = load_pair_or_one(g1, g2, (size_t)blockIdx.x * kPairBlock + threadIdx.x, n);
+  LaneF12 f{&lds[0][threadIdx.x]};
+  miller_loop(f, pq.p, pq.q);
+  LaneF12 out{workspace + (size_t)blockIdx.x * kWorkspaceWords + threadIdx.x};
   f12_copy(out, f);
 }
 
-// slot 0 of every lane -> its final exponentiation, in the standard encoding, and whether it is one
+// slot 0 of every lane -> its final exponentiation: whether it is one and, unless out_std is null, the value in the standard encoding
 __global__ void __launch_bounds__(kPairBlock) k_final_exp(uint32_t* __restrict__ workspace, uint32_t n, uint32_t* __restrict__ out_std,
                                                           uint32_t* __restrict__ is_one) {
   __shared__ uint32_t lds[kF12Limbs][kPairBlock];
   const size_t i = (size_t)blockIdx.x * kPairBlock + threadIdx.x;
-  LdsF12 w{&lds[0][threadIdx.x]};
+  LaneF12 w{&lds[0][threadIdx.x]};
   GlbBank bank{workspace + (size_t)blockIdx.x * kWorkspaceWords + threadIdx.x};
   f12_copy(w, bank.slot(0));
   final_exponentiation(w, bank);
   if (i < n) {
-    f12_to_std(w, reinterpret_cast<uint64_t*>(out_std + i * kF12Words));
+    if (out_std) f12_to_std(w, reinterpret_cast<uint64_t*>(out_std + i * kF12Words));
     is_one[i] = f12_is_one(w) ? 1u : 0u;
   }
 }
 
-int pairing_each_impl(Ctx& c, const char* fn, gs_handle h1, size_t poff, gs_handle h2, size_t qoff, size_t n, uint64_t* out_fq12, int* is_one) {
+// the window (offset, n) of two resident arrays that gs_pairing_product and gs_pairing_each work on
+struct PairWindow { const uint32_t *g1, *g2; };
+int pair_window(Ctx& c, const char* fn, gs_handle h1, size_t poff, gs_handle h2, size_t qoff, size_t n, PairWindow& w) {
   Bases* ps = c.get<Bases>(h1, Kind::G1Bases);
   Bases* qs = c.get<Bases>(h2, Kind::G2Bases);
   if (!ps) return fail(GS_ERR_ARG, "%s: bad G1 base-array handle", fn);
   if (!qs) return fail(GS_ERR_ARG, "%s: bad G2 base-array handle", fn);
-  if (!out_fq12 && !is_one) return fail(GS_ERR_ARG, "%s: both out-pointers are null", fn);
   if (poff > ps->n || ps->n - poff < n) return fail(GS_ERR_SHAPE, "%s: the G1 array has %zu points, %zu were asked for from index %zu", fn, ps->n, n, poff);
   if (qoff > qs->n || qs->n - qoff < n) return fail(GS_ERR_SHAPE, "%s: the G2 array has %zu points, %zu were asked for from index %zu", fn, qs->n, n, qoff);
   if (n >= 0xffffffffull) return fail(GS_ERR_SHAPE, "%s: %zu pairs, indices are 32 bits", fn, n);
+  w = PairWindow{ps->buf.as<uint32_t>() + poff * PointIO<FqTag>::kAffineWords, qs->buf.as<uint32_t>() + qoff * PointIO<Fq2Tag>::kAffineWords};
+  return GS_OK;
+}
+
+int pairing_each_impl(Ctx& c, const char* fn, gs_handle h1, size_t poff, gs_handle h2, size_t qoff, size_t n, uint64_t* out_fq12, int* is_one) {
+  if (!out_fq12 && !is_one) return fail(GS_ERR_ARG, "%s: both out-pointers are null", fn);
+  PairWindow w;
+  if (const int rc = pair_window(c, fn, h1, poff, h2, qoff, n, w)) return rc;
   c.drain();
   PhaseTimer t(c.stream);
   if (!n) {
@@ -158,16 +156,14 @@ int pairing_each_impl(Ctx& c, const char* fn, gs_handle h1, size_t poff, gs_hand
     return GS_OK;
   }
   const size_t count = (n + kPairBlock - 1) / kPairBlock;
-  DevBuf ws(count * kWorkspaceWords * 4), vals(n * kF12Words * 4), flags(n * 4);
+  DevBuf ws(count * kWorkspaceWords * 4), vals(out_fq12 ? n * kF12Words * 4 : 0), flags(n * 4);
   PhaseTimer tm(c.stream);
-  hipLaunchKernelGGL(k_miller_each, dim3((unsigned)count), dim3(kPairBlock), 0, c.stream,
-                     ps->buf.as<uint32_t>() + poff * PointIO<FqTag>::kAffineWords, qs->buf.as<uint32_t>() + qoff * PointIO<Fq2Tag>::kAffineWords,
-                     (uint32_t)n, ws.as<uint32_t>());
+  hipLaunchKernelGGL(k_miller_each, dim3((unsigned)count), dim3(kPairBlock), 0, c.stream, w.g1, w.g2, (uint32_t)n, ws.as<uint32_t>());
   GS_HIP(hipGetLastError());
   tm.stop();
   PhaseTimer tf(c.stream);
-  hipLaunchKernelGGL(k_final_exp, dim3((unsigned)count), dim3(kPairBlock), 0, c.stream, ws.as<uint32_t>(), (uint32_t)n, vals.as<uint32_t>(),
-                     flags.as<uint32_t>());
+  hipLaunchKernelGGL(k_final_exp, dim3((unsigned)count), dim3(kPairBlock), 0, c.stream, ws.as<uint32_t>(), (uint32_t)n,
+                     out_fq12 ? vals.as<uint32_t>() : nullptr, flags.as<uint32_t>());
   GS_HIP(hipGetLastError());
   tf.stop();
   t.stop();
@@ -183,8 +179,9 @@ int pairing_each_impl(Ctx& c, const char* fn, gs_handle h1, size_t poff, gs_hand
   return GS_OK;
 }
 
-// ---- a verdict per Groth16 proof: gs_groth16_verify_each (verify.hip) ----------------------------------------------------------
+// ---- the verify chain: what gs_groth16_verify_each, gs_groth16_verify_each_keys and gs_pinocchio_verify_each run ------------------
 constexpr int kLineWords = 4 * NL;                                     // lambda.c0, lambda.c1, c.c0, c.c1 as limbs
+constexpr size_t kListLimbBytes = (size_t)kPreparedSteps * kLineWords * 4;   // one prepared list as limbs
 
 // prepared lines arrive in standard form (pairing.h, prepare_g2_lines): one thread per field element makes limbs of them, once
 __global__ void k_std_to_limbs(const uint32_t* __restrict__ in, uint32_t nfe, uint32_t* __restrict__ out) {
@@ -196,6 +193,15 @@ __global__ void k_std_to_limbs(const uint32_t* __restrict__ in, uint32_t nfe, ui
   const Fe<ModQ, 1> v = canon(to_mont(unpack32<ModQ>(w)));
 #pragma unroll
   for (int k = 0; k < NL; ++k) out[(size_t)i * NL + k] = v.l[k];
+}
+
+// nlists prepared lists in standard form on the host -> limbs at `out`, through `staging` (nlists * kLineStd * 8 bytes); the host
+// words and the staging buffer are read by the stream: both live until it has run
+void lists_to_limbs(Ctx& c, const uint64_t* std_lists, int nlists, const DevBuf& staging, uint32_t* out) {
+  GS_HIP(hipMemcpyAsync(staging.p, std_lists, nlists * kLineStd * 8, hipMemcpyHostToDevice, c.stream));
+  const uint32_t nfe = (uint32_t)nlists * kPreparedSteps * 4;
+  hipLaunchKernelGGL(k_std_to_limbs, dim3((nfe + 63) / 64), dim3(64), 0, c.stream, staging.as<uint32_t>(), nfe, out);
+  GS_HIP(hipGetLastError());
 }
 
 struct PreparedLines {                                                 // the same words for every lane: a broadcast load
@@ -210,18 +216,6 @@ struct PreparedLines {                                                 // the sa
   __device__ __forceinline__ Fq2e<2> c(int k) const { return pair_at(base + (size_t)k * kLineWords + 2 * NL); }
 };
 
-// vkx_i = IC_0 + sum_j pub_ij IC_{j+1}, one lane per proof (miller.h, groth16_vkx)
-__global__ void __launch_bounds__(kPairBlock) k_groth16_vkx(const uint32_t* __restrict__ ic, const uint32_t* __restrict__ pub, uint32_t npublic,
-                                                            uint32_t n, uint32_t* __restrict__ out) {
-  constexpr int kAw = PointIO<FqTag>::kAffineWords;
-  const size_t i = (size_t)blockIdx.x * kPairBlock + threadIdx.x;
-  if (i >= n) return;
-  const uint32_t* mine = pub + i * npublic * 8;
-  const auto point = [&](int j) { return PointIO<FqTag>::load_affine(ic + (size_t)j * kAw); };
-  const auto bit = [&](int j, int b) { return ((mine[(size_t)j * 8 + (b >> 5)] >> (b & 31)) & 1u) != 0; };
-  PointIO<FqTag>::store_affine(out + i * kAw, groth16_vkx(point, bit, (int)npublic));
-}
-
 // flags[i] = is point i in G2?  (g2_subgroup.h; gs_g2_subgroup_check's kernel reports a count and the first index only)
 __global__ void __launch_bounds__(kPairBlock) k_g2_member_flags(const uint32_t* __restrict__ in, uint32_t n, uint32_t* __restrict__ flags) {
   const size_t i = (size_t)blockIdx.x * kPairBlock + threadIdx.x;
@@ -229,106 +223,63 @@ __global__ void __launch_bounds__(kPairBlock) k_g2_member_flags(const uint32_t* 
   flags[i] = g2_in_subgroup(PointIO<Fq2Tag>::load_affine(in + i * PointIO<Fq2Tag>::kAffineWords)) ? 1u : 0u;
 }
 
-// lane i: the Miller value of e(-A_i, B_i) e(vkx_i, gamma) e(C_i, delta) in ONE accumulator, times the key's e(alpha, beta) Miller
-// value (ab, standard encoding), into slot 0 of the workgroup's workspace for k_final_exp
-__global__ void __launch_bounds__(kPairBlock) k_miller_groth16(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b, const uint32_t* __restrict__ c,
-                                                               const uint32_t* __restrict__ vkx, uint32_t n, const uint32_t* __restrict__ lines,
-                                                               uint32_t skip_gamma, uint32_t skip_delta, const uint64_t* __restrict__ ab,
-                                                               uint32_t* __restrict__ workspace) {
-  __shared__ uint32_t lds[kF12Limbs][kPairBlock];
-  constexpr int kA1 = PointIO<FqTag>::kAffineWords, kA2 = PointIO<Fq2Tag>::kAffineWords;
-  const size_t i = (size_t)blockIdx.x * kPairBlock + threadIdx.x;
-  const size_t at = i < n ? i : 0;                                     // lanes past the end read proof 0 and are not read back
-  Affine<FqTag> p1 = PointIO<FqTag>::load_affine(a + at * kA1);
-  const Affine<Fq2Tag> q1 = PointIO<Fq2Tag>::load_affine(b + at * kA2);
-  const Affine<FqTag> p2 = PointIO<FqTag>::load_affine(vkx + at * kA1);
-  const Affine<FqTag> p3 = PointIO<FqTag>::load_affine(c + at * kA1);
-  p1.y = canon(neg(p1.y));                                             // -A; infinity (0, 0) stays infinity
-  LdsF12 f{&lds[0][threadIdx.x]};
-  miller_loop_groth16(f, p1, q1, p2, skip_gamma != 0, PreparedLines{lines}, p3, skip_delta != 0,
-                      PreparedLines{lines + (size_t)kPreparedSteps * kLineWords});
-  GlbBank bank{workspace + (size_t)blockIdx.x * kWorkspaceWords + threadIdx.x};
-  GlbF12 key = bank.slot(1);
-  f12_from_std(key, ab);
-  f12_mul(f, key);
-  GlbF12 out = bank.slot(0);
-  f12_copy(out, f);
-}
-
-int verify_each_impl(Ctx& c, const char* fn, gs_handle ha, gs_handle hb, gs_handle hc, gs_handle hic, const uint64_t* pub, size_t npublic, size_t n,
-                     const uint64_t* gamma_lines, const uint64_t* delta_lines, const uint64_t* ab, int* member, int* is_one) {
-  Bases* as = c.get<Bases>(ha, Kind::G1Bases);
-  Bases* bs = c.get<Bases>(hb, Kind::G2Bases);
-  Bases* cs = c.get<Bases>(hc, Kind::G1Bases);
-  Bases* ics = c.get<Bases>(hic, Kind::G1Bases);
-  if (!as || !bs || !cs || !ics) return fail(GS_ERR_ARG, "%s: bad base-array handle", fn);
-  if (as->n != n || bs->n != n || cs->n != n || ics->n < npublic + 1) return fail(GS_ERR_SHAPE, "%s: the arrays do not hold %zu proofs", fn, n);
-  if (!n || n >= 0xffffffffull || npublic >= 0xffffffffull) return fail(GS_ERR_SHAPE, "%s: %zu proofs, indices are 32 bits", fn, n);
-  c.drain();
-  constexpr size_t kLineStd = (size_t)kPreparedSteps * 16;              // u64 words of one prepared list
-  const size_t count = (n + kPairBlock - 1) / kPairBlock;
-  const size_t pub_bytes = n * npublic * 32;
-  DevBuf ws(count * kWorkspaceWords * 4), vals(n * kF12Words * 4), flags(n * 4), members(n * 4), vkx(n * PointIO<FqTag>::kAffineWords * 4);
-  DevBuf dpub(pub_bytes ? pub_bytes : 32), lines_std(2 * kLineStd * 8), lines(2 * (size_t)kPreparedSteps * kLineWords * 4), dab(48 * 8);
+// member[i] = is point i of bs in G2, one[l] = is the exponentiated Miller value of lane l one, for the 64 * groups lanes of the
+// caller's Miller kernel.  upload() enqueues the caller's copies, points() its per-proof G1 sums and miller(workspace) its Miller
+// kernel, which leaves lane l's value in slot 0 of its workgroup's workspace; the caller's buffers are allocated before the call.
+template <class Upload, class Points, class Miller>
+void run_verify_chain(Ctx& c, const Bases& bs, size_t groups, Upload&& upload, Points&& points, Miller&& miller, int* member, int* one) {
+  const size_t nb = bs.n, lanes = groups * kPairBlock;
+  DevBuf ws(groups * kWorkspaceWords * 4), flags(lanes * 4), members(nb * 4);
   PhaseTimer t(c.stream), tu(c.stream);
-  std::vector<uint64_t> host_lines(2 * kLineStd, 0);
-  if (gamma_lines) memcpy(host_lines.data(), gamma_lines, kLineStd * 8);
-  if (delta_lines) memcpy(host_lines.data() + kLineStd, delta_lines, kLineStd * 8);
-  if (pub_bytes) GS_HIP(hipMemcpyAsync(dpub.p, pub, pub_bytes, hipMemcpyHostToDevice, c.stream));
-  GS_HIP(hipMemcpyAsync(lines_std.p, host_lines.data(), 2 * kLineStd * 8, hipMemcpyHostToDevice, c.stream));
-  GS_HIP(hipMemcpyAsync(dab.p, ab, 48 * 8, hipMemcpyHostToDevice, c.stream));
-  const uint32_t nfe = 2 * kPreparedSteps * 4;
-  hipLaunchKernelGGL(k_std_to_limbs, dim3((nfe + 63) / 64), dim3(64), 0, c.stream, lines_std.as<uint32_t>(), nfe, lines.as<uint32_t>());
-  GS_HIP(hipGetLastError());
+  upload();
   tu.stop();
   PhaseTimer tmem(c.stream);
-  hipLaunchKernelGGL(k_g2_member_flags, dim3((unsigned)count), dim3(kPairBlock), 0, c.stream, bs->buf.as<uint32_t>(), (uint32_t)n, members.as<uint32_t>());
+  hipLaunchKernelGGL(k_g2_member_flags, dim3((unsigned)((nb + kPairBlock - 1) / kPairBlock)), dim3(kPairBlock), 0, c.stream, bs.buf.as<uint32_t>(),
+                     (uint32_t)nb, members.as<uint32_t>());
   GS_HIP(hipGetLastError());
   tmem.stop();
   PhaseTimer tv(c.stream);
-  hipLaunchKernelGGL(k_groth16_vkx, dim3((unsigned)count), dim3(kPairBlock), 0, c.stream, ics->buf.as<uint32_t>(), dpub.as<uint32_t>(), (uint32_t)npublic,
-                     (uint32_t)n, vkx.as<uint32_t>());
+  points();
   GS_HIP(hipGetLastError());
   tv.stop();
   PhaseTimer tm(c.stream);
-  hipLaunchKernelGGL(k_miller_groth16, dim3((unsigned)count), dim3(kPairBlock), 0, c.stream, as->buf.as<uint32_t>(), bs->buf.as<uint32_t>(),
-                     cs->buf.as<uint32_t>(), vkx.as<uint32_t>(), (uint32_t)n, lines.as<uint32_t>(), gamma_lines ? 0u : 1u, delta_lines ? 0u : 1u,
-                     dab.as<uint64_t>(), ws.as<uint32_t>());
+  miller(ws.as<uint32_t>());
   GS_HIP(hipGetLastError());
   tm.stop();
   PhaseTimer tf(c.stream);
-  hipLaunchKernelGGL(k_final_exp, dim3((unsigned)count), dim3(kPairBlock), 0, c.stream, ws.as<uint32_t>(), (uint32_t)n, vals.as<uint32_t>(),
+  hipLaunchKernelGGL(k_final_exp, dim3((unsigned)groups), dim3(kPairBlock), 0, c.stream, ws.as<uint32_t>(), (uint32_t)lanes, (uint32_t*)nullptr,
                      flags.as<uint32_t>());
   GS_HIP(hipGetLastError());
   tf.stop();
   t.stop();
-  std::vector<uint32_t> hf(n), hm(n);
-  GS_HIP(hipMemcpyAsync(hf.data(), flags.p, n * 4, hipMemcpyDeviceToHost, c.stream));
-  GS_HIP(hipMemcpyAsync(hm.data(), members.p, n * 4, hipMemcpyDeviceToHost, c.stream));
-  GS_HIP(hipStreamSynchronize(c.stream));
-  for (size_t i = 0; i < n; ++i) { is_one[i] = (int)hf[i]; member[i] = (int)hm[i]; }
+  std::vector<uint32_t> hf(lanes), hm(nb);
+  GS_HIP(hipMemcpyAsync(hf.data(), flags.p, lanes * 4, hipMemcpyDeviceToHost, c.stream));
+  GS_HIP(hipMemcpyAsync(hm.data(), members.p, nb * 4, hipMemcpyDeviceToHost, c.stream));
+  GS_HIP(hipStreamSynchronize(c.stream));                               // the caller's pageable host tables are read by now
+  for (size_t l = 0; l < lanes; ++l) one[l] = (int)hf[l];
+  for (size_t i = 0; i < nb; ++i) member[i] = (int)hm[i];
   reset_timing(c);
   c.timing.total_ms = t.ms();
-  c.timing.h2d_ms = tu.ms();                                           // signals, lines, the key's Miller value
-  c.timing.poly_ms = tmem.ms();                                        // membership of the B_i
-  c.timing.plan_ms = tv.ms();                                          // vkx
+  c.timing.h2d_ms = tu.ms();                                           // signals, tables, prepared lists
+  c.timing.poly_ms = tmem.ms();                                        // membership of the prover's G2 points
+  c.timing.plan_ms = tv.ms();                                          // vkx (and Pinocchio's two sums)
   c.timing.accumulate_ms = tm.ms();                                    // the Miller loops
   c.timing.reduce_ms = tf.ms();                                        // the final exponentiations
-  return GS_OK;
 }
 
-// ---- proofs of many keys: gs_groth16_vk_create, gs_groth16_verify_each_keys (verify.hip) ------------------------------------------
+// ---- a verdict per Groth16 proof: gs_groth16_verify_each, gs_groth16_vk_create, gs_groth16_verify_each_keys (verify.hip) -------------
 // One key per one-wave workgroup (verify_plan.h): workgroup g reads its group record and through it its key record, both at addresses
 // that depend on blockIdx.x alone, so the key's words -- the pointers here, and the lines, the IC points and the e(alpha, beta) value
-// behind them -- stay what they are in the single-key kernels: the same for every lane of the wave.  Every slot exists (the groups are
-// whole), padded slots hold the point at infinity and are not read back.  The bodies are those of k_groth16_vkx and k_miller_groth16.
-struct VkRecord {                                                      // the per-call key table, one per entry of `keys`
+// behind them -- are the same for every lane of the wave: broadcast loads.  Every slot exists (the groups are whole), padded slots hold
+// the point at infinity and are not read back.
+struct VkRecord {                                                      // the per-call key table, one per key of the call
   const uint32_t* lines;                                               // gamma's list, then delta's, as limbs
   const uint32_t* ic;
   const uint64_t* ab;
   uint32_t npublic, skip_gamma, skip_delta, reserved;
 };
 
+// vkx_i = IC_0 + sum_j pub_ij IC_{j+1}, one lane per proof (miller.h, groth16_vkx)
 __global__ void __launch_bounds__(kPairBlock) k_groth16_vkx_keys(const VkRecord* __restrict__ keys, const VerifyGroup* __restrict__ groups,
                                                                  const uint32_t* __restrict__ pub, uint32_t* __restrict__ out) {
   constexpr int kAw = PointIO<FqTag>::kAffineWords;
@@ -342,6 +293,8 @@ __global__ void __launch_bounds__(kPairBlock) k_groth16_vkx_keys(const VkRecord*
   PointIO<FqTag>::store_affine(out + i * kAw, groth16_vkx(point, bit, (int)key.npublic));
 }
 
+// lane i: the Miller value of e(-A_i, B_i) e(vkx_i, gamma) e(C_i, delta) in ONE accumulator, times the key's e(alpha, beta) Miller
+// value (ab, standard encoding), into slot 0 of the workgroup's workspace for k_final_exp
 __global__ void __launch_bounds__(kPairBlock) k_miller_groth16_keys(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b,
                                                                     const uint32_t* __restrict__ c, const uint32_t* __restrict__ vkx,
                                                                     const VkRecord* __restrict__ keys, const VerifyGroup* __restrict__ groups,
@@ -355,41 +308,33 @@ __global__ void __launch_bounds__(kPairBlock) k_miller_groth16_keys(const uint32
   const Affine<FqTag> p2 = PointIO<FqTag>::load_affine(vkx + at * kA1);
   const Affine<FqTag> p3 = PointIO<FqTag>::load_affine(c + at * kA1);
   p1.y = canon(neg(p1.y));                                             // -A; infinity (0, 0) stays infinity
-  LdsF12 f{&lds[0][threadIdx.x]};
+  LaneF12 f{&lds[0][threadIdx.x]};
   miller_loop_groth16(f, p1, q1, p2, key.skip_gamma != 0, PreparedLines{key.lines}, p3, key.skip_delta != 0,
                       PreparedLines{key.lines + (size_t)kPreparedSteps * kLineWords});
   GlbBank bank{workspace + (size_t)blockIdx.x * kWorkspaceWords + threadIdx.x};
-  GlbF12 keyval = bank.slot(1);
+  LaneF12 keyval = bank.slot(1);
   f12_from_std(keyval, key.ab);
   f12_mul(f, keyval);
-  GlbF12 out = bank.slot(0);
+  LaneF12 out = bank.slot(0);
   f12_copy(out, f);
 }
 
 // the resident part of a key: the IC array (already uploaded, shared with its handle), the two lists as limbs, the key's Miller value
-int vk_install_impl(Ctx& c, const char* fn, gs_handle hic, size_t nic, const uint64_t* gamma_lines, const uint64_t* delta_lines, const uint64_t* ab,
-                    gs_handle* out) {
+int vk_install_impl(Ctx& c, const char* fn, gs_handle hic, size_t nic, const Groth16KeyWords& words, gs_handle* out) {
   std::shared_ptr<Bases> ics = c.share<Bases>(hic, Kind::G1Bases);
   if (!ics || ics->n != nic || !nic) return fail(GS_ERR_ARG, "%s: bad IC array", fn);
   if (nic - 1 >= 0xffffffffull) return fail(GS_ERR_SHAPE, "%s: %zu IC points, indices are 32 bits", fn, nic);
-  constexpr size_t kLineStd = (size_t)kPreparedSteps * 16;              // u64 words of one prepared list
   auto vk = std::make_shared<GrothVk>();
   vk->ic = ics;
   vk->npublic = nic - 1;
-  vk->skip_gamma = !gamma_lines;
-  vk->skip_delta = !delta_lines;
-  vk->lines.alloc(2 * (size_t)kPreparedSteps * kLineWords * 4);
+  vk->skip_gamma = words.skip_gamma;
+  vk->skip_delta = words.skip_delta;
+  vk->lines.alloc(2 * kListLimbBytes);
   vk->ab.alloc(48 * 8);
-  DevBuf lines_std(2 * kLineStd * 8);
-  std::vector<uint64_t> host_lines(2 * kLineStd, 0);
-  if (gamma_lines) memcpy(host_lines.data(), gamma_lines, kLineStd * 8);
-  if (delta_lines) memcpy(host_lines.data() + kLineStd, delta_lines, kLineStd * 8);
-  GS_HIP(hipMemcpyAsync(lines_std.p, host_lines.data(), 2 * kLineStd * 8, hipMemcpyHostToDevice, c.stream));
-  GS_HIP(hipMemcpyAsync(vk->ab.p, ab, 48 * 8, hipMemcpyHostToDevice, c.stream));
-  const uint32_t nfe = 2 * kPreparedSteps * 4;
-  hipLaunchKernelGGL(k_std_to_limbs, dim3((nfe + 63) / 64), dim3(64), 0, c.stream, lines_std.as<uint32_t>(), nfe, vk->lines.as<uint32_t>());
-  GS_HIP(hipGetLastError());
-  GS_HIP(hipStreamSynchronize(c.stream));                               // the host buffers and lines_std end with this call
+  DevBuf staging(2 * kLineStd * 8);
+  GS_HIP(hipMemcpyAsync(vk->ab.p, words.ab, 48 * 8, hipMemcpyHostToDevice, c.stream));
+  lists_to_limbs(c, words.lines.data(), 2, staging, vk->lines.as<uint32_t>());
+  GS_HIP(hipStreamSynchronize(c.stream));                               // the host words and the staging buffer end with this call
   *out = c.put(std::move(vk));
   return GS_OK;
 }
@@ -404,8 +349,8 @@ int vk_info_impl(Ctx& c, const char* fn, const gs_handle* keys, size_t nkeys, ui
 }
 
 // member[s], is_one[s] for every SLOT s (64 per group); a, b, c hold the proofs' points in slot order, pub the signals in slot order
-int verify_each_keys_impl(Ctx& c, const char* fn, const gs_handle* keys, size_t nkeys, gs_handle ha, gs_handle hb, gs_handle hc, const VerifyGroup* groups,
-                          size_t ngroups, const uint64_t* pub, uint64_t nsignals, int* member, int* is_one) {
+int verify_slots_impl(Ctx& c, const char* fn, const Groth16CallKeys& k, gs_handle ha, gs_handle hb, gs_handle hc, const VerifyGroup* groups,
+                      size_t ngroups, const uint64_t* pub, uint64_t nsignals, int* member, int* is_one) {
   Bases* as = c.get<Bases>(ha, Kind::G1Bases);
   Bases* bs = c.get<Bases>(hb, Kind::G2Bases);
   Bases* cs = c.get<Bases>(hc, Kind::G1Bases);
@@ -413,12 +358,25 @@ int verify_each_keys_impl(Ctx& c, const char* fn, const gs_handle* keys, size_t 
   const size_t n = ngroups * kPairBlock;                                // slots
   if (!ngroups || n >= 0xffffffffull) return fail(GS_ERR_SHAPE, "%s: %zu slots, indices are 32 bits", fn, n);
   if (as->n != n || bs->n != n || cs->n != n) return fail(GS_ERR_SHAPE, "%s: the arrays do not hold %zu slots", fn, n);
+  // the call's key table: the prepared keys' words where they lie, or the one key of this call in buffers that end with it
+  const size_t nkeys = k.keys ? k.nkeys : 1;
   std::vector<VkRecord> table(nkeys);
-  for (size_t k = 0; k < nkeys; ++k) {
-    GrothVk* vk = c.get<GrothVk>(keys[k], Kind::GrothVk);
-    if (!vk) return fail(GS_ERR_ARG, "%s: keys[%zu] is not a prepared verification key on logical device %d", fn, k, c.logical);
-    table[k] = VkRecord{vk->lines.as<uint32_t>(), vk->ic->buf.as<uint32_t>(), vk->ab.as<uint64_t>(), (uint32_t)vk->npublic, vk->skip_gamma ? 1u : 0u,
+  DevBuf own_lines, own_ab, staging;
+  for (size_t i = 0; k.keys && i < nkeys; ++i) {
+    GrothVk* vk = c.get<GrothVk>(k.keys[i], Kind::GrothVk);
+    if (!vk) return fail(GS_ERR_ARG, "%s: keys[%zu] is not a prepared verification key on logical device %d", fn, i, c.logical);
+    table[i] = VkRecord{vk->lines.as<uint32_t>(), vk->ic->buf.as<uint32_t>(), vk->ab.as<uint64_t>(), (uint32_t)vk->npublic, vk->skip_gamma ? 1u : 0u,
                         vk->skip_delta ? 1u : 0u, 0u};
+  }
+  if (!k.keys) {
+    Bases* ics = c.get<Bases>(k.ic, Kind::G1Bases);
+    if (!ics) return fail(GS_ERR_ARG, "%s: bad base-array handle", fn);
+    if (k.npublic >= 0xffffffffull || ics->n < k.npublic + 1) return fail(GS_ERR_SHAPE, "%s: the IC array does not hold %zu points", fn, k.npublic + 1);
+    own_lines.alloc(2 * kListLimbBytes);
+    own_ab.alloc(48 * 8);
+    staging.alloc(2 * kLineStd * 8);
+    table[0] = VkRecord{own_lines.as<uint32_t>(), ics->buf.as<uint32_t>(), own_ab.as<uint64_t>(), (uint32_t)k.npublic, k.words->skip_gamma ? 1u : 0u,
+                        k.words->skip_delta ? 1u : 0u, 0u};
   }
   uint64_t expect = 0;                                                  // the plan against the keys as they are now, under the lock
   for (size_t g = 0; g < ngroups; ++g) {
@@ -430,46 +388,28 @@ int verify_each_keys_impl(Ctx& c, const char* fn, const gs_handle* keys, size_t 
   c.drain();
   constexpr int kAw = PointIO<FqTag>::kAffineWords;
   const size_t pub_bytes = (size_t)nsignals * 32;
-  DevBuf ws(ngroups * kWorkspaceWords * 4), vals(n * kF12Words * 4), flags(n * 4), members(n * 4), vkx(n * kAw * 4);
-  DevBuf dpub(pub_bytes ? pub_bytes : 32), dkeys(nkeys * sizeof(VkRecord)), dgroups(ngroups * sizeof(VerifyGroup));
-  PhaseTimer t(c.stream), tu(c.stream);
-  if (pub_bytes) GS_HIP(hipMemcpyAsync(dpub.p, pub, pub_bytes, hipMemcpyHostToDevice, c.stream));
-  GS_HIP(hipMemcpyAsync(dkeys.p, table.data(), nkeys * sizeof(VkRecord), hipMemcpyHostToDevice, c.stream));
-  GS_HIP(hipMemcpyAsync(dgroups.p, groups, ngroups * sizeof(VerifyGroup), hipMemcpyHostToDevice, c.stream));
-  GS_HIP(hipMemsetAsync(vkx.p, 0, n * kAw * 4, c.stream));              // infinity in the padded slots
-  tu.stop();
-  PhaseTimer tmem(c.stream);
-  hipLaunchKernelGGL(k_g2_member_flags, dim3((unsigned)ngroups), dim3(kPairBlock), 0, c.stream, bs->buf.as<uint32_t>(), (uint32_t)n, members.as<uint32_t>());
-  GS_HIP(hipGetLastError());
-  tmem.stop();
-  PhaseTimer tv(c.stream);
-  hipLaunchKernelGGL(k_groth16_vkx_keys, dim3((unsigned)ngroups), dim3(kPairBlock), 0, c.stream, dkeys.as<VkRecord>(), dgroups.as<VerifyGroup>(),
-                     dpub.as<uint32_t>(), vkx.as<uint32_t>());
-  GS_HIP(hipGetLastError());
-  tv.stop();
-  PhaseTimer tm(c.stream);
-  hipLaunchKernelGGL(k_miller_groth16_keys, dim3((unsigned)ngroups), dim3(kPairBlock), 0, c.stream, as->buf.as<uint32_t>(), bs->buf.as<uint32_t>(),
-                     cs->buf.as<uint32_t>(), vkx.as<uint32_t>(), dkeys.as<VkRecord>(), dgroups.as<VerifyGroup>(), ws.as<uint32_t>());
-  GS_HIP(hipGetLastError());
-  tm.stop();
-  PhaseTimer tf(c.stream);
-  hipLaunchKernelGGL(k_final_exp, dim3((unsigned)ngroups), dim3(kPairBlock), 0, c.stream, ws.as<uint32_t>(), (uint32_t)n, vals.as<uint32_t>(),
-                     flags.as<uint32_t>());
-  GS_HIP(hipGetLastError());
-  tf.stop();
-  t.stop();
-  std::vector<uint32_t> hf(n), hm(n);
-  GS_HIP(hipMemcpyAsync(hf.data(), flags.p, n * 4, hipMemcpyDeviceToHost, c.stream));
-  GS_HIP(hipMemcpyAsync(hm.data(), members.p, n * 4, hipMemcpyDeviceToHost, c.stream));
-  GS_HIP(hipStreamSynchronize(c.stream));                               // the pageable host tables above are read by now
-  for (size_t i = 0; i < n; ++i) { is_one[i] = (int)hf[i]; member[i] = (int)hm[i]; }
-  reset_timing(c);
-  c.timing.total_ms = t.ms();
-  c.timing.h2d_ms = tu.ms();                                           // signals, the key table, the group table
-  c.timing.poly_ms = tmem.ms();                                        // membership of the B_i
-  c.timing.plan_ms = tv.ms();                                          // vkx
-  c.timing.accumulate_ms = tm.ms();                                    // the Miller loops
-  c.timing.reduce_ms = tf.ms();                                        // the final exponentiations
+  DevBuf vkx(n * kAw * 4), dpub(pub_bytes ? pub_bytes : 32), dkeys(nkeys * sizeof(VkRecord)), dgroups(ngroups * sizeof(VerifyGroup));
+  run_verify_chain(
+      c, *bs, ngroups,
+      [&] {
+        if (pub_bytes) GS_HIP(hipMemcpyAsync(dpub.p, pub, pub_bytes, hipMemcpyHostToDevice, c.stream));
+        GS_HIP(hipMemcpyAsync(dkeys.p, table.data(), nkeys * sizeof(VkRecord), hipMemcpyHostToDevice, c.stream));
+        GS_HIP(hipMemcpyAsync(dgroups.p, groups, ngroups * sizeof(VerifyGroup), hipMemcpyHostToDevice, c.stream));
+        GS_HIP(hipMemsetAsync(vkx.p, 0, n * kAw * 4, c.stream));        // infinity in the padded slots
+        if (!k.keys) {
+          GS_HIP(hipMemcpyAsync(own_ab.p, k.words->ab, 48 * 8, hipMemcpyHostToDevice, c.stream));
+          lists_to_limbs(c, k.words->lines.data(), 2, staging, own_lines.as<uint32_t>());
+        }
+      },
+      [&] {
+        hipLaunchKernelGGL(k_groth16_vkx_keys, dim3((unsigned)ngroups), dim3(kPairBlock), 0, c.stream, dkeys.as<VkRecord>(), dgroups.as<VerifyGroup>(),
+                           dpub.as<uint32_t>(), vkx.as<uint32_t>());
+      },
+      [&](uint32_t* ws) {
+        hipLaunchKernelGGL(k_miller_groth16_keys, dim3((unsigned)ngroups), dim3(kPairBlock), 0, c.stream, as->buf.as<uint32_t>(), bs->buf.as<uint32_t>(),
+                           cs->buf.as<uint32_t>(), vkx.as<uint32_t>(), dkeys.as<VkRecord>(), dgroups.as<VerifyGroup>(), ws);
+      },
+      member, is_one);
   return GS_OK;
 }
 
@@ -534,14 +474,14 @@ __global__ void __launch_bounds__(kPairBlock) k_miller_pinocchio(const uint32_t*
   p3.y = canon(neg(p3.y));
   const auto list = [&](int l) { return PreparedLines{lines + (size_t)l * kPreparedSteps * kLineWords}; };
   const auto absent = [&](int l) { return ((skip_mask >> l) & 1u) != 0; };
-  LdsF12 f{&lds[0][threadIdx.x]};
+  LaneF12 f{&lds[0][threadIdx.x]};
   if (eq == 0 || eq == 2) {
     miller_loop_prepared(f, p1, absent(l1), list(l1), p2, absent(l2), list(l2), p3, true, list(l3));
   } else {
     const Affine<Fq2Tag> q1 = PointIO<Fq2Tag>::load_affine(b + at * kA2);
     miller_loop_groth16(f, p1, q1, p2, absent(l2), list(l2), p3, no3 || absent(l3), list(l3));
   }
-  GlbF12 out{workspace + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * kWorkspaceWords + threadIdx.x};
+  LaneF12 out{workspace + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * kWorkspaceWords + threadIdx.x};
   f12_copy(out, f);
 }
 
@@ -556,80 +496,36 @@ int pinocchio_each_impl(Ctx& c, const char* fn, gs_handle hg1, gs_handle hb, gs_
   if (!n || n >= 0xffffffffull / (kPinEquations * 2) || npublic >= 0xffffffffull) return fail(GS_ERR_SHAPE, "%s: %zu proofs, indices are 32 bits", fn, n);
   if (gs1->n != kPinG1 * n || bs->n != n || keys->n != 2 || ics->n < npublic + 1) return fail(GS_ERR_SHAPE, "%s: the arrays do not hold %zu proofs", fn, n);
   c.drain();
-  constexpr size_t kLineStd = (size_t)kPreparedSteps * 16;              // u64 words of one prepared list
   constexpr int kAw = PointIO<FqTag>::kAffineWords;
-  const size_t count = (n + kPairBlock - 1) / kPairBlock;
-  const size_t groups = kPinEquations * count, lanes = groups * kPairBlock;
+  const size_t count = (n + kPairBlock - 1) / kPairBlock;               // workgroups per equation: its lanes are padded to whole ones
   const size_t pub_bytes = n * npublic * 32;
-  DevBuf ws(groups * kWorkspaceWords * 4), vals(lanes * kF12Words * 4), flags(lanes * 4), members(n * 4), xa(n * kAw * 4), xac(n * kAw * 4);
-  DevBuf dpub(pub_bytes ? pub_bytes : 32), lines_std(kPinLists * kLineStd * 8), lines((size_t)kPinLists * kPreparedSteps * kLineWords * 4);
-  PhaseTimer t(c.stream), tu(c.stream);
-  if (pub_bytes) GS_HIP(hipMemcpyAsync(dpub.p, pub, pub_bytes, hipMemcpyHostToDevice, c.stream));
-  GS_HIP(hipMemcpyAsync(lines_std.p, lines_std_host, kPinLists * kLineStd * 8, hipMemcpyHostToDevice, c.stream));
-  const uint32_t nfe = kPinLists * kPreparedSteps * 4;
-  hipLaunchKernelGGL(k_std_to_limbs, dim3((nfe + 63) / 64), dim3(64), 0, c.stream, lines_std.as<uint32_t>(), nfe, lines.as<uint32_t>());
-  GS_HIP(hipGetLastError());
-  tu.stop();
-  PhaseTimer tmem(c.stream);
-  hipLaunchKernelGGL(k_g2_member_flags, dim3((unsigned)count), dim3(kPairBlock), 0, c.stream, bs->buf.as<uint32_t>(), (uint32_t)n, members.as<uint32_t>());
-  GS_HIP(hipGetLastError());
-  tmem.stop();
-  PhaseTimer tv(c.stream);
-  hipLaunchKernelGGL(k_pinocchio_points, dim3((unsigned)count), dim3(kPairBlock), 0, c.stream, ics->buf.as<uint32_t>(), dpub.as<uint32_t>(),
-                     (uint32_t)npublic, gs1->buf.as<uint32_t>(), (uint32_t)n, xa.as<uint32_t>(), xac.as<uint32_t>());
-  GS_HIP(hipGetLastError());
-  tv.stop();
-  PhaseTimer tm(c.stream);
-  hipLaunchKernelGGL(k_miller_pinocchio, dim3((unsigned)count, kPinEquations), dim3(kPairBlock), 0, c.stream, gs1->buf.as<uint32_t>(),
-                     bs->buf.as<uint32_t>(), xa.as<uint32_t>(), xac.as<uint32_t>(), keys->buf.as<uint32_t>(), (uint32_t)n, lines.as<uint32_t>(),
-                     (uint32_t)skip_mask, ws.as<uint32_t>());
-  GS_HIP(hipGetLastError());
-  tm.stop();
-  PhaseTimer tf(c.stream);
-  hipLaunchKernelGGL(k_final_exp, dim3((unsigned)groups), dim3(kPairBlock), 0, c.stream, ws.as<uint32_t>(), (uint32_t)lanes, vals.as<uint32_t>(),
-                     flags.as<uint32_t>());
-  GS_HIP(hipGetLastError());
-  tf.stop();
-  t.stop();
-  std::vector<uint32_t> hf(lanes), hm(n);
-  GS_HIP(hipMemcpyAsync(hf.data(), flags.p, lanes * 4, hipMemcpyDeviceToHost, c.stream));
-  GS_HIP(hipMemcpyAsync(hm.data(), members.p, n * 4, hipMemcpyDeviceToHost, c.stream));
-  GS_HIP(hipStreamSynchronize(c.stream));
-  for (size_t i = 0; i < n; ++i) member[i] = (int)hm[i];
-  for (size_t e = 0; e < (size_t)kPinEquations; ++e)                    // equation e's lanes are padded to whole workgroups
-    for (size_t i = 0; i < n; ++i) one[e * n + i] = (int)hf[e * count * kPairBlock + i];
-  reset_timing(c);
-  c.timing.total_ms = t.ms();
-  c.timing.h2d_ms = tu.ms();                                           // signals and the six prepared lists
-  c.timing.poly_ms = tmem.ms();                                        // membership of the PiB_i
-  c.timing.plan_ms = tv.ms();                                          // vkx and the two sums
-  c.timing.accumulate_ms = tm.ms();                                    // the Miller loops
-  c.timing.reduce_ms = tf.ms();                                        // the final exponentiations
+  DevBuf xa(n * kAw * 4), xac(n * kAw * 4), dpub(pub_bytes ? pub_bytes : 32), staging(kPinLists * kLineStd * 8), lines(kPinLists * kListLimbBytes);
+  std::vector<int> lane_one(kPinEquations * count * kPairBlock);
+  run_verify_chain(
+      c, *bs, kPinEquations * count,
+      [&] {
+        if (pub_bytes) GS_HIP(hipMemcpyAsync(dpub.p, pub, pub_bytes, hipMemcpyHostToDevice, c.stream));
+        lists_to_limbs(c, lines_std_host, kPinLists, staging, lines.as<uint32_t>());
+      },
+      [&] {
+        hipLaunchKernelGGL(k_pinocchio_points, dim3((unsigned)count), dim3(kPairBlock), 0, c.stream, ics->buf.as<uint32_t>(), dpub.as<uint32_t>(),
+                           (uint32_t)npublic, gs1->buf.as<uint32_t>(), (uint32_t)n, xa.as<uint32_t>(), xac.as<uint32_t>());
+      },
+      [&](uint32_t* ws) {
+        hipLaunchKernelGGL(k_miller_pinocchio, dim3((unsigned)count, kPinEquations), dim3(kPairBlock), 0, c.stream, gs1->buf.as<uint32_t>(),
+                           bs->buf.as<uint32_t>(), xa.as<uint32_t>(), xac.as<uint32_t>(), keys->buf.as<uint32_t>(), (uint32_t)n, lines.as<uint32_t>(),
+                           (uint32_t)skip_mask, ws);
+      },
+      member, lane_one.data());
+  for (size_t e = 0; e < (size_t)kPinEquations; ++e)
+    for (size_t i = 0; i < n; ++i) one[e * n + i] = lane_one[e * count * kPairBlock + i];
   return GS_OK;
-}
-
-pairing::Fp12 host_f12(const uint64_t* w) {
-  using namespace gs::pairing;
-  Fp12 f;
-  Fp2* c[6] = {&f.a0.c0, &f.a0.c1, &f.a0.c2, &f.a1.c0, &f.a1.c1, &f.a1.c2};
-  for (int i = 0; i < 6; ++i) *c[i] = Fp2{fp_from_std(w + 8 * i), fp_from_std(w + 8 * i + 4)};
-  return f;
-}
-void host_f12_to_std(const pairing::Fp12& f, uint64_t* out) {
-  using namespace gs::pairing;
-  const Fp2* c[6] = {&f.a0.c0, &f.a0.c1, &f.a0.c2, &f.a1.c0, &f.a1.c1, &f.a1.c2};
-  for (int i = 0; i < 6; ++i) { fp_to_std(c[i]->c0, out + 8 * i); fp_to_std(c[i]->c1, out + 8 * i + 4); }
 }
 
 // the product of the n Miller values, before the final exponentiation
 int miller_product_impl(Ctx& c, const char* fn, gs_handle h1, size_t poff, gs_handle h2, size_t qoff, size_t n, pairing::Fp12* out) {
-  Bases* ps = c.get<Bases>(h1, Kind::G1Bases);
-  Bases* qs = c.get<Bases>(h2, Kind::G2Bases);
-  if (!ps) return fail(GS_ERR_ARG, "%s: bad G1 base-array handle", fn);
-  if (!qs) return fail(GS_ERR_ARG, "%s: bad G2 base-array handle", fn);
-  if (poff > ps->n || ps->n - poff < n) return fail(GS_ERR_SHAPE, "%s: the G1 array has %zu points, %zu were asked for from index %zu", fn, ps->n, n, poff);
-  if (qoff > qs->n || qs->n - qoff < n) return fail(GS_ERR_SHAPE, "%s: the G2 array has %zu points, %zu were asked for from index %zu", fn, qs->n, n, qoff);
-  if (n >= 0xffffffffull) return fail(GS_ERR_SHAPE, "%s: %zu pairs, indices are 32 bits", fn, n);
+  PairWindow w;
+  if (const int rc = pair_window(c, fn, h1, poff, h2, qoff, n, w)) return rc;
   c.drain();
   *out = pairing::f12_one();
   PhaseTimer t(c.stream);
@@ -641,9 +537,7 @@ int miller_product_impl(Ctx& c, const char* fn, gs_handle h1, size_t poff, gs_ha
   }
   size_t count = (n + kPairBlock - 1) / kPairBlock;
   DevBuf a(count * kF12Words * 4), b(((count + kPairBlock - 1) / kPairBlock) * kF12Words * 4);
-  hipLaunchKernelGGL(k_miller_pairs, dim3((unsigned)count), dim3(kPairBlock), 0, c.stream,
-                     ps->buf.as<uint32_t>() + poff * PointIO<FqTag>::kAffineWords, qs->buf.as<uint32_t>() + qoff * PointIO<Fq2Tag>::kAffineWords,
-                     (uint32_t)n, a.as<uint32_t>());
+  hipLaunchKernelGGL(k_miller_pairs, dim3((unsigned)count), dim3(kPairBlock), 0, c.stream, w.g1, w.g2, (uint32_t)n, a.as<uint32_t>());
   GS_HIP(hipGetLastError());
   DevBuf* src = &a;
   DevBuf* dst = &b;
@@ -660,8 +554,8 @@ int miller_product_impl(Ctx& c, const char* fn, gs_handle h1, size_t poff, gs_ha
   GS_HIP(hipStreamSynchronize(c.stream));
   reset_timing(c);
   c.timing.total_ms = t.ms();
-  pairing::Fp12 f = host_f12(host.data());
-  for (size_t i = 1; i < count; ++i) f = pairing::f12_mul(f, host_f12(host.data() + i * (kF12Words / 2)));
+  pairing::Fp12 f = pairing::f12_from_std(host.data());
+  for (size_t i = 1; i < count; ++i) f = pairing::f12_mul(f, pairing::f12_from_std(host.data() + i * (kF12Words / 2)));
   *out = f;
   return GS_OK;
 }
@@ -670,44 +564,24 @@ int miller_product_impl(Ctx& c, const char* fn, gs_handle h1, size_t poff, gs_ha
 
 namespace gs {
 
-// for gs_groth16_verify_batch (verify.hip): the product of the Miller values, the caller multiplies its own pairs in
 int miller_product(const char* fn, gs_handle g1, size_t poff, gs_handle g2, size_t qoff, size_t n, pairing::Fp12* out) {
   return guarded([&](Ctx& ctx) -> int { return miller_product_impl(ctx, fn, g1, poff, g2, qoff, n, out); }, true, false, g1);
 }
-
-// for gs_groth16_verify_each (verify.hip): per proof, is B in G2 and is the exponentiated product of the four pairs one.  The four
-// arrays are resident; gamma_lines / delta_lines are prepared lists (pairing.h) or null for an infinite gamma / delta; ab is the
-// Miller value of e(alpha, beta) in the standard encoding.
-int groth16_verify_each_device(const char* fn, gs_handle ha, gs_handle hb, gs_handle hc, gs_handle hic, const uint64_t* pub, size_t npublic, size_t n,
-                               const uint64_t* gamma_lines, const uint64_t* delta_lines, const uint64_t* ab, int* member, int* is_one) {
-  return guarded([&](Ctx& ctx) -> int { return verify_each_impl(ctx, fn, ha, hb, hc, hic, pub, npublic, n, gamma_lines, delta_lines, ab, member, is_one); },
-                 true, false, ha);
+int groth16_vk_install(const char* fn, gs_handle hic, size_t nic, const Groth16KeyWords& words, gs_handle* out) {
+  return guarded([&](Ctx& ctx) -> int { return vk_install_impl(ctx, fn, hic, nic, words, out); }, true, true, hic);
 }
-// for gs_pinocchio_verify_each (verify.hip): per proof, is PiB in G2 (member[i]) and is the exponentiated product of equation e + 1 one
-// (one[e * n + i]).  g1 holds the proofs' seven G1 points as slabs of n (PiA, PiAp, PiBp, PiC, PiCp, PiH, PiKp), key = Vkb, G1Kbg;
-// lines = the six prepared lists (Vka, Vkc, Vkz, G2Kbg, G2Kg, the generator; pairing.h), zeros for a list whose bit in skip_mask is set.
+int groth16_vk_info(const char* fn, const gs_handle* keys, size_t nkeys, uint32_t* npublic) {
+  return guarded([&](Ctx& ctx) -> int { return vk_info_impl(ctx, fn, keys, nkeys, npublic); }, true, true, nkeys ? keys[0] : 0);
+}
+int groth16_verify_slots_device(const char* fn, const Groth16CallKeys& keys, gs_handle ha, gs_handle hb, gs_handle hc, const VerifyGroup* groups,
+                                size_t ngroups, const uint64_t* pub, uint64_t nsignals, int* member, int* is_one) {
+  return guarded([&](Ctx& ctx) -> int { return verify_slots_impl(ctx, fn, keys, ha, hb, hc, groups, ngroups, pub, nsignals, member, is_one); }, true,
+                 false, ha);
+}
 int pinocchio_verify_each_device(const char* fn, gs_handle g1, gs_handle hb, gs_handle hic, gs_handle key, const uint64_t* pub, size_t npublic, size_t n,
                                  const uint64_t* lines, unsigned skip_mask, int* member, int* one) {
   return guarded([&](Ctx& ctx) -> int { return pinocchio_each_impl(ctx, fn, g1, hb, hic, key, pub, npublic, n, lines, skip_mask, member, one); }, true,
                  false, g1);
-}
-void f12_words(const pairing::Fp12& f, uint64_t* out) { host_f12_to_std(f, out); }
-
-// for gs_groth16_vk_create (verify.hip): the key object over an uploaded IC array (the object keeps the array alive, the caller frees
-// its handle), the prepared lists (null for an infinite gamma / delta) and the Miller value of e(alpha, beta)
-int groth16_vk_install(const char* fn, gs_handle hic, size_t nic, const uint64_t* gamma_lines, const uint64_t* delta_lines, const uint64_t* ab,
-                       gs_handle* out) {
-  return guarded([&](Ctx& ctx) -> int { return vk_install_impl(ctx, fn, hic, nic, gamma_lines, delta_lines, ab, out); }, true, true, hic);
-}
-// for gs_groth16_verify_each_keys (verify.hip): npublic of every key; GS_ERR_ARG for a handle that is not a prepared key
-int groth16_vk_info(const char* fn, const gs_handle* keys, size_t nkeys, uint32_t* npublic) {
-  return guarded([&](Ctx& ctx) -> int { return vk_info_impl(ctx, fn, keys, nkeys, npublic); }, true, true, nkeys ? keys[0] : 0);
-}
-// per SLOT of the plan (verify_plan.h), is B in G2 and is the exponentiated product of the four pairs one
-int groth16_verify_each_keys_device(const char* fn, const gs_handle* keys, size_t nkeys, gs_handle ha, gs_handle hb, gs_handle hc,
-                                    const VerifyGroup* groups, size_t ngroups, const uint64_t* pub, uint64_t nsignals, int* member, int* is_one) {
-  return guarded([&](Ctx& ctx) -> int { return verify_each_keys_impl(ctx, fn, keys, nkeys, ha, hb, hc, groups, ngroups, pub, nsignals, member, is_one); },
-                 true, false, ha);
 }
 
 }  // namespace gs
@@ -722,7 +596,7 @@ int gs_pairing_product(gs_handle g1, size_t poff, gs_handle g2, size_t qoff, siz
   }, true, false, g1);
   if (rc != GS_OK) return rc;
   const pairing::Fp12 v = n ? pairing::final_exponentiation(f) : f;   // on the calling thread, outside the context's lock
-  if (out_fq12) host_f12_to_std(v, out_fq12);
+  if (out_fq12) pairing::f12_to_std(v, out_fq12);
   if (is_one) *is_one = pairing::f12_eq(v, pairing::f12_one()) ? 1 : 0;
   return GS_OK;
 }

@@ -1,10 +1,11 @@
 // Verifier entry points: groth16.VerifyProof (groth16/groth16.go:281-305), snark.VerifyProof
 // (snark.go:292-368) and the pairing seam under them (bn128/bn128.go:179-186), on the host.  They do not touch the
-// device context and do not take its lock: a verifier thread can run beside in-flight proofs.
+// device context and do not take its lock: a verifier thread can run beside in-flight proofs.  The batch and per-proof verifiers
+// below them do their per-key and per-proof host work here and run the rest on the device through verify_device.h.
 #include <atomic>
 
-#include "pairing.h"
 #include "runtime.h"
+#include "verify_device.h"
 #include "verify_plan.h"
 
 using namespace gs;
@@ -46,12 +47,15 @@ bool product_is_one(const std::vector<G1Aff>& ps, const std::vector<G2Aff>& qs, 
   return f12_eq(final_exponentiation(f), f12_one());
 }
 
-void f12_to_std(const Fp12& f, uint64_t* out) {     // the reference's [2][3][2]*big.Int order
-  const Fp2* c[6] = {&f.a0.c0, &f.a0.c1, &f.a0.c2, &f.a1.c0, &f.a1.c1, &f.a1.c2};
-  for (int i = 0; i < 6; ++i) {
-    fp_to_std(c[i]->c0, out + 8 * i);
-    fp_to_std(c[i]->c1, out + 8 * i + 4);
-  }
+// What every verifier tests of its counts before any work.  The reference indexes vk.IC[i+1] for every public signal and panics past
+// the end (groth16.go:285); strict mode wants exactly one signal per IC point (a short list would silently verify the statement "the
+// missing inputs are 0").  GS_OK: *strict is the mode of this call.
+int check_signal_count(const char* fn, size_t nic, size_t npublic, bool* strict) {
+  if (nic < npublic + 1) return fail(GS_ERR_SHAPE, "%s: %zu public signals need %zu IC points, vk has %zu", fn, npublic, npublic + 1, nic);
+  *strict = g_strict.load() != 0;
+  if (*strict && nic != npublic + 1)
+    return fail(GS_ERR_SHAPE, "%s (strict): vk has %zu IC points, so exactly %zu public signals are required (got %zu)", fn, nic, nic - 1, npublic);
+  return GS_OK;
 }
 
 // vk.IC[0] + sum_i publicSignals[i] * vk.IC[i+1]   (groth16.go:283-286, snark.go:330-333)
@@ -124,16 +128,12 @@ int gs_groth16_verify(const uint64_t vk_g1_alpha[12], const uint64_t vk_g2_beta[
   return host_guarded([&]() -> int {
     if (!vk_g1_alpha || !vk_g2_beta || !vk_g2_gamma || !vk_g2_delta || !vk_ic || !pi_a || !pi_b || !pi_c || !ok || (npublic && !public_signals))
       return fail(GS_ERR_ARG, "gs_groth16_verify: null argument");
-    // the reference indexes vk.IC[i+1] for every public signal and panics past the end (groth16.go:285)
-    if (nic < npublic + 1) return fail(GS_ERR_SHAPE, "gs_groth16_verify: %zu public signals need %zu IC points, vk has %zu", npublic, npublic + 1, nic);
-    if (g_strict.load()) {
-      // strict: exactly one signal per IC point (a short list would silently verify the statement "the missing inputs are 0"),
-      // and canonical encodings only (x and x + r, X and X + q name the same element: accepting both makes proofs malleable)
-      if (nic != npublic + 1) return fail(GS_ERR_SHAPE, "gs_groth16_verify (strict): vk has %zu IC points, so exactly %zu public signals are required (got %zu)", nic, nic - 1, npublic);
-      if (!scalars_canonical(public_signals, npublic) || !coords_canonical(pi_a, 3) || !coords_canonical(pi_b, 6) || !coords_canonical(pi_c, 3)) {
-        *ok = 0;
-        return GS_OK;
-      }
+    bool strict;
+    if (const int rc = check_signal_count("gs_groth16_verify", nic, npublic, &strict)) return rc;
+    // strict: canonical encodings only (x and x + r, X and X + q name the same element: accepting both makes proofs malleable)
+    if (strict && (!scalars_canonical(public_signals, npublic) || !coords_canonical(pi_a, 3) || !coords_canonical(pi_b, 6) || !coords_canonical(pi_c, 3))) {
+      *ok = 0;
+      return GS_OK;
     }
     G1Aff ic = g1j_affine(accumulate_ic(vk_ic, nic, public_signals, npublic));
     // e(A, B) == e(alpha, beta) e(IC, gamma) e(C, delta)   <=>   e(-A, B) e(alpha, beta) e(IC, gamma) e(C, delta) == 1
@@ -151,14 +151,12 @@ int gs_pinocchio_verify(const uint64_t vka[24], const uint64_t vkb[12], const ui
   return host_guarded([&]() -> int {
     if (!vka || !vkb || !vkc || !g1kbg || !g2kbg || !g2kg || !vkz || !vk_ic || !proof || !ok || (npublic && !public_signals))
       return fail(GS_ERR_ARG, "gs_pinocchio_verify: null argument");
-    if (nic < npublic + 1) return fail(GS_ERR_SHAPE, "gs_pinocchio_verify: %zu public signals need %zu IC points, vk has %zu", npublic, npublic + 1, nic);
-    if (g_strict.load()) {
-      if (nic != npublic + 1) return fail(GS_ERR_SHAPE, "gs_pinocchio_verify (strict): vk has %zu IC points, so exactly %zu public signals are required (got %zu)", nic, nic - 1, npublic);
-      if (!scalars_canonical(public_signals, npublic) || !coords_canonical(proof, 27)) {
-        *ok = 0;
-        if (failed_check) *failed_check = 0;
-        return GS_OK;
-      }
+    bool strict;
+    if (const int rc = check_signal_count("gs_pinocchio_verify", nic, npublic, &strict)) return rc;
+    if (strict && (!scalars_canonical(public_signals, npublic) || !coords_canonical(proof, 27))) {
+      *ok = 0;
+      if (failed_check) *failed_check = 0;
+      return GS_OK;
     }
     // proof layout: PiA, PiAp (G1) | PiB (G2) | PiBp, PiC, PiCp, PiH, PiKp (G1)  -- snark.go:59-69
     const G1Aff piA = g1_from_jacobian_std(proof), piAp = g1_from_jacobian_std(proof + 12);
@@ -198,20 +196,6 @@ int gs_pinocchio_verify(const uint64_t vka[24], const uint64_t vkb[12], const ui
 // scaling A by the weights, the weighted sum of the C, the subgroup test of the B and the n Miller loops with their product -- runs on
 // the device through the library's own entry points; the host forms the npublic + 1 scalars of the public-input sum, runs the three
 // key pairs through the multi-Miller loop above and finishes with ONE final exponentiation.
-
-namespace gs {
-int miller_product(const char* fn, gs_handle g1, size_t poff, gs_handle g2, size_t qoff, size_t n, pairing::Fp12* out);   // pairing_device.hip
-int groth16_verify_each_device(const char* fn, gs_handle ha, gs_handle hb, gs_handle hc, gs_handle hic, const uint64_t* pub, size_t npublic, size_t n,
-                               const uint64_t* gamma_lines, const uint64_t* delta_lines, const uint64_t* ab, int* member, int* is_one);
-void f12_words(const pairing::Fp12& f, uint64_t* out);
-int pinocchio_verify_each_device(const char* fn, gs_handle g1, gs_handle hb, gs_handle hic, gs_handle key, const uint64_t* pub, size_t npublic, size_t n,
-                                 const uint64_t* lines, unsigned skip_mask, int* member, int* one);
-int groth16_vk_install(const char* fn, gs_handle hic, size_t nic, const uint64_t* gamma_lines, const uint64_t* delta_lines, const uint64_t* ab,
-                       gs_handle* out);
-int groth16_vk_info(const char* fn, const gs_handle* keys, size_t nkeys, uint32_t* npublic);
-int groth16_verify_each_keys_device(const char* fn, const gs_handle* keys, size_t nkeys, gs_handle ha, gs_handle hb, gs_handle hc,
-                                    const VerifyGroup* groups, size_t ngroups, const uint64_t* pub, uint64_t nsignals, int* member, int* is_one);
-}
 
 namespace {
 
@@ -299,6 +283,85 @@ bool groth16_proof_passes_screen(bool strict, const uint64_t* pub, size_t npubli
   return g1_on_curve(g1_from_jacobian_std(a)) && g2_on_curve(g2_from_jacobian_std(b)) && g1_on_curve(g1_from_jacobian_std(c));
 }
 
+// The per-key host work of the per-proof Groth16 verifiers: the curve tests of the key, the Miller value of e(alpha, beta) and the
+// prepared lines of gamma and delta.  False for a key that cannot verify anything, with the point and what is wrong with it.
+struct KeyFault { const char *point, *why; };
+bool prepare_groth16_key(const uint64_t alpha_w[12], const uint64_t beta_w[24], const uint64_t gamma_w[24], const uint64_t delta_w[24],
+                         gs::Groth16KeyWords& out, KeyFault& fault) {
+  const auto refuse = [&](const char* point, const char* why) { fault = KeyFault{point, why}; return false; };
+  const G1Aff alpha = g1_from_jacobian_std(alpha_w);
+  const G2Aff beta = g2_from_jacobian_std(beta_w), gamma = g2_from_jacobian_std(gamma_w), delta = g2_from_jacobian_std(delta_w);
+  if (!g1_on_curve(alpha)) return refuse("alpha", "is not on the curve");
+  if (!g2_on_curve(beta)) return refuse("beta", "is not on the twist");
+  if (!g2_on_curve(gamma)) return refuse("gamma", "is not on the twist");
+  if (!g2_on_curve(delta)) return refuse("delta", "is not on the twist");
+  Fp12 fab;
+  if (!multi_miller_loop({alpha}, {beta}, fab)) return refuse("beta", "is not of order r (a degenerate step in its Miller loop)");
+  f12_to_std(fab, out.ab);
+  out.lines.assign(2 * gs::kLineStd, 0);
+  out.skip_gamma = gamma.inf;
+  out.skip_delta = delta.inf;
+  std::vector<uint64_t> list;
+  if (!gamma.inf) {
+    if (!prepare_g2_lines(gamma, list)) return refuse("gamma", "is not of order r (a degenerate step in its prepared lines)");
+    memcpy(out.lines.data(), list.data(), gs::kLineStd * 8);
+  }
+  if (!delta.inf) {
+    if (!prepare_g2_lines(delta, list)) return refuse("delta", "is not of order r (a degenerate step in its prepared lines)");
+    memcpy(out.lines.data() + gs::kLineStd, list.data(), gs::kLineStd * 8);
+  }
+  return true;
+}
+
+// What the two per-proof Groth16 calls share once their keys stand: per proof what the single verifier tests before its pairings, the
+// permutation into the slot order of verify_plan.h (one key per one-wave workgroup; infinity in bad and in padded slots, because the
+// uploads refuse a whole array for one point off its curve), the device run and the fold into ok_each / nbad.  npublic: per key.
+int groth16_verdicts(const char* fn, const gs::Groth16CallKeys& keys, const uint32_t* npublic, const uint32_t* key_of_proof, bool strict,
+                     const uint64_t* public_signals, const uint64_t* pi_a, const uint64_t* pi_b, const uint64_t* pi_c, size_t n, int* ok_each,
+                     uint64_t* nbad) {
+  VerifyPlan plan;
+  if (plan_verify_slots(key_of_proof, n, keys.keys ? keys.nkeys : 1, npublic, plan) != kVpOk)
+    return fail(GS_ERR_SHAPE, "%s: %zu proofs need more than 2^32 slots (64 per key and started group): pass them in windows", fn, n);
+  if (plan.nsignals && !public_signals) return fail(GS_ERR_ARG, "%s: null argument", fn);
+  const size_t slots = plan.proof_of_slot.size();
+  std::vector<uint64_t> a(12 * slots, 0), b(24 * slots, 0), c(12 * slots, 0), pub(plan.nsignals ? 4 * (size_t)plan.nsignals : 4, 0);
+  std::vector<const uint64_t*> pub_of(n);
+  {
+    const uint64_t* at = public_signals;
+    for (size_t i = 0; i < n; ++i) { pub_of[i] = at; at += 4 * (size_t)npublic[key_of_proof[i]]; }
+  }
+  std::vector<char> bad(n, 0);
+  for (size_t g = 0; g < plan.groups.size(); ++g) {
+    const size_t np = npublic[plan.groups[g].key];
+    for (uint32_t l = 0; l < plan.groups[g].valid; ++l) {
+      const size_t s = g * kVpLanes + l, i = plan.proof_of_slot[s];
+      if (np) memcpy(pub.data() + 4 * ((size_t)plan.groups[g].sig_off + l * np), pub_of[i], 32 * np);
+      if (!groth16_proof_passes_screen(strict, pub_of[i], np, pi_a + 12 * i, pi_b + 24 * i, pi_c + 12 * i)) { bad[i] = 1; continue; }
+      memcpy(a.data() + 12 * s, pi_a + 12 * i, 96);
+      memcpy(b.data() + 24 * s, pi_b + 24 * i, 192);
+      memcpy(c.data() + 12 * s, pi_c + 12 * i, 96);
+    }
+  }
+  HandleBag bag;
+  gs_handle *ha = &bag.hs[0], *hb = &bag.hs[1], *hc = &bag.hs[2];
+  int rc;
+  if ((rc = gs_g1_upload(a.data(), slots, ha)) != GS_OK) return rc;
+  if ((rc = gs_g2_upload(b.data(), slots, hb)) != GS_OK) return rc;
+  if ((rc = gs_g1_upload(c.data(), slots, hc)) != GS_OK) return rc;
+  std::vector<int> member(slots), one(slots);
+  rc = gs::groth16_verify_slots_device(fn, keys, *ha, *hb, *hc, plan.groups.data(), plan.groups.size(), pub.data(), plan.nsignals, member.data(),
+                                       one.data());
+  if (rc != GS_OK) return rc;
+  uint64_t count = 0;
+  for (size_t i = 0; i < n; ++i) {
+    const size_t s = plan.slot_of_proof[i];
+    ok_each[i] = (!bad[i] && member[s] && one[s]) ? 1 : 0;
+    count += ok_each[i] ? 0 : 1;
+  }
+  if (nbad) *nbad = count;
+  return GS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -312,9 +375,8 @@ int gs_groth16_verify_batch(const uint64_t vk_g1_alpha[12], const uint64_t vk_g2
     if (!vk_g1_alpha || !vk_g2_beta || !vk_g2_gamma || !vk_g2_delta || !vk_ic || !challenge || !ok || (n && (!pi_a || !pi_b || !pi_c)) ||
         (n && npublic && !public_signals))
       return fail(GS_ERR_ARG, "%s: null argument", fn);
-    if (nic < npublic + 1) return fail(GS_ERR_SHAPE, "%s: %zu public signals need %zu IC points, vk has %zu", fn, npublic, npublic + 1, nic);
-    if (g_strict.load() && nic != npublic + 1)
-      return fail(GS_ERR_SHAPE, "%s (strict): vk has %zu IC points, so exactly %zu public signals are required (got %zu)", fn, nic, nic - 1, npublic);
+    bool strict;
+    if (const int shape = check_signal_count(fn, nic, npublic, &strict)) return shape;
     const Fr s = fr_from_std(challenge);
     if (fr_eq(s, Fr{{0, 0, 0, 0}}) || fr_eq(s, frc().one))
       return fail(GS_ERR_ARG, "%s: the challenge is 0 or 1 mod r: every weight would be the same (draw it at random, after the proofs are fixed)", fn);
@@ -323,8 +385,8 @@ int gs_groth16_verify_batch(const uint64_t vk_g1_alpha[12], const uint64_t vk_g2
       return GS_OK;
     }
     const auto reject = [&]() -> int { *ok = 0; return GS_OK; };        // *ok is written by the paths that return GS_OK, and only then
-    if (g_strict.load() && (!scalars_canonical(public_signals, n * npublic) || !coords_canonical(pi_a, 3 * n) || !coords_canonical(pi_b, 6 * n) ||
-                            !coords_canonical(pi_c, 3 * n)))
+    if (strict && (!scalars_canonical(public_signals, n * npublic) || !coords_canonical(pi_a, 3 * n) || !coords_canonical(pi_b, 6 * n) ||
+                   !coords_canonical(pi_c, 3 * n)))
       return reject();
     // the weights z_i = s^i in standard form, their sum, and sum_i z_i pub_ij per public input
     std::vector<uint64_t> z(4 * n);
@@ -387,9 +449,8 @@ int gs_groth16_verify_batch(const uint64_t vk_g1_alpha[12], const uint64_t vk_g2
 }
 
 // gs_groth16_verify_each (include/gosnark_hip.h): the verdict of gs_groth16_verify for every proof of a batch, on the device.  The host
-// does what is O(1) per call or a few products per proof: the key (curve tests, the Miller value of e(alpha, beta), the prepared lines
-// of gamma and delta) and the screening of the 3n points, because the uploads refuse a whole array for one point off its curve: such a
-// proof gets 0 and the point at infinity travels in its place.
+// does what is O(1) per call or a few products per proof: the key (prepare_groth16_key; it lives for this call only) and the screening
+// of the 3n points (groth16_verdicts).
 int gs_groth16_verify_each(const uint64_t vk_g1_alpha[12], const uint64_t vk_g2_beta[24], const uint64_t vk_g2_gamma[24],
                            const uint64_t vk_g2_delta[24], const uint64_t* vk_ic, size_t nic, const uint64_t* public_signals, size_t npublic,
                            const uint64_t* pi_a, const uint64_t* pi_b, const uint64_t* pi_c, size_t nproofs, int* ok_each, uint64_t* nbad) {
@@ -399,68 +460,40 @@ int gs_groth16_verify_each(const uint64_t vk_g1_alpha[12], const uint64_t vk_g2_
     if (!vk_g1_alpha || !vk_g2_beta || !vk_g2_gamma || !vk_g2_delta || !vk_ic || (n && (!pi_a || !pi_b || !pi_c || !ok_each)) ||
         (n && npublic && !public_signals))
       return fail(GS_ERR_ARG, "%s: null argument", fn);
-    if (nic < npublic + 1) return fail(GS_ERR_SHAPE, "%s: %zu public signals need %zu IC points, vk has %zu", fn, npublic, npublic + 1, nic);
-    const bool strict = g_strict.load() != 0;
-    if (strict && nic != npublic + 1)
-      return fail(GS_ERR_SHAPE, "%s (strict): vk has %zu IC points, so exactly %zu public signals are required (got %zu)", fn, nic, nic - 1, npublic);
+    bool strict;
+    if (const int shape = check_signal_count(fn, nic, npublic, &strict)) return shape;
     if (!n) {
       if (nbad) *nbad = 0;
       return GS_OK;
     }
     // the IC points go up first: without a device this is where the call ends, before any work and with nothing written
     HandleBag bag;
-    gs_handle *ha = &bag.hs[0], *hb = &bag.hs[1], *hc = &bag.hs[2], *hic = &bag.hs[3];
-    bool key_ok = true;
-    int rc = gs_g1_upload(vk_ic, nic, hic);
-    if (rc == GS_ERR_ARG) key_ok = false;                               // an IC point off the curve
-    else if (rc != GS_OK) return rc;
-    const auto all_zero = [&]() -> int {
+    gs_handle* hic = &bag.hs[0];
+    const int rc = gs_g1_upload(vk_ic, nic, hic);
+    if (rc != GS_OK && rc != GS_ERR_ARG) return rc;
+    // the key: a point off its curve (GS_ERR_ARG for one of the IC) or a degenerate step makes every verdict 0, as it makes
+    // gs_groth16_verify answer 0 for every proof
+    gs::Groth16KeyWords words;
+    KeyFault fault;
+    if (rc == GS_ERR_ARG || !prepare_groth16_key(vk_g1_alpha, vk_g2_beta, vk_g2_gamma, vk_g2_delta, words, fault)) {
       for (size_t i = 0; i < n; ++i) ok_each[i] = 0;
       if (nbad) *nbad = n;
       return GS_OK;
-    };
-    // the key: a point off its curve or a degenerate step makes every verdict 0, as it makes gs_groth16_verify answer 0 for every proof
-    const G1Aff alpha = g1_from_jacobian_std(vk_g1_alpha);
-    const G2Aff beta = g2_from_jacobian_std(vk_g2_beta), gamma = g2_from_jacobian_std(vk_g2_gamma), delta = g2_from_jacobian_std(vk_g2_delta);
-    if (!key_ok || !g1_on_curve(alpha) || !g2_on_curve(beta) || !g2_on_curve(gamma) || !g2_on_curve(delta)) return all_zero();
-    Fp12 fab;
-    if (!multi_miller_loop({alpha}, {beta}, fab)) return all_zero();
-    uint64_t ab[48];
-    gs::f12_words(fab, ab);
-    std::vector<uint64_t> gl, dl;
-    if (!gamma.inf && !prepare_g2_lines(gamma, gl)) return all_zero();
-    if (!delta.inf && !prepare_g2_lines(delta, dl)) return all_zero();
-    // the proofs: per proof what the single verifier tests before its pairings
-    std::vector<uint64_t> a(pi_a, pi_a + 12 * n), b(pi_b, pi_b + 24 * n), c(pi_c, pi_c + 12 * n);
-    std::vector<char> bad(n, 0);
-    for (size_t i = 0; i < n; ++i) {
-      if (!groth16_proof_passes_screen(strict, public_signals + 4 * i * npublic, npublic, pi_a + 12 * i, pi_b + 24 * i, pi_c + 12 * i)) {
-        bad[i] = 1;
-        memset(a.data() + 12 * i, 0, 96);
-        memset(b.data() + 24 * i, 0, 192);
-        memset(c.data() + 12 * i, 0, 96);
-      }
     }
-    if ((rc = gs_g1_upload(a.data(), n, ha)) != GS_OK) return rc;
-    if ((rc = gs_g2_upload(b.data(), n, hb)) != GS_OK) return rc;
-    if ((rc = gs_g1_upload(c.data(), n, hc)) != GS_OK) return rc;
-    std::vector<int> member(n), one(n);
-    rc = gs::groth16_verify_each_device(fn, *ha, *hb, *hc, *hic, public_signals, npublic, n, gamma.inf ? nullptr : gl.data(),
-                                        delta.inf ? nullptr : dl.data(), ab, member.data(), one.data());
-    if (rc != GS_OK) return rc;
-    uint64_t count = 0;
-    for (size_t i = 0; i < n; ++i) {
-      ok_each[i] = (!bad[i] && member[i] && one[i]) ? 1 : 0;
-      count += ok_each[i] ? 0 : 1;
-    }
-    if (nbad) *nbad = count;
-    return GS_OK;
+    if (npublic >= 0xffffffffull) return fail(GS_ERR_SHAPE, "%s: %zu proofs, indices are 32 bits", fn, n);
+    gs::Groth16CallKeys key;
+    key.ic = *hic;
+    key.npublic = npublic;
+    key.words = &words;
+    const uint32_t np = (uint32_t)npublic;
+    const std::vector<uint32_t> key_of_proof(n, 0);                     // one key: the trivial plan
+    return groth16_verdicts(fn, key, &np, key_of_proof.data(), strict, public_signals, pi_a, pi_b, pi_c, n, ok_each, nbad);
   });
 }
 
-// gs_groth16_vk_create (include/gosnark_hip.h): the per-key host work of gs_groth16_verify_each, done once: the curve tests of the key,
-// the Miller value of e(alpha, beta) and the prepared lines of gamma and delta, kept on the device beside the IC points.  Where
-// gs_groth16_verify_each answers a key that cannot verify anything with all-zero verdicts, this call refuses to install it.
+// gs_groth16_vk_create (include/gosnark_hip.h): the per-key host work of gs_groth16_verify_each, done once and kept on the device
+// beside the IC points.  Where gs_groth16_verify_each answers a key that cannot verify anything with all-zero verdicts, this call
+// refuses to install it.
 int gs_groth16_vk_create(const uint64_t vk_g1_alpha[12], const uint64_t vk_g2_beta[24], const uint64_t vk_g2_gamma[24],
                          const uint64_t vk_g2_delta[24], const uint64_t* vk_ic, size_t nic, gs_handle* out) {
   return host_guarded([&]() -> int {
@@ -476,29 +509,19 @@ int gs_groth16_vk_create(const uint64_t vk_g1_alpha[12], const uint64_t vk_g2_be
         if (!g1_on_curve(g1_from_jacobian_std(vk_ic + 12 * j))) return fail(GS_ERR_ARG, "%s: IC[%zu] is not on the curve", fn, j);
     }
     if (rc != GS_OK) return rc;
-    const G1Aff alpha = g1_from_jacobian_std(vk_g1_alpha);
-    const G2Aff beta = g2_from_jacobian_std(vk_g2_beta), gamma = g2_from_jacobian_std(vk_g2_gamma), delta = g2_from_jacobian_std(vk_g2_delta);
-    if (!g1_on_curve(alpha)) return fail(GS_ERR_ARG, "%s: alpha is not on the curve", fn);
-    if (!g2_on_curve(beta)) return fail(GS_ERR_ARG, "%s: beta is not on the twist", fn);
-    if (!g2_on_curve(gamma)) return fail(GS_ERR_ARG, "%s: gamma is not on the twist", fn);
-    if (!g2_on_curve(delta)) return fail(GS_ERR_ARG, "%s: delta is not on the twist", fn);
-    Fp12 fab;
-    if (!multi_miller_loop({alpha}, {beta}, fab)) return fail(GS_ERR_ARG, "%s: beta is not of order r (a degenerate step in its Miller loop)", fn);
-    uint64_t ab[48];
-    gs::f12_words(fab, ab);
-    std::vector<uint64_t> gl, dl;
-    if (!gamma.inf && !prepare_g2_lines(gamma, gl)) return fail(GS_ERR_ARG, "%s: gamma is not of order r (a degenerate step in its prepared lines)", fn);
-    if (!delta.inf && !prepare_g2_lines(delta, dl)) return fail(GS_ERR_ARG, "%s: delta is not of order r (a degenerate step in its prepared lines)", fn);
+    gs::Groth16KeyWords words;
+    KeyFault fault;
+    if (!prepare_groth16_key(vk_g1_alpha, vk_g2_beta, vk_g2_gamma, vk_g2_delta, words, fault))
+      return fail(GS_ERR_ARG, "%s: %s %s", fn, fault.point, fault.why);
     gs_handle h = 0;
-    if ((rc = gs::groth16_vk_install(fn, *hic, nic, gamma.inf ? nullptr : gl.data(), delta.inf ? nullptr : dl.data(), ab, &h)) != GS_OK) return rc;
+    if ((rc = gs::groth16_vk_install(fn, *hic, nic, words, &h)) != GS_OK) return rc;
     *out = h;
     return GS_OK;
   });
 }
 
 // gs_groth16_verify_each_keys (include/gosnark_hip.h): gs_groth16_verify_each for proofs that each name their key.  The keys are
-// prepared objects, so what is left for the host is per proof: the screening of the 3n points and the permutation into the slot order
-// of verify_plan.h, one key per one-wave workgroup.
+// prepared objects, so what is left for the host is per proof (groth16_verdicts).
 int gs_groth16_verify_each_keys(const gs_handle* keys, size_t nkeys, const uint32_t* key_of_proof, const uint64_t* public_signals,
                                 const uint64_t* pi_a, const uint64_t* pi_b, const uint64_t* pi_c, size_t nproofs, int* ok_each, uint64_t* nbad) {
   return host_guarded([&]() -> int {
@@ -516,53 +539,15 @@ int gs_groth16_verify_each_keys(const gs_handle* keys, size_t nkeys, const uint3
         return fail(GS_ERR_ARG, "%s: keys[%zu] lives on logical device %d, keys[0] on %d", fn, k, handle_device(keys[k]), handle_device(keys[0]));
     // the keys' signal counts: without a device this is where the call ends, before any work and with nothing written
     std::vector<uint32_t> npublic(nkeys);
-    int rc = gs::groth16_vk_info(fn, keys, nkeys, npublic.data());
+    const int rc = gs::groth16_vk_info(fn, keys, nkeys, npublic.data());
     if (rc != GS_OK) return rc;
     const int here = gs_get_device();                                   // the proofs' arrays are created where the calling thread works
     if (handle_device(keys[0]) != here)
       return fail(GS_ERR_ARG, "%s: the keys live on logical device %d, the calling thread works on %d (gs_set_device)", fn, handle_device(keys[0]), here);
-    VerifyPlan plan;
-    const VerifyPlanStatus ps = plan_verify_slots(key_of_proof, n, nkeys, npublic.data(), plan);
-    if (ps != kVpOk) return fail(GS_ERR_SHAPE, "%s: %zu proofs need more than 2^32 slots (64 per key and started group): pass them in windows", fn, n);
-    if (plan.nsignals && !public_signals) return fail(GS_ERR_ARG, "%s: null argument", fn);
-    const bool strict = g_strict.load() != 0;
-    // the proofs in slot order: per proof what the single verifier tests before its pairings; infinity in bad and in padded slots
-    const size_t slots = plan.proof_of_slot.size();
-    std::vector<uint64_t> a(12 * slots, 0), b(24 * slots, 0), c(12 * slots, 0), pub(plan.nsignals ? 4 * (size_t)plan.nsignals : 4, 0);
-    std::vector<const uint64_t*> pub_of(n);
-    {
-      const uint64_t* at = public_signals;
-      for (size_t i = 0; i < n; ++i) { pub_of[i] = at; at += 4 * (size_t)npublic[key_of_proof[i]]; }
-    }
-    std::vector<char> bad(n, 0);
-    for (size_t g = 0; g < plan.groups.size(); ++g) {
-      const size_t np = npublic[plan.groups[g].key];
-      for (uint32_t l = 0; l < plan.groups[g].valid; ++l) {
-        const size_t s = g * kVpLanes + l, i = plan.proof_of_slot[s];
-        if (np) memcpy(pub.data() + 4 * ((size_t)plan.groups[g].sig_off + l * np), pub_of[i], 32 * np);
-        if (!groth16_proof_passes_screen(strict, pub_of[i], np, pi_a + 12 * i, pi_b + 24 * i, pi_c + 12 * i)) { bad[i] = 1; continue; }
-        memcpy(a.data() + 12 * s, pi_a + 12 * i, 96);
-        memcpy(b.data() + 24 * s, pi_b + 24 * i, 192);
-        memcpy(c.data() + 12 * s, pi_c + 12 * i, 96);
-      }
-    }
-    HandleBag bag;
-    gs_handle *ha = &bag.hs[0], *hb = &bag.hs[1], *hc = &bag.hs[2];
-    if ((rc = gs_g1_upload(a.data(), slots, ha)) != GS_OK) return rc;
-    if ((rc = gs_g2_upload(b.data(), slots, hb)) != GS_OK) return rc;
-    if ((rc = gs_g1_upload(c.data(), slots, hc)) != GS_OK) return rc;
-    std::vector<int> member(slots), one(slots);
-    rc = gs::groth16_verify_each_keys_device(fn, keys, nkeys, *ha, *hb, *hc, plan.groups.data(), plan.groups.size(), pub.data(), plan.nsignals,
-                                             member.data(), one.data());
-    if (rc != GS_OK) return rc;
-    uint64_t count = 0;
-    for (size_t i = 0; i < n; ++i) {
-      const size_t s = plan.slot_of_proof[i];
-      ok_each[i] = (!bad[i] && member[s] && one[s]) ? 1 : 0;
-      count += ok_each[i] ? 0 : 1;
-    }
-    if (nbad) *nbad = count;
-    return GS_OK;
+    gs::Groth16CallKeys prepared;
+    prepared.keys = keys;
+    prepared.nkeys = nkeys;
+    return groth16_verdicts(fn, prepared, npublic.data(), key_of_proof, g_strict.load() != 0, public_signals, pi_a, pi_b, pi_c, n, ok_each, nbad);
   });
 }
 
@@ -579,10 +564,8 @@ int gs_pinocchio_verify_each(const uint64_t vka[24], const uint64_t vkb[12], con
     const size_t n = nproofs;
     if (!vka || !vkb || !vkc || !g1kbg || !g2kbg || !g2kg || !vkz || !vk_ic || (n && (!proofs || !ok_each)) || (n && npublic && !public_signals))
       return fail(GS_ERR_ARG, "%s: null argument", fn);
-    if (nic < npublic + 1) return fail(GS_ERR_SHAPE, "%s: %zu public signals need %zu IC points, vk has %zu", fn, npublic, npublic + 1, nic);
-    const bool strict = g_strict.load() != 0;
-    if (strict && nic != npublic + 1)
-      return fail(GS_ERR_SHAPE, "%s (strict): vk has %zu IC points, so exactly %zu public signals are required (got %zu)", fn, nic, nic - 1, npublic);
+    bool strict;
+    if (const int shape = check_signal_count(fn, nic, npublic, &strict)) return shape;
     if (!n) {
       if (nbad) *nbad = 0;
       return GS_OK;
@@ -612,7 +595,6 @@ int gs_pinocchio_verify_each(const uint64_t vka[24], const uint64_t vkb[12], con
     memcpy(key_g1 + 12, g1kbg, 96);
     if (!g1_on_curve(g1_from_jacobian_std(vkb))) { key_fail |= eq(2); memset(key_g1, 0, 96); }
     if (!g1_on_curve(g1_from_jacobian_std(g1kbg))) { key_fail |= eq(5); memset(key_g1 + 12, 0, 96); }
-    constexpr size_t kLineStd = (size_t)kPreparedSteps * 16;
     enum { kVka = 0, kVkc, kVkz, kG2Kbg, kG2Kg, kGen, kLists };        // pairing_device.hip, the order of the lists
     const uint64_t* key_g2[kLists] = {vka, vkc, vkz, g2kbg, g2kg, kG2Gen};
     const unsigned uses[kLists] = {eq(1), eq(3), eq(4), eq(5), eq(5), 0};

@@ -59,19 +59,9 @@ static void rd_words(std::istringstream& ss, uint64_t* w, int count) {
   }
 }
 static H::Fp2 host_f2(const uint64_t* w) { return H::Fp2{H::fp_from_std(w), H::fp_from_std(w + 4)}; }
-static H::Fp12 host_f12(const uint64_t* w) {
-  H::Fp12 f;
-  H::Fp2* c[6] = {&f.a0.c0, &f.a0.c1, &f.a0.c2, &f.a1.c0, &f.a1.c1, &f.a1.c2};
-  for (int i = 0; i < 6; ++i) *c[i] = host_f2(w + 8 * i);
-  return f;
-}
-static void host_words(const H::Fp12& f, uint64_t* w) {
-  const H::Fp2* c[6] = {&f.a0.c0, &f.a0.c1, &f.a0.c2, &f.a1.c0, &f.a1.c1, &f.a1.c2};
-  for (int i = 0; i < 6; ++i) { H::fp_to_std(c[i]->c0, w + 8 * i); H::fp_to_std(c[i]->c1, w + 8 * i + 4); }
-}
 static std::string show(const H::Fp12& f) {
   uint64_t w[48];
-  host_words(f, w);
+  H::f12_to_std(f, w);
   return hex_words(w, 12);
 }
 static std::string show(const Fq12& f) {
@@ -81,7 +71,7 @@ static std::string show(const Fq12& f) {
 }
 static Fq12 eng_f12(const H::Fp12& f) {
   uint64_t w[48];
-  host_words(f, w);
+  H::f12_to_std(f, w);
   Fq12 r;
   f12_from_std(r, w);
   return r;
@@ -132,7 +122,7 @@ int main() {
       rd_words(ss, a, 12);
       Fq12 fa;
       f12_from_std(fa, a);
-      const H::Fp12 ha = host_f12(a);
+      const H::Fp12 ha = H::f12_from_std(a);
       Fq12Bank bank;
       if (op == "conj") {
         f12_conj(fa);

@@ -48,16 +48,9 @@ static void rd_words(std::istringstream& ss, uint64_t* w, int count) {
   }
 }
 static H::Fp2 host_f2(const uint64_t* w) { return H::Fp2{H::fp_from_std(w), H::fp_from_std(w + 4)}; }
-static H::Fp12 host_f12(const uint64_t* w) {
-  H::Fp12 f;
-  H::Fp2* c[6] = {&f.a0.c0, &f.a0.c1, &f.a0.c2, &f.a1.c0, &f.a1.c1, &f.a1.c2};
-  for (int i = 0; i < 6; ++i) *c[i] = host_f2(w + 8 * i);
-  return f;
-}
 static std::string show(const H::Fp12& f) {
   uint64_t w[48];
-  const H::Fp2* c[6] = {&f.a0.c0, &f.a0.c1, &f.a0.c2, &f.a1.c0, &f.a1.c1, &f.a1.c2};
-  for (int i = 0; i < 6; ++i) { H::fp_to_std(c[i]->c0, w + 8 * i); H::fp_to_std(c[i]->c1, w + 8 * i + 4); }
+  H::f12_to_std(f, w);
   return hex_words(w, 12);
 }
 static std::string show(const Fq12& f) {
@@ -87,10 +80,10 @@ int main() {
         rd_words(ss, b, 12);
         f12_from_std(fb, b);
         f12_mul(fa, fb);
-        std::cout << show(fa) << " " << show(H::f12_mul(host_f12(a), host_f12(b))) << "\n";
+        std::cout << show(fa) << " " << show(H::f12_mul(H::f12_from_std(a), H::f12_from_std(b))) << "\n";
       } else {
         f12_sqr(fa);
-        std::cout << show(fa) << " " << show(H::f12_sqr(host_f12(a))) << "\n";
+        std::cout << show(fa) << " " << show(H::f12_sqr(H::f12_from_std(a))) << "\n";
       }
     } else if (op == "line") {
       uint64_t a[48], l[24];
@@ -100,8 +93,8 @@ int main() {
       f12_from_std(fa, a);
       f12_mul_line(fa, eng_f2(l), eng_f2(l + 8), eng_f2(l + 16));
       H::Fp12 g{H::Fp6{host_f2(l), H::f2_zero(), H::f2_zero()}, H::Fp6{host_f2(l + 8), host_f2(l + 16), H::f2_zero()}};
-      std::cout << show(fa) << " " << show(H::f12_mul(host_f12(a), g)) << " "
-                << show(H::f12_mul_line(host_f12(a), H::fp_from_std(l), host_f2(l + 8), host_f2(l + 16))) << "\n";
+      std::cout << show(fa) << " " << show(H::f12_mul(H::f12_from_std(a), g)) << " "
+                << show(H::f12_mul_line(H::f12_from_std(a), H::fp_from_std(l), host_f2(l + 8), host_f2(l + 16))) << "\n";
     } else if (op == "pair") {
       Affine<FqTag> p;
       Affine<Fq2Tag> q;
@@ -135,7 +128,7 @@ int main() {
       f12_to_std(f, fw);
       H::Fp12 want;
       if (!H::multi_miller_loop({hp}, {hq}, want)) { std::cout << "degenerate\n"; continue; }
-      std::cout << show(H::final_exponentiation(host_f12(fw))) << " " << show(H::final_exponentiation(want)) << "\n";
+      std::cout << show(H::final_exponentiation(H::f12_from_std(fw))) << " " << show(H::final_exponentiation(want)) << "\n";
     } else {
       std::cout << "?\n";
     }

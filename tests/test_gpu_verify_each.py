@@ -14,6 +14,7 @@ import gosnark_amd  # noqa: F401
 from gosnark_amd import capi, groth16, utils
 import golden_util as GU
 import membership_util as M
+import multikey_util as MK
 from oracle import ref_py as O
 
 pytestmark = pytest.mark.gpu
@@ -214,6 +215,50 @@ def test_keys_with_0_and_3_public_inputs_from_known_discrete_logs(npublic):
     host = [groth16.VerifyProof(vk, p, s) for p, s in zip(proofs, signals)]
     assert host == [i % 2 == 0 for i in range(n)]                       # the construction accepts, the perturbation does not
     assert groth16.VerifyProofsEach(vk, proofs, signals) == host
+
+
+@pytest.mark.parametrize("which", ["gamma", "delta"])
+def test_an_infinite_gamma_or_delta_in_one_full_group_and_two_lanes(which):
+    """The key's skip flags travel in the call's key record: 66 proofs, one change of every kind on both sides of the group seam.  With an
+    infinite gamma the signals, with an infinite delta C, do not enter the product: the host verifier says what such a change does."""
+    d = MK.DlogKey(1, 620 + len(which), gamma_infinite=which == "gamma", delta_infinite=which == "delta")
+    proofs, signals = d.proofs(66)
+    changed = {0: "A", 63: "B", 64: "C", 65: "public"}
+    for at, what in changed.items():
+        proofs[at], signals[at] = MK.tamper(proofs[at], signals[at], what)
+    before = capi.alloc_counters()
+    got = agree(d.vk, proofs, signals, set(changed), expect_false=False)
+    after = capi.alloc_counters()
+    assert got[0] is False and got[63] is False                         # A and B enter the product whatever the key is
+    assert after[0] - before[0] == after[1] - before[1]                 # the key made for the call leaves nothing behind
+
+
+def test_fewer_signals_than_ic_points_outside_strict_mode():
+    """npublic = 2 under a key with four IC points: the call's key record carries the call's count, not the key's.  The yardstick is
+    gs_groth16_verify with the same two signals, which reads the missing third one as 0."""
+    d = MK.DlogKey(3, 640)
+    n = 65
+    both = [d.proof(sig=[d.rng.randrange(R), d.rng.randrange(R), 0]) for _ in range(n)]
+    proofs, pubs = [p for p, _ in both], [s[:2] for _, s in both]
+    for at, what in ((0, "A"), (64, "public")):
+        proofs[at], pubs[at] = MK.tamper(proofs[at], pubs[at], what)
+    host = [groth16.VerifyProof(d.vk, p, s) for p, s in zip(proofs, pubs)]
+    assert host == [i not in (0, 64) for i in range(n)]
+    lib = capi.load_library()
+    before = capi.alloc_counters()
+    assert _raw_call(d.vk, proofs, pubs) == (0, [int(h) for h in host], 2)
+    try:
+        assert lib.gs_verify_set_strict(1) == 0
+        assert _raw_call(d.vk, proofs, pubs) == (-4, [7] * n, 77)       # GS_ERR_SHAPE, nothing written
+        assert b"exactly 3 public signals" in lib.gs_last_error()
+    finally:
+        lib.gs_verify_set_strict(0)
+    dx, dy, dz = d.vk.G2_Delta
+    bad_key = groth16.Vk(IC=d.vk.IC, G1_Alpha=d.vk.G1_Alpha, G2_Beta=d.vk.G2_Beta, G2_Gamma=d.vk.G2_Gamma, G2_Delta=(dx, (dy[0], (dy[1] + 1) % Q), dz))
+    assert not groth16.VerifyProof(bad_key, proofs[1], pubs[1])
+    assert _raw_call(bad_key, proofs, pubs) == (0, [0] * n, n)           # a key point off its curve: every verdict 0
+    after = capi.alloc_counters()
+    assert after[0] - before[0] == after[1] - before[1]
 
 
 def test_ragged_input_raises_like_verify_proofs(batch):

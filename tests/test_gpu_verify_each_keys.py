@@ -185,8 +185,10 @@ def test_one_key_only_equals_verify_proofs_each(zoo):
     proofs, signals = d.proofs(130)
     for at, what in ((0, "A"), (63, "public"), (64, "C"), (65, "B"), (129, "public")):
         proofs[at], signals[at] = MK.tamper(proofs[at], signals[at], what)
-    want = groth16.VerifyProofsEach(d.vk, proofs, signals)                 # untouched code
-    assert want == [i not in (0, 63, 64, 65, 129) for i in range(130)]
+    want = [i not in (0, 63, 64, 65, 129) for i in range(130)]
+    for i, host in MK.host_verdicts([d.vk], [0] * 130, proofs, signals, only=(0, 63, 64, 65, 129)).items():
+        assert host == want[i], i
+    assert groth16.VerifyProofsEach(d.vk, proofs, signals) == want
     key = groth16.PrepareVerificationKey(d.vk)
     assert groth16.VerifyProofsEachKeys([key], [0] * 130, proofs, signals) == want
     key.handle.free()
