@@ -8,7 +8,7 @@ import ctypes
 
 import numpy as np
 
-from . import capi
+from . import capi, r1csqap
 from .capi import call, harr, ptr64, raw
 
 GS_ERR_BUSY = -6
@@ -115,6 +115,22 @@ def generate(S, circuit, pk, w, px, rs=()):
 def generate_from_witness(S, circuit, pk, r1cs, w, rs=()):
     dev, wa = resident(S, circuit, pk), host_scalars(S, w, "witness")
     return _unless_busy(S, lambda: prove_witness_host_begin(S, dev, r1cs, wa, rs), lambda: prove_from_witness_host(S, dev, r1cs, wa, rs))
+
+
+def generate_checked(S, circuit, pk, r1cs, w, rs=(), check_r1cs=None):
+    """Refusal on request: the witness is uploaded once, checked against ALL constraints of `check_r1cs` (default: `r1cs`; the
+    three-matrix system of circuit.r1cs when `r1cs` is a .zkey key's product system) with cap 16, and only a witness that passes is
+    proved, from the same resident vector (prove_witness).  A bad one raises r1csqap.WitnessError before anything is proved."""
+    dev = resident(S, circuit, pk)
+    dw = capi.scalars_upload(host_scalars(S, w, "witness"))
+    try:
+        report = (r1cs if check_r1cs is None else check_r1cs).CheckWitness(dw, cap=16)
+        if not report:
+            report._witness = w
+            raise r1csqap.WitnessError(report)
+        return prove(S, "prove_witness", dev, r1cs, dw, rs)
+    finally:
+        dw.free()
 
 
 class Prover:

@@ -97,6 +97,7 @@ _SIGS = {
                       u64p, u64p, u64p, u64p, u64p],
     "gs_r1cs_upload": [ctypes.c_size_t, ctypes.c_size_t, u32p, u32p, u64p, u32p, u32p, u64p, u32p, u32p, u64p, ctypes.POINTER(Handle)],
     "gs_r1cs_px": [Handle, Handle, ctypes.POINTER(Handle)],
+    "gs_r1cs_check": [Handle, Handle, ctypes.c_size_t, u64p, u32p, u64p],
     "gs_r1cs_upload_domain": [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, u32p, u32p, u64p, u32p, u32p, u64p, u32p, u32p, u64p,
                               ctypes.POINTER(Handle)],
     "gs_groth16_pk_derive_eval_domain": [Handle, ctypes.c_size_t],
@@ -597,6 +598,19 @@ def r1cs_colsum(r1cs, basis_a=None, basis_b=None, basis_c=None, g2=False):
     cell = HandleCell()
     call("gs_r1cs_colsum_g2" if g2 else "gs_r1cs_colsum_g1", raw(r1cs), raw(basis_a), raw(basis_b), raw(basis_c), cell.ref)
     return cell.result()
+
+
+def r1cs_check(r1cs, w, cap=16):
+    """gs_r1cs_check: which of ALL n constraints of a resident three-matrix R1CS a resident witness breaks -> (count, the first
+    min(cap, count) violated rows in ascending order, their (A w, B w, C w) as an [rows, 3, 4] uint64 array, canonical)."""
+    cap = int(cap)
+    if cap < 0:
+        raise ValueError("gs_r1cs_check: cap = %d" % cap)
+    count = ctypes.c_uint64(0)
+    rows, values = np.zeros(cap, dtype=np.uint32), np.zeros((cap, 3, 4), dtype=np.uint64)
+    call("gs_r1cs_check", raw(r1cs), raw(w), cap, ctypes.byref(count), ptr32(rows) if cap else None, ptr64(values) if cap else None)
+    k = min(cap, int(count.value))
+    return int(count.value), rows[:k], values[:k]
 
 
 def g1_scale(bases, k):

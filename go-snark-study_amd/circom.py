@@ -172,6 +172,13 @@ def GenerateProofs(dev_pk, dev_r1cs, w, r=None, s=None):
     return GenerateProofsWithRS(dev_pk, dev_r1cs, w, groth16.FqRRand() if r is None else r, groth16.FqRRand() if s is None else s)
 
 
+def GenerateProofsChecked(dev_pk, dev_r1cs, w, check_r1cs=None, r=None, s=None):
+    """GenerateProofs that refuses a witness which breaks a constraint (r1csqap.WitnessError, nothing proved).  check_r1cs: the system
+    the witness is checked against, default dev_r1cs -- for a .zkey key, whose own system is a product system without C, the
+    three-matrix system of circuit.r1cs (a DeviceDomainR1CS; CheckWtns builds the same one)."""
+    return groth16.GenerateProofsChecked(None, dev_pk, dev_r1cs, w, r, s, check_r1cs)
+
+
 def VerifyFromCircom(vk, proof, public):
     """externalVerif/circomVerifier.go:26-90 on parsed JSON (dictionaries / lists as json.load returns them, or the parsed objects)
     -> bool, over gs_groth16_verify (host side, needs no device)."""
@@ -945,6 +952,17 @@ def _setup_system(r1cs, k):
     val_a = np.concatenate([r1cs.a[2].reshape(-1, 4), one])
     pad = lambda m: (np.concatenate([m[0], np.full(npub, m[0][-1], dtype=np.uint32)]), m[1], m[2])      # noqa: E731
     return DeviceDomainR1CS(k, (rp_a, col_a, val_a), pad(r1cs.b), pad(r1cs.c), r1cs.nVars)
+
+
+def CheckWtns(r1cs_path, wtns_path, cap=16):
+    """What `snarkjs wtns check` answers, on the device: which constraints of circuit.r1cs does witness.wtns break?  ->
+    r1csqap.WitnessReport (report.explain(i, ReadR1cs(r1cs_path)) spells a reported row out).  The system is the one SetupFromPtau
+    builds the key on; its appended rows hold no B and no C and are satisfied by every witness, so a reported row is a constraint of
+    the file."""
+    r1cs, w = ReadR1cs(r1cs_path), ReadWtns(wtns_path)
+    if w.shape[0] != r1cs.nWires:
+        raise ValueError("%s holds %d values, %s has nWires = %d" % (wtns_path, w.shape[0], r1cs_path, r1cs.nWires))
+    return _setup_system(r1cs, _setup_domain_bits(r1cs)).CheckWitness(np.ascontiguousarray(w, dtype=np.uint64), cap)
 
 
 def SetupFromPtau(r1cs_path, ptau_path, zkey_path, timing=None, prepared=False):

@@ -44,6 +44,7 @@ uint64_t object_bytes(Object* o) {
     case Kind::R1cs: {
       auto* r = static_cast<R1csObj*>(o);
       uint64_t t = r->w_mont.bytes + r->vals.bytes + r->coef.bytes + r->prod.bytes;
+      t += r->chk_w_mont.bytes + r->chk_vals.bytes + r->chk_pos.bytes + r->chk_tiles.bytes + r->chk_rows.bytes + r->chk_values.bytes;
       for (int i = 0; i < 3; ++i) t += r->rowptr[i].bytes + r->col[i].bytes + r->val[i].bytes;
       return t;
     }

@@ -1,6 +1,7 @@
 // Sparse R1CS on the device (include/gosnark_hip.h, "R1CS"): upload, and witness -> constraint values -> ax, bx, cx, px.
 #include "prove.h"
 #include "domain.h"
+#include "scan.h"
 
 #include <algorithm>
 
@@ -45,19 +46,22 @@ static int r1cs_upload_impl(Ctx& c, size_t n, size_t m, const uint32_t* const rp
 // w (standard form, m elements, device) -> o.vals = [A w | B w | C w] (o.points() each, standard form): the values of ax, bx, cx at the
 // nodes 1..n (CombinePolynomials' sum_i w_i alpha_i(x) evaluated there, r1csqap.go:191-210) -- or, for a domain R1CS, at omega^0 ..
 // omega^(n-1), followed by the zeros of the empty rows up to 2^k
-void gs::r1cs_values_dev(Ctx& c, R1csObj& o, const uint32_t* w_dev) {
+void gs::r1cs_values_dev(Ctx& c, R1csObj& o, const uint32_t* w_dev) { r1cs_values_into_dev(c, o, w_dev, o.w_mont, o.vals); }
+// The same stage into workspaces the caller names (grown here): gs_r1cs_check keeps its own pair, because o.w_mont and o.vals belong to
+// the polynomial stage of the proofs in flight on this system.
+void gs::r1cs_values_into_dev(Ctx& c, R1csObj& o, const uint32_t* w_dev, DevBuf& w_mont, DevBuf& vals) {
   const size_t n = o.n, m = o.m, np = o.points();
-  o.w_mont.ensure(m * 32); o.vals.ensure(3 * np * 32);
-  GS_HIP(hipMemcpyAsync(o.w_mont.p, w_dev, m * 32, hipMemcpyDeviceToDevice, c.stream));
-  poly_canon_dev(c, o.w_mont.as<uint32_t>(), m, 1);                                         // w -> Montgomery
+  w_mont.ensure(m * 32); vals.ensure(3 * np * 32);
+  GS_HIP(hipMemcpyAsync(w_mont.p, w_dev, m * 32, hipMemcpyDeviceToDevice, c.stream));
+  poly_canon_dev(c, w_mont.as<uint32_t>(), m, 1);                                           // w -> Montgomery
   for (int k = 0; k < (o.product ? 2 : 3); ++k) {
-    uint32_t* out = o.vals.as<uint32_t>() + k * np * 8;
-    spmv_dev(c, o.rowptr[k].as<uint32_t>(), o.col[k].as<uint32_t>(), o.val[k].as<uint32_t>(), o.w_mont.as<uint32_t>(), n, m, out);
+    uint32_t* out = vals.as<uint32_t>() + k * np * 8;
+    spmv_dev(c, o.rowptr[k].as<uint32_t>(), o.col[k].as<uint32_t>(), o.val[k].as<uint32_t>(), w_mont.as<uint32_t>(), n, m, out);
     if (np > n) GS_HIP(hipMemsetAsync(out + n * 8, 0, (np - n) * 32, c.stream));
   }
   // a product system: [A w | B w | a o b], the third vector by one point-wise kernel (not fused into the first transform pass: that
   // pass is shared with every other caller of ntt_forward_n, and the vector is 32 B per point against the three transforms' 6 passes)
-  if (o.product) r1cs_product_dev(c, o.vals.as<uint32_t>(), np);
+  if (o.product) r1cs_product_dev(c, vals.as<uint32_t>(), np);
 }
 
 // w -> o.coef = [ax | bx | cx] (o.points() each) and px_out (o.npx()), canonical standard form
@@ -167,6 +171,56 @@ int gs_r1cs_px(gs_handle hr1cs, gs_handle hw, gs_handle* px_inout) {
     if (!c.any_inflight()) reset_timing(c);
     c.timing.poly_ms = t.ms();
     c.timing.total_ms = c.timing.poly_ms;
+    return GS_OK;
+  }, true, true, hr1cs);
+}
+
+// Which constraints does a resident witness break?  All n rows, not the roots of a key's Z; no key needed (include/gosnark_hip.h).
+// Runs beside proofs in flight (allow_inflight): on the polynomial stream like gs_r1cs_px -- never the accumulation stream; spmv_dev's
+// hand-off list of long rows is shared with the proofs' polynomial stages, and stream order keeps it consistent -- but in workspaces
+// of its own (R1csObj::chk_*), since o.vals of a proof in flight is still read after this call was enqueued.  The call waits for its
+// own stream position only, so when it returns the device has finished reading w: like every blocking entry point it leaves no read
+// mark on the vector (runtime.h, Scalars), and a gs_scalars_update that follows cannot overtake it.
+int gs_r1cs_check(gs_handle hr1cs, gs_handle hw, size_t cap, uint64_t* nviolated, uint32_t* rows, uint64_t* values) {
+  return guarded([&](Ctx& c) -> int {
+    const char* fn = "gs_r1cs_check";
+    if (!nviolated) return fail(GS_ERR_ARG, "%s: null nviolated", fn);
+    if (cap && !rows) return fail(GS_ERR_ARG, "%s: cap = %zu but rows is null", fn, cap);
+    R1csObj* o = c.get<R1csObj>(hr1cs, Kind::R1cs);
+    Scalars* w = c.get<Scalars>(hw, Kind::Scalars);
+    if (!o || !w) return fail(GS_ERR_ARG, "%s: bad handle (an R1CS and a scalar vector of the same logical device)", fn);
+    if (o->product)
+      return fail(GS_ERR_SHAPE, "%s: a .zkey key's system holds A and B only, no C (c = a b by definition): the check needs the three "
+                                "matrices of circuit.r1cs (gs_r1cs_upload / gs_r1cs_upload_domain)", fn);
+    if (w->n != o->m) return fail(GS_ERR_SHAPE, "len(w) = %zu but the system has %zu variables", w->n, o->m);
+    const size_t n = o->n, capd = std::min(cap, n);
+    o->chk_pos.ensure((n + 1) * 4);
+    o->chk_tiles.ensure((size_t)scan_tiles(n + 1) * 4);
+    if (capd) { o->chk_rows.ensure(capd * 4); o->chk_values.ensure(capd * 96); }
+    uint32_t* pos = o->chk_pos.as<uint32_t>();
+    StreamScope sc(c, c.aux_stream[1]);
+    PhaseTimer total(c.stream), tvals(c.stream);
+    r1cs_values_into_dev(c, *o, w->buf.as<uint32_t>(), o->chk_w_mont, o->chk_vals);
+    tvals.stop();
+    PhaseTimer trows(c.stream);
+    r1cs_check_rows_dev(c, o->chk_vals.as<uint32_t>(), n, o->points(), pos, o->chk_tiles.as<uint32_t>(), capd, o->chk_rows.as<uint32_t>(),
+                        o->chk_values.as<uint32_t>());
+    trows.stop();
+    uint32_t count = 0;
+    GS_HIP(hipMemcpyAsync(&count, pos + n, 4, hipMemcpyDeviceToHost, c.stream));
+    GS_HIP(hipStreamSynchronize(c.stream));
+    const size_t k = std::min<size_t>(count, capd);           // nothing at and beyond it is written
+    if (k) {
+      GS_HIP(hipMemcpyAsync(rows, o->chk_rows.p, k * 4, hipMemcpyDeviceToHost, c.stream));
+      if (values) GS_HIP(hipMemcpyAsync(values, o->chk_values.p, k * 96, hipMemcpyDeviceToHost, c.stream));
+    }
+    total.stop();
+    GS_HIP(hipStreamSynchronize(c.stream));
+    *nviolated = count;
+    if (!c.any_inflight()) reset_timing(c);
+    c.timing.poly_ms = tvals.ms();
+    c.timing.reduce_ms = trows.ms();
+    c.timing.total_ms = total.ms();                           // with the result copies: gs_timing has no field for them
     return GS_OK;
   }, true, true, hr1cs);
 }

@@ -66,6 +66,12 @@ bool hx_direct_dev(Ctx& c, const uint32_t* vals_std, size_t n, size_t dz, uint32
 // it collects the proof, and takes the exact route if it is not zero); hx_from_values_dev: values -> coefficients.
 bool hx_values_dev(Ctx& c, const uint32_t* vals_std, size_t n, size_t dz, uint32_t* hv_out_std);
 void r1cs_check_dev(Ctx& c, const uint32_t* vals_std, size_t n, size_t dz, uint32_t* bad_dev);
+// r1cs_check_rows_dev: which of ALL n rows violate a b = c -- not the roots of a key's Z, which is r1cs_check_dev's criterion.  vals =
+// [a | b | c], `stride` elements each (n <= stride), standard form.  pos (n + 1 words) receives the exclusive prefix sums of the rows'
+// flags, so pos[n] is the count; rows / values (cap slots, cap <= n; unused when cap = 0) receive the first cap violated rows in
+// ascending order and their three values, canonical.  tile_sum: scan_tiles(n + 1) words of scratch (scan.h).  Enqueue only.
+void r1cs_check_rows_dev(Ctx& c, const uint32_t* vals_std, size_t n, size_t stride, uint32_t* pos, uint32_t* tile_sum, size_t cap, uint32_t* rows,
+                         uint32_t* values);
 // r1cs_product_dev: the third vector of vals = [a | b | .] (n each) becomes a_j b_j -- a product system has no C matrix (enqueue only)
 void r1cs_product_dev(Ctx& c, uint32_t* vals_std, size_t n);
 void hx_from_values_dev(Ctx& c, const uint32_t* hv_std, size_t n, size_t dz, uint32_t* hx_out_std);

@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "poly_kernels.h"
+#include "scan.h"
 
 namespace gs {
 
@@ -542,6 +543,17 @@ void r1cs_check_dev(Ctx& c, const uint32_t* vals_std, size_t n, size_t dz, uint3
   for (int i = 0; i < NL; ++i) r2.l[i] = ModR::r2(i);
   GS_HIP(hipMemsetAsync(bad_dev, 0, 4, c.stream));
   if (n) hipLaunchKernelGGL(k_r1cs_check, grid1(n), dim3(256), 0, c.stream, vals_std, (uint32_t)n, (uint32_t)dz, to_const(relax<2>(r2)), bad_dev);
+  GS_HIP(hipGetLastError());
+}
+
+// The rows of ALL n that violate a b = c, in order (poly.h): one word per row, the prefix sums of scan.h, one gather.  Enqueue only.
+void r1cs_check_rows_dev(Ctx& c, const uint32_t* vals_std, size_t n, size_t stride, uint32_t* pos, uint32_t* tile_sum, size_t cap, uint32_t* rows,
+                         uint32_t* values) {
+  Fe<ModR, 1> r2;
+  for (int i = 0; i < NL; ++i) r2.l[i] = ModR::r2(i);
+  hipLaunchKernelGGL(k_r1cs_flags, grid1(n + 1), dim3(256), 0, c.stream, vals_std, (uint32_t)n, (uint32_t)stride, to_const(relax<2>(r2)), pos);
+  scan_exclusive_dev(c, pos, n + 1, tile_sum);
+  if (cap && n) hipLaunchKernelGGL(k_r1cs_gather, grid1(n), dim3(256), 0, c.stream, vals_std, (uint32_t)n, (uint32_t)stride, pos, (uint32_t)std::min(cap, n), rows, values);
   GS_HIP(hipGetLastError());
 }
 

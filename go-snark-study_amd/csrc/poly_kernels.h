@@ -725,6 +725,34 @@ __global__ void __launch_bounds__(256) k_r1cs_product(uint32_t* __restrict__ val
   if (j >= n) return;
   store_fr(vals + ((size_t)2 * n + j) * 8, mul(mul(load_fr(vals + (size_t)j * 8), load_fr(vals + ((size_t)n + j) * 8)), from_const(r2)));
 }
+// The witness check that names its rows (gs_r1cs_check), over ALL n rows of vals = [a | b | c] (`stride` elements each, standard form,
+// not canonical): flag[j] = (a_j b_j != c_j mod r) for j < n and flag[n] = 0 -- n + 1 words, so that the exclusive prefix sums of the
+// flags end in the count ...
+__global__ void __launch_bounds__(256) k_r1cs_flags(const uint32_t* __restrict__ vals, uint32_t n, uint32_t stride, const FrConst r2, uint32_t* __restrict__ flag) {
+  wave_priority<GS_PRIO_POLY>();
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j > n) return;
+  uint32_t f = 0;
+  if (j < n) {
+    const Fr2 ab = mul(mul(load_fr(vals + (size_t)j * 8), load_fr(vals + ((size_t)stride + j) * 8)), from_const(r2));      // standard a b
+    f = is_zero(sub(ab, load_fr(vals + ((size_t)2 * stride + j) * 8))) ? 0u : 1u;
+  }
+  flag[j] = f;
+}
+// ... and pos = those prefix sums (n + 1 words; row j is violated iff pos[j + 1] != pos[j], and it is violation number pos[j]): the
+// first `cap` violated rows in ascending order, with their three values in canonical standard form.  cap <= the slots of rows / values.
+__global__ void __launch_bounds__(256) k_r1cs_gather(const uint32_t* __restrict__ vals, uint32_t n, uint32_t stride, const uint32_t* __restrict__ pos,
+                                                      uint32_t cap, uint32_t* __restrict__ rows, uint32_t* __restrict__ values) {
+  wave_priority<GS_PRIO_POLY>();
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const uint32_t p = pos[j];
+  if (pos[j + 1] == p || p >= cap) return;             // (p read from memory: never trusted as an index beyond cap)
+  rows[p] = j;
+#pragma unroll
+  for (uint32_t k = 0; k < 3; ++k)
+    store_fr_canon(values + ((size_t)p * 3 + k) * 8, canon(load_fr(vals + ((size_t)k * stride + j) * 8)));
+}
 // Taylor shift, step 1: p[i'] = g[n-1-i'] (n-1-i')! for i' < n, zero padded to N
 __global__ void __launch_bounds__(256) k_hx_shift_in(const uint32_t* __restrict__ g, const uint32_t* __restrict__ fact, uint32_t n, uint32_t N, uint32_t* __restrict__ p) {
   wave_priority<GS_PRIO_POLY>();

@@ -168,6 +168,7 @@ inline Scalars* inout_scalars(Ctx& c, gs_handle* handle, size_t n, const char* w
 }
 // capi_r1cs.hip: w (standard form, m elements, device) -> o.vals = [A w | B w | C w], and -> o.coef = [ax | bx | cx] and px_out
 void r1cs_values_dev(Ctx& c, R1csObj& o, const uint32_t* w_dev);
+void r1cs_values_into_dev(Ctx& c, R1csObj& o, const uint32_t* w_dev, DevBuf& w_mont, DevBuf& vals);      // the same into the caller's workspaces
 void r1cs_px_dev(Ctx& c, R1csObj& o, const uint32_t* w_dev, uint32_t* px_out);
 
 }  // namespace gs

@@ -148,6 +148,9 @@ struct R1csObj : Object {        // sparse R1CS resident on the device: A, B, C 
   size_t n = 0, m = 0, nnz[3] = {0, 0, 0};
   DevBuf rowptr[3], col[3], val[3];
   DevBuf w_mont, vals, coef, prod;       // grow-once workspaces of gs_r1cs_px
+  // grow-once workspaces of gs_r1cs_check alone (never those above: they carry the polynomial stage of the proofs in flight): the
+  // witness in Montgomery form, [A w | B w | C w], the n + 1 flags / positions, the scan's tile sums, the rows and values found
+  DevBuf chk_w_mont, chk_vals, chk_pos, chk_tiles, chk_rows, chk_values;
   // 0: the reference's QAP, row j at the node j + 1.  k >= 1: the QAP over the domain of the 2^k-th roots of unity (domain.h), row j at
   // omega^j, n <= 2^k; the value and coefficient vectors then have 2^k elements each (rows n .. 2^k - 1 are zero).
   int domain_log2 = 0;

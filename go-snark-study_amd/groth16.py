@@ -198,6 +198,13 @@ def GenerateProofsFromWitnessWithRS(circuit, pk, dev_r1cs, w, r, s):
     return _scheme.generate_from_witness(_S, circuit, pk, dev_r1cs, w, (r, s))
 
 
+def GenerateProofsChecked(circuit, pk, dev_r1cs, w, r=None, s=None, check_r1cs=None):
+    """go/groth16hip.GenerateProofsChecked: the witness is checked against ALL constraints of check_r1cs (default: dev_r1cs) first
+    (DeviceR1CS.CheckWitness); a bad one raises r1csqap.WitnessError before anything is proved, a good one is proved from the same
+    resident vector (gs_groth16_prove_witness): the proof of the unchecked call with the same r, s."""
+    return _scheme.generate_checked(_S, circuit, pk, dev_r1cs, w, (FqRRand() if r is None else r, FqRRand() if s is None else s), check_r1cs)
+
+
 class Prover(_scheme.Prover):
     """The streaming drop-in (go/groth16hip.Prover, tests/c/stream_producer.c): one resident key, a NEW witness per Submit, up to three
     proofs in flight, proofs back in submission order.

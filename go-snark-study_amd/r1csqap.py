@@ -143,6 +143,52 @@ def ZPoly(deg):
     return capi.u64_to_ints(capi.zpoly(deg))
 
 
+class WitnessReport:
+    """The outcome of DeviceR1CS.CheckWitness / circom.CheckWtns: truthy only when the witness satisfies every constraint.  `count`:
+    how many of ALL n rows it violates (not the roots of a key's Z, which is what the prover's own count looks at); `rows`: the first
+    `cap` of them, 0-based, ascending; `values`: their (A w, B w, C w) as integers in [0, r)."""
+
+    def __init__(self, count, rows, values, witness=None):
+        self.count, self.rows, self.values = int(count), [int(j) for j in rows], [tuple(int(x) for x in v) for v in values]
+        self._witness = witness
+
+    def __bool__(self):
+        return self.count == 0
+
+    def __repr__(self):
+        if self:
+            return "WitnessReport(every constraint satisfied)"
+        shown = ", ".join(str(j) for j in self.rows[:8]) + (", ..." if self.count > min(len(self.rows), 8) else "")
+        return "WitnessReport(%d violated: rows %s)" % (self.count, shown)
+
+    def explain(self, i, r1cs, w=None):
+        """Host only.  The three linear combinations of the i-th reported row (self.rows[i]) of a parsed circuit (circom.R1cs, or
+        anything with CSR triples a, b, c) -> (A, B, C), each a list of (signal, coefficient, witness value) in the file's order,
+        integers in [0, r).  w: the witness, when the report was not made from integers or a file."""
+        w = self._witness if w is None else w
+        if w is None:
+            raise ValueError("explain: the report was made from a resident vector; pass the witness")
+        j = self.rows[i]
+        out = []
+        for rp, col, val in (r1cs.a, r1cs.b, r1cs.c):
+            if j + 1 >= len(rp):
+                raise ValueError("explain: row %d, the circuit has %d constraints" % (j, len(rp) - 1))
+            lo, hi = int(rp[j]), int(rp[j + 1])
+            coef = capi.u64_to_ints(np.asarray(val).reshape(-1, 4)[lo:hi]) if hi > lo else []
+            sig = [int(s) for s in col[lo:hi]]
+            wv = [int(x) % R for x in (capi.u64_to_ints(np.asarray(w)[sig]) if isinstance(w, np.ndarray) else [w[s] for s in sig])]
+            out.append([(s, c % R, x) for s, c, x in zip(sig, coef, wv)])
+        return tuple(out)
+
+
+class WitnessError(ValueError):
+    """GenerateProofsChecked refused a witness before proving anything: .report is its WitnessReport."""
+
+    def __init__(self, report):
+        super().__init__("the witness violates %d constraint(s): %r" % (report.count, report))
+        self.report = report
+
+
 class DeviceR1CS:
     """A sparse R1CS resident on the device (gs_r1cs_upload): upload once per circuit, then ComputePxResident per proof."""
 
@@ -162,3 +208,16 @@ class DeviceR1CS:
         cell = capi.HandleCell(px_handle)
         capi.call("gs_r1cs_px", capi.raw(self), capi.raw(w_handle), cell.ref)
         return cell.result()
+
+    def CheckWitness(self, w, cap=16):
+        """Which constraints does the witness break (gs_r1cs_check: all n rows, no key, beside proofs in flight)?  -> WitnessReport.
+        w: a resident vector (capi.scalars_upload), or integers / an [nvars, 4] uint64 array, uploaded for the call and freed.  A
+        product system (circom.DeviceZkeyR1CS) holds no C: the library's GS_ERR_SHAPE error comes through unchanged."""
+        resident = isinstance(w, (capi.DeviceHandle, int))
+        dw = w if resident else capi.scalars_upload(capi.u64_rows(w))
+        try:
+            count, rows, values = capi.r1cs_check(self, dw, cap)
+        finally:
+            if not resident:
+                dw.free()
+        return WitnessReport(count, rows, [capi.u64_to_ints(v) for v in values], witness=None if resident else w)

@@ -92,6 +92,12 @@ def GenerateProofsFromWitness(circuit, pk, dev_r1cs, w):
     return _scheme.generate_from_witness(_S, circuit, pk, dev_r1cs, w)
 
 
+def GenerateProofsChecked(circuit, pk, dev_r1cs, w, check_r1cs=None):
+    """go/snarkhip.GenerateProofsChecked: as groth16.GenerateProofsChecked -- a witness that breaks a constraint raises
+    r1csqap.WitnessError before anything is proved."""
+    return _scheme.generate_checked(_S, circuit, pk, dev_r1cs, w, check_r1cs=check_r1cs)
+
+
 class Prover(_scheme.Prover):
     """The streaming drop-in (go/snarkhip.Prover; see groth16.Prover): Submit(w[, px]) / Collect(), three proofs in flight."""
     scheme = _S

@@ -1,8 +1,14 @@
 package gosnarkhip
 
+/*
+#include "gosnark_hip.h"
+*/
+import "C"
+
 import (
 	"errors"
 	"math/big"
+	"runtime"
 )
 
 // CSR is one R1CS matrix (constraints x variables) in compressed sparse rows: what gs_groth16_setup,
@@ -71,4 +77,48 @@ func R1CSFromQAP(polys [][]*big.Int, n int, order *big.Int) [][]*big.Int {
 		}
 	}
 	return out
+}
+
+// WitnessViolations is what R1csCheck found: Count of ALL n constraints are violated; Rows holds the first cap of them, 0-based and
+// ascending, and Values[i] the canonical (A w)_j, (B w)_j, (C w)_j of j = Rows[i].
+type WitnessViolations struct {
+	Count  uint64
+	Rows   []uint32
+	Values [][3]*big.Int
+}
+
+// Ok reports whether the witness satisfies every constraint.
+func (v WitnessViolations) Ok() bool { return v.Count == 0 }
+
+// R1csCheck names the constraints a resident witness (NVars elements) breaks (gs_r1cs_check): every row of the system, not the roots
+// of a key's Z that the prover's own count looks at; no key is needed and nothing is proved.  It runs beside proofs in flight.  cap = 0
+// only counts.  A product system (UploadR1CSZkey) is refused: it holds no C.  C call sequence: tests/c/r1cs_check.c.
+func R1csCheck(q *R1CS, w Handle, cap int) (WitnessViolations, error) {
+	var v WitnessViolations
+	if cap < 0 {
+		return v, errors.New("gosnark-hip: negative cap")
+	}
+	rows := make([]uint32, cap)
+	vals := make([]uint64, 12*cap)
+	var count C.uint64_t
+	err := call(func() C.int {
+		return C.gs_r1cs_check(C.gs_handle(q.h), C.gs_handle(w), C.size_t(cap), &count, ptr32(rows), ptr(vals))
+	})
+	runtime.KeepAlive(rows)
+	runtime.KeepAlive(vals)
+	if err != nil {
+		return v, err
+	}
+	v.Count = uint64(count)
+	k := cap
+	if v.Count < uint64(cap) {
+		k = int(v.Count)
+	}
+	v.Rows = rows[:k]
+	v.Values = make([][3]*big.Int, k)
+	for i := range v.Values {
+		abc := unpackScalars(vals[12*i : 12*i+12])
+		v.Values[i] = [3]*big.Int{abc[0], abc[1], abc[2]}
+	}
+	return v, nil
 }

@@ -242,6 +242,47 @@ func GenerateProofsFromWitnessWithRS(circuit circuitcompiler.Circuit, pk *groth1
 	return proof, err
 }
 
+// WitnessError is what GenerateProofsChecked returns for a witness that breaks a constraint: nothing was proved.
+type WitnessError struct {
+	Violations gosnarkhip.WitnessViolations
+}
+
+func (e *WitnessError) Error() string {
+	return fmt.Sprintf("groth16hip: the witness violates %d constraint(s), first rows %v", e.Violations.Count, e.Violations.Rows)
+}
+
+// GenerateProofsChecked is GenerateProofsFromWitnessWithRS with refusal on request: the witness is uploaded once and checked against
+// ALL constraints of circuit.R1CS (gosnarkhip.R1csCheck, cap 16); a bad one returns *WitnessError before anything is proved, a good
+// one is proved from the same resident vector (gs_groth16_prove_witness).  C call sequence: tests/c/r1cs_check.c, then
+// tests/c/witness_to_proof.c.
+func GenerateProofsChecked(circuit circuitcompiler.Circuit, pk *groth16.Pk, w []*big.Int, r, s *big.Int) (groth16.Proof, error) {
+	var proof groth16.Proof
+	order := groth16.Utils.FqR.Q
+	e, err := deviceKey(circuit, pk)
+	if err != nil {
+		return proof, err
+	}
+	defer unpin(e)
+	q, err := deviceR1CS(circuit, e)
+	if err != nil {
+		return proof, err
+	}
+	dw, err := gosnarkhip.UploadScalars(Device, w, order)
+	if err != nil {
+		return proof, err
+	}
+	defer gosnarkhip.Free(dw)
+	v, err := gosnarkhip.R1csCheck(q, dw, 16)
+	if err != nil {
+		return proof, err
+	}
+	if !v.Ok() {
+		return proof, &WitnessError{v}
+	}
+	proof.PiA, proof.PiB, proof.PiC, err = e.key.ProveWitness(q, dw, r, s, order)
+	return proof, err
+}
+
 // Prover is the STREAMING drop-in: one key, many witnesses, three proofs in flight (cli/main.go:480-501 in a loop).
 //
 //	p, err := groth16hip.NewProver(circuit, pk)

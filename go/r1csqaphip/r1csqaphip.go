@@ -144,3 +144,14 @@ func (pf PolynomialField) DivisorPolynomial(px, z []*big.Int) []*big.Int {
 	q, _ := pf.Div(px, z)
 	return q
 }
+
+// CheckWitness names the constraints of a resident system that the witness w breaks, before anything is proved (gosnarkhip.R1csCheck:
+// all n rows, the first cap of them with their values).  w is uploaded for the call and freed.
+func CheckWitness(q *gosnarkhip.R1CS, w []*big.Int, order *big.Int, cap int) (gosnarkhip.WitnessViolations, error) {
+	dw, err := gosnarkhip.UploadScalars(gosnarkhip.DeviceOf(q.Handle()), w, order)
+	if err != nil {
+		return gosnarkhip.WitnessViolations{}, err
+	}
+	defer gosnarkhip.Free(dw)
+	return gosnarkhip.R1csCheck(q, dw, cap)
+}

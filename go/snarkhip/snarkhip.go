@@ -192,6 +192,48 @@ func GenerateProofsFromWitness(circuit circuitcompiler.Circuit, pk snark.Pk, w [
 	return toProof(p), nil
 }
 
+// WitnessError is what GenerateProofsChecked returns for a witness that breaks a constraint: nothing was proved.
+type WitnessError struct {
+	Violations gosnarkhip.WitnessViolations
+}
+
+func (e *WitnessError) Error() string {
+	return fmt.Sprintf("snarkhip: the witness violates %d constraint(s), first rows %v", e.Violations.Count, e.Violations.Rows)
+}
+
+// GenerateProofsChecked is GenerateProofsFromWitness with refusal on request (see groth16hip.GenerateProofsChecked): the witness is
+// uploaded once, checked against ALL constraints of circuit.R1CS (cap 16), and only a witness that passes is proved, from the same
+// resident vector (gs_pinocchio_prove_witness).
+func GenerateProofsChecked(circuit circuitcompiler.Circuit, pk snark.Pk, w []*big.Int) (snark.Proof, error) {
+	order := snark.Utils.FqR.Q
+	e, err := deviceKey(circuit, &pk)
+	if err != nil {
+		return snark.Proof{}, err
+	}
+	defer unpin(e)
+	q, err := deviceR1CS(circuit, e)
+	if err != nil {
+		return snark.Proof{}, err
+	}
+	dw, err := gosnarkhip.UploadScalars(Device, w, order)
+	if err != nil {
+		return snark.Proof{}, err
+	}
+	defer gosnarkhip.Free(dw)
+	v, err := gosnarkhip.R1csCheck(q, dw, 16)
+	if err != nil {
+		return snark.Proof{}, err
+	}
+	if !v.Ok() {
+		return snark.Proof{}, &WitnessError{v}
+	}
+	p, err := e.key.ProveWitness(q, dw)
+	if err != nil {
+		return snark.Proof{}, err
+	}
+	return toProof(p), nil
+}
+
 // Prover is the streaming drop-in (see groth16hip.Prover): one key, many witnesses, three proofs in flight, proofs back in
 // submission order.  C call sequence: tests/c/stream_producer.c (Groth16 twin) / tests/c/stream_host.c (the Pinocchio tickets).
 type Prover struct {

@@ -187,6 +187,28 @@ int gs_r1cs_upload(size_t n, size_t m,
                    const uint32_t* b_rowptr, const uint32_t* b_col, const uint64_t* b_val,
                    const uint32_t* c_rowptr, const uint32_t* c_col, const uint64_t* c_val, gs_handle* out);
 int gs_r1cs_px(gs_handle r1cs, gs_handle w, gs_handle* px_inout);
+/* Which constraints does a witness break?  gs_r1cs_check needs no key and proves nothing: r1cs is a handle of gs_r1cs_upload or
+ * gs_r1cs_upload_domain, w a resident scalar vector of exactly m elements (any 256-bit words, counted mod r).
+ *   *nviolated                   the number of rows j < n with (A w)_j (B w)_j != (C w)_j mod r;
+ *   rows[0 .. min(cap, count))   the violated rows, 0-based, ascending: the FIRST cap of them;
+ *   values[i] (3 x 4 words)      (A w)_j, (B w)_j, (C w)_j of j = rows[i], canonical standard form; values may be NULL.
+ * Entries at and beyond min(cap, count) are not written; cap = 0 (rows may then be NULL) only counts.
+ * WHAT IS EXAMINED: all n rows of the system.  This is not the prover's criterion: the violated-constraint count of the witness
+ * routes (gs_timing.fallbacks, *violated of gs_*_witness_values) looks at the deg Z roots of the KEY's Z, so for the reference's
+ * m = n + 1 shape, where Z has n - 1 roots and the key does not enforce constraint n, the prover counts 0 for
+ * a witness that breaks only the last row and this call still reports row n - 1.  The padded rows n .. 2^k - 1 of a domain system
+ * are never reported.
+ * Exact for every system the uploads accept and at any n: rows of more than 512 entries are summed by a workgroup each, up to 4096
+ * of them per matrix and the rest by one thread each (slower, the same sums); the positions are exact prefix sums of one word per row.
+ * Errors, nothing written: a product system (gs_r1cs_upload_zkey) is GS_ERR_SHAPE -- a .zkey key's system holds no C, and the check
+ * needs the three matrices of circuit.r1cs --, and so is a w that does not have m elements; a handle of another kind or of another
+ * logical device than r1cs's, a null nviolated, cap > 0 with null rows: GS_ERR_ARG; no device: GS_ERR_NOT_INIT.  No host fallback.
+ * Blocking, but it does NOT wait for outstanding tickets: it works in buffers of its own on the stream of the polynomial stages, beside
+ * the accumulations of the proofs in flight, and waits only for its own work; a gs_scalars_update of w after it returns is safe.
+ * gs_last_timing(): poly_ms = the values stage (copy, Montgomery conversion, three sparse products), reduce_ms = flags, prefix sums
+ * and gather, total_ms = all device time of the call including the result copies. */
+int gs_r1cs_check(gs_handle r1cs, gs_handle w, size_t cap, uint64_t* nviolated, uint32_t* rows /* cap, may be NULL iff cap = 0 */,
+                  uint64_t* values /* cap x 3 x 4 words, may be NULL */);
 /* The same sparse system as a QAP over a POWER-OF-TWO DOMAIN -- what snarkjs / circom Groth16 keys (proving_key.json: polsA/B/C, A,
  * B1, B2, C, hExps) are built on.  m = 2^log2_domain, 1 <= log2_domain <= 27, n <= m constraints; omega = 5^((r-1)/m); row c of the
  * system sits at omega^c (rows n .. m-1 are empty); ax, bx, cx are the interpolants of degree < m, Z = x^m - 1, and
