@@ -133,6 +133,24 @@ def generate_checked(S, circuit, pk, r1cs, w, rs=(), check_r1cs=None):
         dw.free()
 
 
+def generate_from_inputs(S, circuit, pk, r1cs, plan, inputs, rs=()):
+    """From the input values to the proof without a host witness: the witness is solved on the device (plan: r1csqap.SolvePlan of
+    `r1cs`, made once per circuit by r1cs.PlanSolve), checked against ALL constraints -- the plan's check rows are examined by nothing
+    else --, and proved from the same resident vector.  r1csqap.SolveError when variables stay unsolved or a divisor was zero,
+    r1csqap.WitnessError when the solved witness breaks a constraint; nothing is proved then."""
+    dev = resident(S, circuit, pk)
+    (dw,), report = plan.Solve([list(inputs)])
+    try:
+        if not report:
+            raise r1csqap.SolveError(report)
+        check = r1cs.CheckWitness(dw, cap=16)
+        if not check:
+            raise r1csqap.WitnessError(check)
+        return prove(S, "prove_witness", dev, r1cs, dw, rs)
+    finally:
+        dw.free()
+
+
 class Prover:
     """Submit / Collect / Close over one resident key: up to MaxInFlight host-buffer tickets, proofs back in submission order.
     A subclass names its `scheme` and gives _submit its public face."""

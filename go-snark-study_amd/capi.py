@@ -52,6 +52,14 @@ class CheckReport(ctypes.Structure):
     _fields_ = [("nchecks", ctypes.c_uint32), ("failed", ctypes.c_uint32), ("check", CheckResult * CHECK_MAX)]
 
 
+class SolveOpts(ctypes.Structure):
+    _fields_ = [("narrow", ctypes.c_uint32), ("run_max_rows", ctypes.c_uint32)]
+
+
+class SolveStats(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint64) for n in ("solved", "unsolved", "checks", "stuck", "levels", "launches", "wide_launches", "widest_level")]
+
+
 class KeyCheckInput(ctypes.Structure):
     _fields_ = ([(n, Handle) for n in ("a", "b1", "b2", "ic", "c", "h", "key_system", "circuit_system", "tau_g1", "tau_g2", "alpha_tau_g1",
                                        "beta_tau_g1")]
@@ -98,6 +106,10 @@ _SIGS = {
     "gs_r1cs_upload": [ctypes.c_size_t, ctypes.c_size_t, u32p, u32p, u64p, u32p, u32p, u64p, u32p, u32p, u64p, ctypes.POINTER(Handle)],
     "gs_r1cs_px": [Handle, Handle, ctypes.POINTER(Handle)],
     "gs_r1cs_check": [Handle, Handle, ctypes.c_size_t, u64p, u32p, u64p],
+    "gs_r1cs_solve_plan": [Handle, u32p, ctypes.c_size_t, ctypes.POINTER(SolveOpts), ctypes.POINTER(Handle), ctypes.POINTER(SolveStats)],
+    "gs_r1cs_solve_unsolved": [Handle, ctypes.c_size_t, u32p, u64p],
+    "gs_r1cs_solve": [Handle, ctypes.c_size_t, u64p, ctypes.POINTER(Handle), u64p, u32p],
+    "gs_solve_abi_sizes": [ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)],
     "gs_r1cs_upload_domain": [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, u32p, u32p, u64p, u32p, u32p, u64p, u32p, u32p, u64p,
                               ctypes.POINTER(Handle)],
     "gs_groth16_pk_derive_eval_domain": [Handle, ctypes.c_size_t],
@@ -286,6 +298,11 @@ def load_library():
         if ib.value != ctypes.sizeof(KeyCheckInput) or rb.value != ctypes.sizeof(CheckReport):
             raise GosnarkHipError(-1, "%s takes gs_key_check_input / gs_check_report of %d / %d bytes, this binding expects %d / %d: rebuild the library"
                                   % (path, ib.value, rb.value, ctypes.sizeof(KeyCheckInput), ctypes.sizeof(CheckReport)))
+        ob, sb = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        lib.gs_solve_abi_sizes(ctypes.byref(ob), ctypes.byref(sb))
+        if ob.value != ctypes.sizeof(SolveOpts) or sb.value != ctypes.sizeof(SolveStats):
+            raise GosnarkHipError(-1, "%s takes gs_solve_opts / gs_solve_stats of %d / %d bytes, this binding expects %d / %d: rebuild the library"
+                                  % (path, ob.value, sb.value, ctypes.sizeof(SolveOpts), ctypes.sizeof(SolveStats)))
         _LIB = lib
         return lib
 
@@ -611,6 +628,44 @@ def r1cs_check(r1cs, w, cap=16):
     call("gs_r1cs_check", raw(r1cs), raw(w), cap, ctypes.byref(count), ptr32(rows) if cap else None, ptr64(values) if cap else None)
     k = min(cap, int(count.value))
     return int(count.value), rows[:k], values[:k]
+
+
+NO_FAILED_ROW = 0xFFFFFFFF
+
+
+def r1cs_solve_plan(r1cs, input_vars, narrow=0, run_max_rows=0):
+    """gs_r1cs_solve_plan: the level plan of a resident three-matrix R1CS for the given input variables -> (plan handle, SolveStats)."""
+    iv = np.ascontiguousarray([int(v) for v in input_vars], dtype=np.uint32)
+    opts, stats, cell = SolveOpts(int(narrow), int(run_max_rows)), SolveStats(), HandleCell()
+    call("gs_r1cs_solve_plan", raw(r1cs), ptr32(iv) if iv.size else None, iv.size, ctypes.byref(opts), cell.ref, ctypes.byref(stats))
+    return cell.result(), stats
+
+
+def r1cs_solve_unsolved(plan):
+    """gs_r1cs_solve_unsolved: the variables no row defines, ascending."""
+    count = ctypes.c_uint64(0)
+    call("gs_r1cs_solve_unsolved", raw(plan), 0, None, ctypes.byref(count))
+    out = np.zeros(int(count.value), dtype=np.uint32)
+    if out.size:
+        call("gs_r1cs_solve_unsolved", raw(plan), out.size, ptr32(out), ctypes.byref(count))
+    return [int(v) for v in out]
+
+
+def r1cs_solve(plan, inputs, into=None):
+    """gs_r1cs_solve: inputs = one list of integers (any value below 2^256, counted mod r) per witness, in the plan's input order;
+    into = None, or one resident vector (or None) per witness to overwrite -> (handles, nfailed list, first_failed_row list with None
+    for 'none')."""
+    nwit = len(inputs)
+    flat = [int(v) for row in inputs for v in row]
+    iw = ints_to_u64(flat) if flat else np.zeros((1, 4), dtype=np.uint64)
+    into = [None] * nwit if into is None else list(into)
+    if len(into) != nwit:
+        raise ValueError("gs_r1cs_solve: %d witnesses but %d vectors to overwrite" % (nwit, len(into)))
+    handles = harr(into) if nwit else (Handle * 1)()
+    nfailed, first = np.zeros(max(nwit, 1), dtype=np.uint64), np.zeros(max(nwit, 1), dtype=np.uint32)
+    call("gs_r1cs_solve", raw(plan), nwit, ptr64(iw), handles, ptr64(nfailed), ptr32(first))
+    out = [x if x is not None else DeviceHandle(handles[b]) for b, x in enumerate(into)]
+    return out, [int(x) for x in nfailed[:nwit]], [None if int(x) == NO_FAILED_ROW else int(x) for x in first[:nwit]]
 
 
 def g1_scale(bases, k):

@@ -48,6 +48,11 @@ uint64_t object_bytes(Object* o) {
       for (int i = 0; i < 3; ++i) t += r->rowptr[i].bytes + r->col[i].bytes + r->val[i].bytes;
       return t;
     }
+    case Kind::SolvePlan: {              // the plan's own arrays and workspaces (its system is counted under the system's handle)
+      auto* p = static_cast<SolvePlanObj*>(o);
+      return p->rows.bytes + p->targets.bytes + p->forms.bytes + p->elems.bytes + p->input_vars.bytes + p->ws_ptrs.bytes + p->ws_inputs.bytes +
+             p->ws_fail.bytes;
+    }
     default: break;
   }
   return 0;

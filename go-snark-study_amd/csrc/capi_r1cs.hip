@@ -2,6 +2,8 @@
 #include "prove.h"
 #include "domain.h"
 #include "scan.h"
+#include "r1cs_solve.h"
+#include "solve_plan.h"
 
 #include <algorithm>
 
@@ -223,6 +225,182 @@ int gs_r1cs_check(gs_handle hr1cs, gs_handle hw, size_t cap, uint64_t* nviolated
     c.timing.total_ms = total.ms();                           // with the result copies: gs_timing has no field for them
     return GS_OK;
   }, true, true, hr1cs);
+}
+
+// ---- witnesses solved from the system (include/gosnark_hip.h; solve_plan.h, r1cs_solve.hip) -----------------------------------------
+// The plan is made on the host from the system's CSR arrays, which are read back from the device once, here (uploads keep no host
+// copy: most systems are never solved).  The arrays are immutable after the upload, so the copies need no ordering against proofs in
+// flight; they go on the polynomial stream like everything else of the solver.
+int gs_r1cs_solve_plan(gs_handle hr1cs, const uint32_t* input_vars, size_t ninputs, const gs_solve_opts* opts, gs_handle* plan_out,
+                       gs_solve_stats* stats) {
+  return guarded([&](Ctx& c) -> int {
+    const char* fn = "gs_r1cs_solve_plan";
+    if (!plan_out) return fail(GS_ERR_ARG, "%s: null plan", fn);
+    if (ninputs && !input_vars) return fail(GS_ERR_ARG, "%s: ninputs = %zu but input_vars is null", fn, ninputs);
+    std::shared_ptr<R1csObj> o = c.share<R1csObj>(hr1cs, Kind::R1cs);
+    if (!o) return fail(GS_ERR_ARG, "%s: bad handle (an R1CS)", fn);
+    if (o->product)
+      return fail(GS_ERR_SHAPE, "%s: a .zkey key's system holds A and B only, no C (c = a b by definition): the solver needs the three "
+                                "matrices of circuit.r1cs (gs_r1cs_upload / gs_r1cs_upload_domain)", fn);
+    const size_t n = o->n, m = o->m;
+    StreamScope sc(c, c.aux_stream[1]);
+    std::vector<uint32_t> rp[3], cl[3];
+    std::vector<uint64_t> vl[3];
+    SolveCsr mat[3];
+    for (int k = 0; k < 3; ++k) {
+      const size_t nnz = o->nnz[k];
+      rp[k].resize(n + 1); cl[k].resize(std::max<size_t>(nnz, 1)); vl[k].resize(std::max<size_t>(nnz, 1) * 4);
+      GS_HIP(hipMemcpyAsync(rp[k].data(), o->rowptr[k].p, (n + 1) * 4, hipMemcpyDeviceToHost, c.stream));
+      if (nnz) {
+        GS_HIP(hipMemcpyAsync(cl[k].data(), o->col[k].p, nnz * 4, hipMemcpyDeviceToHost, c.stream));
+        GS_HIP(hipMemcpyAsync(vl[k].data(), o->val[k].p, nnz * 32, hipMemcpyDeviceToHost, c.stream));
+      }
+      mat[k] = SolveCsr{rp[k].data(), cl[k].data(), vl[k].data()};
+    }
+    GS_HIP(hipStreamSynchronize(c.stream));
+    SolvePlan hp;
+    size_t bad = 0;
+    switch (plan_solve_levels(mat, n, m, input_vars, ninputs, hp, &bad)) {
+      case kSpOk: break;
+      case kSpInputRange: return fail(GS_ERR_ARG, "%s: input_vars[%zu] = %u but the system has %zu variables", fn, bad, input_vars[bad], m);
+      case kSpInputZero: return fail(GS_ERR_ARG, "%s: input_vars[%zu] = 0: variable 0 is the constant one, not an input", fn, bad);
+      case kSpInputTwice: return fail(GS_ERR_ARG, "%s: input_vars[%zu] = %u is listed twice", fn, bad, input_vars[bad]);
+    }
+    auto p = std::make_unique<SolvePlanObj>();
+    p->sys = o;
+    p->ninputs = ninputs;
+    const size_t ns = p->nsolved = hp.entries.size();
+    SolveOptions so;
+    if (opts) { so.narrow = opts->narrow; so.run_max_rows = opts->run_max_rows; }
+    std::vector<SolveLaunch> launches;
+    plan_solve_launches(hp.level_off, so, launches);
+    std::vector<uint32_t> targets(ns), forms(ns), elems(ns * 8);
+    p->host_rows.resize(ns);
+    for (size_t i = 0; i < ns; ++i) {
+      p->host_rows[i] = hp.entries[i].row; targets[i] = hp.entries[i].target; forms[i] = hp.entries[i].form;
+      memcpy(&elems[i * 8], hp.entries[i].elem, 32);
+    }
+    p->rows.alloc(ns * 4); p->targets.alloc(ns * 4); p->forms.alloc(ns * 4); p->elems.alloc(ns * 32);
+    p->input_vars.alloc(ninputs * 4);
+    if (ns) {
+      GS_HIP(hipMemcpyAsync(p->rows.p, p->host_rows.data(), ns * 4, hipMemcpyHostToDevice, c.stream));
+      GS_HIP(hipMemcpyAsync(p->targets.p, targets.data(), ns * 4, hipMemcpyHostToDevice, c.stream));
+      GS_HIP(hipMemcpyAsync(p->forms.p, forms.data(), ns * 4, hipMemcpyHostToDevice, c.stream));
+      GS_HIP(hipMemcpyAsync(p->elems.p, elems.data(), ns * 32, hipMemcpyHostToDevice, c.stream));
+    }
+    if (ninputs) GS_HIP(hipMemcpyAsync(p->input_vars.p, input_vars, ninputs * 4, hipMemcpyHostToDevice, c.stream));
+    GS_HIP(hipStreamSynchronize(c.stream));
+    gs_solve_stats& st = p->stats;
+    st.solved = ns; st.unsolved = hp.unsolved.size(); st.checks = hp.checks; st.stuck = hp.stuck;
+    st.levels = hp.level_off.size() - 1; st.launches = launches.size();
+    for (const SolveLaunch& l : launches) {
+      p->launches.push_back(SolvePlanObj::Launch{l.lo, l.hi, l.run});
+      st.wide_launches += !l.run;
+    }
+    for (size_t l = 0; l + 1 < hp.level_off.size(); ++l) st.widest_level = std::max<uint64_t>(st.widest_level, hp.level_off[l + 1] - hp.level_off[l]);
+    p->unsolved = std::move(hp.unsolved);
+    if (stats) *stats = st;
+    *plan_out = c.put(std::move(p));
+    return GS_OK;
+  }, true, true, hr1cs);
+}
+
+int gs_r1cs_solve_unsolved(gs_handle hplan, size_t cap, uint32_t* vars, uint64_t* count) {
+  return guarded([&](Ctx& c) -> int {
+    const char* fn = "gs_r1cs_solve_unsolved";
+    SolvePlanObj* p = c.get<SolvePlanObj>(hplan, Kind::SolvePlan);
+    if (!p) return fail(GS_ERR_ARG, "%s: bad handle (a plan of gs_r1cs_solve_plan)", fn);
+    if (!count) return fail(GS_ERR_ARG, "%s: null count", fn);
+    if (cap && !vars) return fail(GS_ERR_ARG, "%s: cap = %zu but vars is null", fn, cap);
+    const size_t k = std::min(cap, p->unsolved.size());
+    if (k) memcpy(vars, p->unsolved.data(), k * 4);
+    *count = p->unsolved.size();
+    return GS_OK;
+  }, true, true, hplan);
+}
+
+// Runs beside proofs in flight like gs_r1cs_check: on the polynomial stream, in workspaces the plan owns, waiting only for itself.
+// The vectors it overwrites may still be read by pipelined operations: the stream first waits for their read marks (runtime.h,
+// Scalars), as gs_scalars_update's copy does.  When the call returns the device has finished with every vector, so it leaves no mark.
+int gs_r1cs_solve(gs_handle hplan, size_t nwit, const uint64_t* inputs, gs_handle* w_inout, uint64_t* nfailed, uint32_t* first_failed_row) {
+  return guarded([&](Ctx& c) -> int {
+    const char* fn = "gs_r1cs_solve";
+    SolvePlanObj* p = c.get<SolvePlanObj>(hplan, Kind::SolvePlan);
+    if (!p) return fail(GS_ERR_ARG, "%s: bad handle (a plan of gs_r1cs_solve_plan)", fn);
+    if (!nwit || nwit >= (1ull << 31)) return fail(GS_ERR_ARG, "%s: nwit = %zu", fn, nwit);
+    if (!w_inout || !nfailed || !first_failed_row || (p->ninputs && !inputs)) return fail(GS_ERR_ARG, "%s: null argument", fn);
+    R1csObj& o = *p->sys;
+    const size_t m = o.m;
+    std::vector<Scalars*> vec(nwit, nullptr);
+    for (size_t b = 0; b < nwit; ++b) {
+      if (!w_inout[b]) continue;
+      vec[b] = c.get<Scalars>(w_inout[b], Kind::Scalars);
+      if (!vec[b]) return fail(GS_ERR_ARG, "%s: w_inout[%zu] is not a scalar vector of the plan's logical device", fn, b);
+      if (vec[b]->n != m) return fail(GS_ERR_SHAPE, "%s: w_inout[%zu] holds %zu elements but the system has %zu variables", fn, b, vec[b]->n, m);
+    }
+    {
+      std::vector<Scalars*> sorted;
+      for (Scalars* s : vec) if (s) sorted.push_back(s);
+      std::sort(sorted.begin(), sorted.end());
+      if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return fail(GS_ERR_ARG, "%s: a vector is listed twice in w_inout", fn);
+    }
+    // every allocation before the first handle is given out: a call that fails for memory leaves w_inout as it was
+    std::vector<std::unique_ptr<Scalars>> fresh;
+    for (size_t b = 0; b < nwit; ++b) {
+      if (vec[b]) continue;
+      fresh.push_back(std::make_unique<Scalars>());
+      fresh.back()->n = m;
+      fresh.back()->buf.alloc(m * 32);
+      vec[b] = fresh.back().get();
+    }
+    p->ws_ptrs.ensure(nwit * sizeof(uint32_t*));
+    p->ws_fail.ensure(nwit * 8);
+    p->ws_inputs.ensure(std::max<size_t>(nwit * p->ninputs, 1) * 32);
+    std::vector<uint32_t*> ptrs(nwit);
+    for (size_t b = 0; b < nwit; ++b) ptrs[b] = vec[b]->buf.as<uint32_t>();
+    std::vector<uint32_t> fail_host(nwit * 2);
+
+    StreamScope sc(c, c.aux_stream[1]);
+    for (Scalars* s : vec) for (auto& r : s->reads) GS_HIP(hipStreamWaitEvent(c.stream, r.ev, 0));
+    PhaseTimer total(c.stream), th(c.stream);
+    GS_HIP(hipMemcpyAsync(p->ws_ptrs.p, ptrs.data(), nwit * sizeof(uint32_t*), hipMemcpyHostToDevice, c.stream));
+    if (p->ninputs) GS_HIP(hipMemcpyAsync(p->ws_inputs.p, inputs, nwit * p->ninputs * 32, hipMemcpyHostToDevice, c.stream));
+    th.stop();
+    uint32_t* const* wtab = p->ws_ptrs.as<uint32_t*>();
+    uint32_t* fail_dev = p->ws_fail.as<uint32_t>();
+    SolveDev d;
+    for (int k = 0; k < 3; ++k) { d.rowptr[k] = o.rowptr[k].as<uint32_t>(); d.col[k] = o.col[k].as<uint32_t>(); d.val[k] = o.val[k].as<uint32_t>(); }
+    d.rows = p->rows.as<uint32_t>(); d.targets = p->targets.as<uint32_t>(); d.forms = p->forms.as<uint32_t>(); d.elems = p->elems.as<uint32_t>();
+    d.m = (uint32_t)m;
+    PhaseTimer tsolve(c.stream);
+    solve_begin_dev(c, wtab, nwit, m, p->ws_inputs.as<uint32_t>(), p->input_vars.as<uint32_t>(), p->ninputs, fail_dev);
+    for (const SolvePlanObj::Launch& l : p->launches) {
+      if (l.run) solve_run_dev(c, d, l.lo, l.hi, wtab, nwit, fail_dev);
+      else solve_level_dev(c, d, l.lo, l.hi, wtab, nwit, fail_dev);
+    }
+    solve_finish_dev(c, wtab, nwit, m);
+    tsolve.stop();
+    GS_HIP(hipMemcpyAsync(fail_host.data(), fail_dev, nwit * 8, hipMemcpyDeviceToHost, c.stream));
+    total.stop();
+    GS_HIP(hipStreamSynchronize(c.stream));
+    for (size_t b = 0, f = 0; b < nwit; ++b) {
+      nfailed[b] = fail_host[2 * b];
+      const uint32_t pos = fail_host[2 * b + 1];
+      first_failed_row[b] = pos < p->host_rows.size() ? p->host_rows[pos] : 0xffffffffu;
+      if (!w_inout[b]) w_inout[b] = c.put(std::move(fresh[f++]));
+    }
+    if (!c.any_inflight()) reset_timing(c);
+    c.timing.h2d_ms = th.ms();
+    c.timing.poly_ms = tsolve.ms();
+    c.timing.total_ms = total.ms();
+    return GS_OK;
+  }, true, true, hplan);
+}
+
+int gs_solve_abi_sizes(size_t* opts_bytes, size_t* stats_bytes) {
+  if (opts_bytes) *opts_bytes = sizeof(gs_solve_opts);
+  if (stats_bytes) *stats_bytes = sizeof(gs_solve_stats);
+  return GS_OK;
 }
 
 }  // extern "C"

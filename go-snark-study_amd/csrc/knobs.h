@@ -9,6 +9,7 @@
 //    multiple of `multiple_of`, not a power of two where one is needed -- falls back to the default instead of being used.
 #pragma once
 #include <cerrno>
+#include <cstdint>
 #include <cstdlib>
 
 namespace gs {
@@ -44,6 +45,20 @@ inline long acc_group_forced(bool g2) {                 // read once per process
   static const long g1_v = acc_group_env("GS_ACC_GROUP_G1"), g2_v = acc_group_env("GS_ACC_GROUP_G2");
   return g2 ? g2_v : g1_v;
 }
+
+// The schedule of gs_r1cs_solve (solve_plan.h), when gs_solve_opts leaves a field 0.  Levels narrower than kSolveNarrow rows merge into
+// sequential runs (k_solve_run: one thread per witness walks them in order), cut every kSolveRunMaxRows rows.
+// Measured on one MI355X (profiles/r1cs_solve_timing.txt, tools/time_r1cs_solve.py), one witness: one dependent row in k_solve_run
+// takes 6.78 us on sqchain 2^16 and 6.51 us on sqchain 2^12 (a chain of dependent loads -- plan entry, row pointers, entries, the
+// element the row before stored -- and some ten field multiplications, in ONE wave with nothing to hide them behind); the same 2^12
+// chain with every row a launch of its own takes 8.33 us per launch, so a launch boundary costs 1.82 us (the ABI cannot enqueue an
+// empty level; the difference on one chain stands for the gap between two launches).  The ratio gap / row is 0.28: rounded to a power
+// of two it is below one row, i.e. a launch of its own is cheaper than a run for every level of two rows or more (8.3 us against
+// 13 us and up), and only a level of ONE row is cheaper inside a run (6.5 us against 8.3 us).  Hence kSolveNarrow = 2: the smallest
+// value that still merges anything.  kSolveRunMaxRows keeps one launch under 50 ms: 50 ms / 6.78 us = 7379 rows, as a power of two
+// 4096 (28 ms).
+constexpr uint32_t kSolveNarrow = 2;
+constexpr uint32_t kSolveRunMaxRows = 1u << 12;
 
 #ifdef GS_DEV_KNOBS
 inline bool dev_flag(const char* name) { return getenv(name) != nullptr; }

@@ -121,7 +121,7 @@ struct DevBuf {
 };
 
 // ---- handle table ---------------------------------------------------------------------------------
-enum class Kind : uint32_t { G1Bases = 1, G2Bases, Scalars, GrothPk, PinocchioPk, R1cs, GrothVk };
+enum class Kind : uint32_t { G1Bases = 1, G2Bases, Scalars, GrothPk, PinocchioPk, R1cs, GrothVk, SolvePlan };
 
 struct Object {
   Kind kind;
@@ -160,6 +160,22 @@ struct R1csObj : Object {        // sparse R1CS resident on the device: A, B, C 
   size_t points() const { return domain_log2 ? (size_t)1 << domain_log2 : n; }      // elements per value / coefficient vector
   size_t npx() const { return 2 * points() - 1; }                                    // coefficients of px = ax bx - cx
   R1csObj() : Object(Kind::R1cs) {}
+};
+// The level plan of gs_r1cs_solve_plan (solve_plan.h), resident: one entry per solved row, in solve order.  The plan reads its system's
+// CSR arrays in every solve, so it keeps the system alive (gs_free of the R1CS handle is then deferred to the plan's).
+struct SolvePlanObj : Object {
+  std::shared_ptr<R1csObj> sys;
+  size_t ninputs = 0, nsolved = 0;
+  DevBuf rows, targets, forms, elems;    // nsolved x u32 | u32 | u32 | 8 u32 (Montgomery): the plan in solve order
+  DevBuf input_vars;                     // ninputs x u32
+  std::vector<uint32_t> host_rows;       // position -> row, for first_failed_row
+  std::vector<uint32_t> unsolved;        // ascending
+  struct Launch { uint32_t lo, hi; bool run; };
+  std::vector<Launch> launches;
+  gs_solve_stats stats{};
+  // grow-once workspaces of gs_r1cs_solve: the table of witness pointers, the inputs, per witness [failure count | first position]
+  DevBuf ws_ptrs, ws_inputs, ws_fail;
+  SolvePlanObj() : Object(Kind::SolvePlan) {}
 };
 struct Scalars : Object {        // n x 8 u32 words, standard form, resident
   DevBuf buf;

@@ -205,6 +205,13 @@ def GenerateProofsChecked(circuit, pk, dev_r1cs, w, r=None, s=None, check_r1cs=N
     return _scheme.generate_checked(_S, circuit, pk, dev_r1cs, w, (FqRRand() if r is None else r, FqRRand() if s is None else s), check_r1cs)
 
 
+def GenerateProofsFromInputs(circuit, pk, dev_r1cs, plan, inputs, r=None, s=None):
+    """go/gosnarkhip R1csSolve + GenerateProofsChecked: the witness is SOLVED on the device from the values of the plan's input variables
+    (plan = dev_r1cs.PlanSolve(input_vars), once per circuit), checked against all constraints and proved from the same resident
+    vector.  r1csqap.SolveError: variables stay unsolved or a divisor was zero; r1csqap.WitnessError: a check row is broken."""
+    return _scheme.generate_from_inputs(_S, circuit, pk, dev_r1cs, plan, inputs, (FqRRand() if r is None else r, FqRRand() if s is None else s))
+
+
 class Prover(_scheme.Prover):
     """The streaming drop-in (go/groth16hip.Prover, tests/c/stream_producer.c): one resident key, a NEW witness per Submit, up to three
     proofs in flight, proofs back in submission order.

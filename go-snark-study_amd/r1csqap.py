@@ -221,3 +221,60 @@ class DeviceR1CS:
             if not resident:
                 dw.free()
         return WitnessReport(count, rows, [capi.u64_to_ints(v) for v in values], witness=None if resident else w)
+
+    def PlanSolve(self, input_vars, narrow=0, run_max_rows=0):
+        """gs_r1cs_solve_plan: how to solve this system's witnesses from the values of `input_vars` (variable 0, the constant one, is
+        never an input) -> SolvePlan.  Once per circuit; narrow / run_max_rows = 0 take the library's defaults."""
+        return SolvePlan(self, input_vars, narrow, run_max_rows)
+
+
+class SolveReport:
+    """The outcome of SolvePlan.Solve: truthy only when every variable was solved and no divisor was zero.  `unsolved`: the variables
+    no row defines (they are 0 in every witness); `nfailed[b]`: the rows of witness b whose divisor was zero (their target is 0);
+    `first_failed_row[b]`: the first of them in solve order, or None."""
+
+    def __init__(self, unsolved, nfailed, first_failed_row):
+        self.unsolved, self.nfailed, self.first_failed_row = list(unsolved), list(nfailed), list(first_failed_row)
+
+    def __bool__(self):
+        return not self.unsolved and not any(self.nfailed)
+
+    def __repr__(self):
+        if self:
+            return "SolveReport(%d witnesses solved)" % len(self.nfailed)
+        bad = [b for b, k in enumerate(self.nfailed) if k]
+        return "SolveReport(%d variables unsolved; zero divisor in witnesses %s)" % (len(self.unsolved), bad[:8])
+
+
+class SolveError(ValueError):
+    """GenerateProofsFromInputs could not make the witnesses: variables stay unsolved or a divisor was zero.  .report is the SolveReport."""
+
+    def __init__(self, report):
+        super().__init__("the system does not determine the witness: %r" % (report,))
+        self.report = report
+
+
+class SolvePlan:
+    """The level plan of a DeviceR1CS for one list of input variables (gs_r1cs_solve_plan).  .stats: solved, unsolved, checks, stuck,
+    levels, launches, wide_launches, widest_level.  The plan keeps its system alive on the device."""
+
+    def __init__(self, r1cs, input_vars, narrow=0, run_max_rows=0):
+        self.r1cs, self.input_vars = r1cs, [int(v) for v in input_vars]
+        self.handle, st = capi.r1cs_solve_plan(r1cs, self.input_vars, narrow, run_max_rows)
+        self.stats = {name: int(getattr(st, name)) for name, _ in st._fields_}
+        self._unsolved = None
+
+    def unsolved(self):
+        if self._unsolved is None:
+            self._unsolved = capi.r1cs_solve_unsolved(self.handle)
+        return list(self._unsolved)
+
+    def Solve(self, inputs, into=None):
+        """inputs: one list of len(input_vars) integers per witness (any value below 2^256, counted mod r).  into: None, or one resident
+        vector of nvars elements (or None) per witness to overwrite.  -> (resident witness handles, SolveReport).  The plan's check
+        rows are not examined here: DeviceR1CS.CheckWitness does that."""
+        for row in inputs:
+            if len(row) != len(self.input_vars):
+                raise ValueError("Solve: %d values for %d input variables" % (len(row), len(self.input_vars)))
+        handles, nfailed, first = capi.r1cs_solve(self.handle, inputs, into)
+        return handles, SolveReport(self.unsolved(), nfailed, first)

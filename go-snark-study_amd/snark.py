@@ -98,6 +98,11 @@ def GenerateProofsChecked(circuit, pk, dev_r1cs, w, check_r1cs=None):
     return _scheme.generate_checked(_S, circuit, pk, dev_r1cs, w, check_r1cs=check_r1cs)
 
 
+def GenerateProofsFromInputs(circuit, pk, dev_r1cs, plan, inputs):
+    """As groth16.GenerateProofsFromInputs: the witness is solved on the device from the plan's input values, checked, then proved."""
+    return _scheme.generate_from_inputs(_S, circuit, pk, dev_r1cs, plan, inputs)
+
+
 class Prover(_scheme.Prover):
     """The streaming drop-in (go/snarkhip.Prover; see groth16.Prover): Submit(w[, px]) / Collect(), three proofs in flight."""
     scheme = _S

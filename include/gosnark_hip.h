@@ -209,6 +209,50 @@ int gs_r1cs_px(gs_handle r1cs, gs_handle w, gs_handle* px_inout);
  * and gather, total_ms = all device time of the call including the result copies. */
 int gs_r1cs_check(gs_handle r1cs, gs_handle w, size_t cap, uint64_t* nviolated, uint32_t* rows /* cap, may be NULL iff cap = 0 */,
                   uint64_t* values /* cap x 3 x 4 words, may be NULL */);
+/* Solving witnesses FROM the system.  For the systems the reference's compiler emits every row holds one flattened gate whose `out`
+ * sits alone in C (or alone in A / B for a division), so each row defines one new signal from earlier ones: a sparse triangular
+ * solve, wide where circuits are wide and independent over the witnesses of one circuit.
+ * gs_r1cs_solve_plan builds the level plan ONCE per (system, input variables) on the host (csrc/solve_plan.h holds the definition:
+ * known_0 = {0} + inputs; level l takes every unused row with exactly one distinct variable outside known_(l-1) whose summed
+ * coefficient is nonzero in exactly one matrix; lowest row wins a tie; rows left over whose variables all became known are CHECKS,
+ * which the solve does not examine -- gs_r1cs_check does).  input_vars: ninputs distinct variables in 1 .. m-1 (variable 0 is the
+ * constant one), in the order gs_r1cs_solve's values come in.  opts (may be NULL; a 0 field means the default of csrc/knobs.h):
+ * levels narrower than `narrow` rows merge into sequential runs of at most `run_max_rows` rows, one launch each; every other level
+ * is one launch.  *stats is optional.  The plan handle keeps its system alive; gs_free releases it.  The system's matrices are read
+ * back from the device once, here.
+ * gs_r1cs_solve_unsolved: *count = how many variables no row defines; vars[0 .. min(cap, count)) = the first of them, ascending.
+ * gs_r1cs_solve: nwit witnesses in one set of launches.  inputs[b][k] (4 words, any 256-bit value, counted mod r) is input_vars[k] of
+ * witness b.  w_inout[b]: 0 to create a vector of m elements, or a resident vector of exactly m elements to overwrite (the call
+ * first waits for the reads pipelined operations still have on it, like gs_scalars_update).  Result: canonical standard form in
+ * [0, r) -- what gs_scalars_upload of the integers would hold --, unsolved variables 0.  A row whose divisor is zero for a witness
+ * stores 0 for that witness and goes on: nfailed[b] counts such rows, first_failed_row[b] is the first of them in solve order
+ * (0xFFFFFFFF = none); both arrays are required and the call still returns GS_OK.
+ * A row of more than 512 entries is walked by one thread: slow, the same sums.
+ * Errors, nothing written (no output, no vector): a product system (gs_r1cs_upload_zkey) is GS_ERR_SHAPE, in gs_r1cs_check's words;
+ * an input variable that is 0, >= m or listed twice, a handle of another kind, a null argument, nwit = 0: GS_ERR_ARG; an overwrite
+ * vector that does not hold m elements: GS_ERR_SHAPE; no device: GS_ERR_NOT_INIT.  No host fallback.
+ * Blocking, but like gs_r1cs_check it does not wait for outstanding tickets: the stream of the polynomial stages, workspaces of its own.
+ * gs_last_timing(): h2d_ms = the inputs' copy, poly_ms = the level and run launches, total_ms = all device time of the call. */
+typedef struct {
+  uint32_t narrow;                  /* levels of fewer rows merge into runs; 0 = default */
+  uint32_t run_max_rows;            /* a run is cut every so many rows; 0 = default */
+} gs_solve_opts;
+typedef struct {
+  uint64_t solved;                  /* rows that define a variable = variables solved */
+  uint64_t unsolved;                /* variables no row defines (inputs and variable 0 are not counted) */
+  uint64_t checks;                  /* rows that define nothing and whose variables are all known */
+  uint64_t stuck;                   /* rows with a variable that stays unsolved */
+  uint64_t levels;
+  uint64_t launches;                /* wide launches + runs */
+  uint64_t wide_launches;
+  uint64_t widest_level;            /* rows */
+} gs_solve_stats;
+int gs_r1cs_solve_plan(gs_handle r1cs, const uint32_t* input_vars, size_t ninputs, const gs_solve_opts* opts /* may be NULL */,
+                       gs_handle* plan, gs_solve_stats* stats /* may be NULL */);
+int gs_r1cs_solve_unsolved(gs_handle plan, size_t cap, uint32_t* vars /* cap, may be NULL iff cap = 0 */, uint64_t* count);
+int gs_r1cs_solve(gs_handle plan, size_t nwit, const uint64_t* inputs /* nwit x ninputs x 4 words */, gs_handle* w_inout /* nwit */,
+                  uint64_t* nfailed /* nwit */, uint32_t* first_failed_row /* nwit */);
+int gs_solve_abi_sizes(size_t* opts_bytes, size_t* stats_bytes);
 /* The same sparse system as a QAP over a POWER-OF-TWO DOMAIN -- what snarkjs / circom Groth16 keys (proving_key.json: polsA/B/C, A,
  * B1, B2, C, hExps) are built on.  m = 2^log2_domain, 1 <= log2_domain <= 27, n <= m constraints; omega = 5^((r-1)/m); row c of the
  * system sits at omega^c (rows n .. m-1 are empty); ax, bx, cx are the interpolants of degree < m, Z = x^m - 1, and
